@@ -17,6 +17,12 @@ sequence, no data-path collective; --distinct-sequences gives rank r sequence r)
 over RCCL every --gather-every frames, asynchronously; `value` = frames tracked by all ranks / max-over-ranks wall time.
 
 Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: it renders the drive, warms up, times --steps steps, writes the last timed step's
+outputs when --dump-outputs DIR is given, and prints the line. Everything else — the CPU baseline and the oracle comparisons, the
+unannounced second pass, tracking error and determinism checks, the side legs (stress / saturated drives, dense 1080p, disparity,
+single pair, shim, batched sequences), configs[3] of N > 1 runs and the roofline figures that take launches of their own — runs
+only with --full.
 """
 import argparse
 import gc
@@ -891,6 +897,23 @@ def configs3_leg(api, seqs, my_ids, n_sequences, world, rank, local_rank, backen
                      "(odo_tracker_batch), schedule-based pose gather" % (n_sequences, world))
 
 
+def dump_outputs(path, trk, poses_kf, poses_abs, kf_flags=None, depth_shape=None):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy (float32, ~6 MB): pose_to_keyframe and abs_pose
+    of every sequence this rank tracked (n x 4 x 4, row-major), the new-keyframe flags (n), and for one sequence on the single tracker
+    that frame's depth outputs (odo_tracker_outputs: validity mask, disparity, inverse depth). The inputs are the seeded synthetic
+    drive, so two builds run with the same arguments can be compared array for array."""
+    os.makedirs(path, exist_ok=True)
+    n = poses_kf.shape[0]
+    arrays = dict(pose_to_keyframe=poses_kf.reshape(n, 4, 4).transpose(0, 2, 1), abs_pose=poses_abs.reshape(n, 4, 4).transpose(0, 2, 1))
+    if kf_flags is not None:
+        arrays["new_keyframe"] = kf_flags
+    if depth_shape is not None:
+        trk._sync()
+        arrays.update(zip(("depth_valid", "disparity", "inverse_depth"), trk.outputs(*depth_shape)))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, np.float32))
+
+
 COMPACT_MAX_BYTES = 4096   # the driver reads the LAST stdout line; round 5's 21 KB line came back unparsed
 
 
@@ -1133,6 +1156,12 @@ def main():
                     help="file the full record goes to (notes, per-level tables, every side leg); stdout's last line is the compact one")
     ap.add_argument("--no-causal", action="store_true",
                     help="skip the second pass that times the same steps with no frame announced ahead (value_without_announced_frames)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline (CPU baseline, oracle comparisons, unannounced pass, side legs, "
+                         "configs[3], roofline launches of their own); the options above that select those apply only with it")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (poses, keyframe flag, depth outputs) "
+                         "to DIR/<name>.npy as float32")
     ap.add_argument("--launch-probe", default="", help=argparse.SUPPRESS)
     ap.add_argument("--no-batch", action="store_true",
                     help="--sequences: a rank that holds several sequences tracks them one after the other (one odo_tracker) instead "
@@ -1166,19 +1195,20 @@ def main():
         seqs = [render_sequence(args.unique_frames, rank if args.distinct_sequences else 0, workers)]
     seq = seqs[0] if seqs else render_sequence(args.unique_frames, 0, workers)   # a rank without a sequence still takes part
     c3_ids, c3_seqs, c3_steps, c3_warm = [], [], 0, 0
-    if world > 1 and args.sequences == 0 and args.configs3 > 0 and not args.no_extras:
+    extras = args.full and not args.no_extras   # the side legs (and configs[3] of N > 1 runs) are --full only
+    if world > 1 and args.sequences == 0 and args.configs3 > 0 and extras:
         c3_warm = min(args.warmup, 5)
         c3_steps = max(1, min(args.steps, 40))
         c3_ids = shard(args.configs3, rank, world)
         c3_seqs = [render_sequence(c3_warm + c3_steps + 1, sid, workers) for sid in c3_ids]
     stress_seq = None
-    if world == 1 and not args.no_extras and not args.no_stress and args.drive != "corridor":
+    if world == 1 and extras and not args.no_stress and args.drive != "corridor":
         stress_seq = render_sequence(min(args.unique_frames, 200), 0, workers, drive="corridor")
     saturated_seq = None
-    if world == 1 and not args.no_extras and "saturated" in args.extras.split(","):
+    if world == 1 and extras and "saturated" in args.extras.split(","):
         saturated_seq = render_sequence(min(args.unique_frames, args.warmup + args.steps + 2, 200), 0, workers, drive="dense")
     batch_seqs = None
-    if world == 1 and not args.no_extras and "batched" in args.extras.split(","):
+    if world == 1 and extras and "batched" in args.extras.split(","):
         nb = min(args.unique_frames, 40)   # eight distinct short drives for the batched leg (rendered before the GPU is touched)
         batch_seqs = [dict(left=seq["left"][:nb], right=seq["right"][:nb])] + [render_sequence(nb, sid, workers) for sid in range(1, 8)]
     import torch
@@ -1358,6 +1388,10 @@ def main():
 
     fps = args.steps * n_sequences / elapsed   # frames tracked by all ranks / max-over-ranks wall time
     host_timing = trk.timing()
+    if args.dump_outputs and rank == 0:   # before anything else runs on the tracker: its outputs are the last timed step's
+        last = n_total - 1
+        dump_outputs(args.dump_outputs, trk, poses_kf[:, last], poses_abs[:, last], None if use_batch else kf_flags[:, last],
+                     seq["left"][0].shape if args.sequences == 0 and my_seq_ids else None)
     c3 = None
     if c3_steps > 0:
         try:
@@ -1385,8 +1419,8 @@ def main():
                    f"itself: launch_us = start-to-start period of the pair ({ev_timed['step_periods']} step + {ev_timed['coarse_periods']} "
                    f"coarse pairs), exec_span_us = entry of the first block to exit of the last ({ev_timed['step_sampled']} + "
                    f"{ev_timed['coarse_sampled']} launches of {ev_timed['launches']}); launch counts exact")
-        else:
-            # --sequences / --event-sample 0: a second pass over the same frames with every launch sampled
+        elif args.full:
+            # --sequences / --event-sample 0 (--full): a second pass over the same frames with every launch sampled
             n_frames_ev = min(args.steps, 100)
             trk.init(*dev[0])
             trk.event_timing(1)
@@ -1402,46 +1436,53 @@ def main():
             total_us = e1["total_us"]
             ev = dict(bytes=e1["bytes"], active_launches=e1["active_launches"], coarse_launches=e1["coarse_launches"])
             how = "a separate pass over the same frames with the execution span of every LM launch recorded (not the timed run)"
-        achieved = ev["bytes"] / (total_us * 1e-6) / 1e9 if total_us > 0 else 0.0
-        kernel_us_per_frame = total_us / n_frames_ev
-        # one persistent launch per Solve (lm_fine_kernel) instead of a step launch per evaluation: as many as coarse launches
-        fine = step_launches <= 1.05 * max(ev["coarse_launches"], 1)
-        fine_key = "lm_fine_kernel" if fine else "lm_step_kernel"
-        roof = dict(bound="hbm", kernel="LM evaluation kernels (lm_coarse_kernel + %s)" % fine_key,
-                    achieved=round(achieved, 3), peak=HBM_PEAK_GBS, unit="GB/s", frac=round(achieved / HBM_PEAK_GBS, 6),
-                    traffic=lm_traffic(fine, args.drive)[0], traffic_source=lm_traffic(fine, args.drive)[1], measured=how,
-                    evaluations_per_frame=round(ev["active_launches"] / n_frames_ev, 2),
-                    algorithmic_bytes_per_frame=round(ev["bytes"] / n_frames_ev, 1),
-                    kernel_us_per_frame=round(kernel_us_per_frame, 2),
-                    # the LM chain IS the frame (everything else overlaps it): the ratio sits at ~1, sampling noise of a few percent
-                    kernel_time_over_step_time=round(kernel_us_per_frame / (elapsed / args.steps * 1e6), 3) if ev_timed is not None else None,
-                    kernel_time_fits_in_step=bool(kernel_us_per_frame <= 1.03 * elapsed / args.steps * 1e6) if ev_timed is not None else None,
-                    lm_coarse_kernel=dict(launches_per_frame=round(ev["coarse_launches"] / n_frames_ev, 2),
-                                          launch_us=round(coarse_us, 2), exec_span_us=round(coarse_span, 2)),
-                    note="single 1241x376 frame: the working set is cache resident and every evaluation is a serial chain "
-                         "(solve, exp, 13-30k points); see roofline_dense_1080p for the HBM-bound shape")
+        else:   # a plain run whose timed steps sampled no launch: no roofline (the pass of its own above is --full only)
+            ev = None
+        roof = dict(bound="hbm", kernel="LM evaluation kernels", achieved=None, peak=HBM_PEAK_GBS, unit="GB/s", frac=None, traffic=None,
+                    measured="not measured: no LM launch of the timed steps was sampled (--event-sample 0 or --sequences without --full)")
+        evals = []
+        if ev is not None:
+            achieved = ev["bytes"] / (total_us * 1e-6) / 1e9 if total_us > 0 else 0.0
+            kernel_us_per_frame = total_us / n_frames_ev
+            # one persistent launch per Solve (lm_fine_kernel) instead of a step launch per evaluation: as many as coarse launches
+            fine = step_launches <= 1.05 * max(ev["coarse_launches"], 1)
+            fine_key = "lm_fine_kernel" if fine else "lm_step_kernel"
+            roof = dict(bound="hbm", kernel="LM evaluation kernels (lm_coarse_kernel + %s)" % fine_key,
+                        achieved=round(achieved, 3), peak=HBM_PEAK_GBS, unit="GB/s", frac=round(achieved / HBM_PEAK_GBS, 6),
+                        traffic=lm_traffic(fine, args.drive)[0], traffic_source=lm_traffic(fine, args.drive)[1], measured=how,
+                        evaluations_per_frame=round(ev["active_launches"] / n_frames_ev, 2),
+                        algorithmic_bytes_per_frame=round(ev["bytes"] / n_frames_ev, 1),
+                        kernel_us_per_frame=round(kernel_us_per_frame, 2),
+                        # the LM chain IS the frame (everything else overlaps it): the ratio sits at ~1, sampling noise of a few percent
+                        kernel_time_over_step_time=round(kernel_us_per_frame / (elapsed / args.steps * 1e6), 3) if ev_timed is not None else None,
+                        kernel_time_fits_in_step=bool(kernel_us_per_frame <= 1.03 * elapsed / args.steps * 1e6) if ev_timed is not None else None,
+                        lm_coarse_kernel=dict(launches_per_frame=round(ev["coarse_launches"] / n_frames_ev, 2),
+                                              launch_us=round(coarse_us, 2), exec_span_us=round(coarse_span, 2)),
+                        note="single 1241x376 frame: the working set is cache resident and every evaluation is a serial chain "
+                             "(solve, exp, 13-30k points); see roofline_dense_1080p for the HBM-bound shape")
+            if fine:
+                roof[fine_key] = dict(launches_per_frame=round(step_launches / n_frames_ev, 2), launch_us=round(step_span, 2),
+                                      exec_span_us=round(step_span, 2),
+                                      what="every evaluation of the levels the coarse launch leaves, in one persistent launch: 30 workgroups (32 where a level of 61-64 or 121-128 virtual blocks would need another pass) "
+                                           "of one XCD exchange their partial rows through L2 (DESIGN.md section 5.1); us per evaluation = "
+                                           "(coarse + fine) exec spans / evaluations_per_frame",
+                                      us_per_evaluation_both_kernels=round(kernel_us_per_frame / max(ev["active_launches"] / n_frames_ev, 1e-9), 2))
+            else:
+                roof[fine_key] = dict(launches_per_frame=round(step_launches / n_frames_ev, 2), launch_us=round(step_us, 3),
+                                      exec_span_us=round(step_span, 3),
+                                      algorithmic_bytes_per_launch=round((ev["bytes"]) / max(ev["active_launches"], 1), 1),
+                                      achieved=round(ev["bytes"] / max(ev["active_launches"], 1) / (step_us * 1e-6) / 1e9, 2) if step_us > 0 else None)
+            evals = [ev["active_launches"] / n_frames_ev]
         pk, pf = trk.persistent_stats()
         dk, df = trk.depth_persistent_stats()
         roof["persistent_launch"] = dict(workgroups=pk, solves_redone_on_step_launches=pf,
                                          depth_lm_persistent=dk, depth_jobs_redone_on_step_launches=df,
                                          note="lm_fine_kernel: 0 workgroups = off (by choice or after three fall-backs); depth_lm_persistent_kernel likewise")
-        if fine:
-            roof[fine_key] = dict(launches_per_frame=round(step_launches / n_frames_ev, 2), launch_us=round(step_span, 2),
-                                  exec_span_us=round(step_span, 2),
-                                  what="every evaluation of the levels the coarse launch leaves, in one persistent launch: 30 workgroups (32 where a level of 61-64 or 121-128 virtual blocks would need another pass) "
-                                       "of one XCD exchange their partial rows through L2 (DESIGN.md section 5.1); us per evaluation = "
-                                       "(coarse + fine) exec spans / evaluations_per_frame",
-                                  us_per_evaluation_both_kernels=round(kernel_us_per_frame / max(ev["active_launches"] / n_frames_ev, 1e-9), 2))
-        else:
-            roof[fine_key] = dict(launches_per_frame=round(step_launches / n_frames_ev, 2), launch_us=round(step_us, 3),
-                                  exec_span_us=round(step_span, 3),
-                                  algorithmic_bytes_per_launch=round((ev["bytes"]) / max(ev["active_launches"], 1), 1),
-                                  achieved=round(ev["bytes"] / max(ev["active_launches"], 1) / (step_us * 1e-6) / 1e9, 2) if step_us > 0 else None)
-        evals = [ev["active_launches"] / n_frames_ev]
-        tr0 = trk.time_residual(0, reps=100)   # evaluation-only kernel on level 0 (no LM update), for reference
-        roof["eval_only_L0"] = dict(launch_us=round(tr0["mean_us"], 3), residuals=tr0["n_points"],
-                                    algorithmic_bytes=int(tr0["bytes"]),
-                                    achieved=round(tr0["bytes"] / (tr0["mean_us"] * 1e-6) / 1e9, 2))
+        if args.full:
+            tr0 = trk.time_residual(0, reps=100)   # evaluation-only kernel on level 0 (no LM update), for reference
+            roof["eval_only_L0"] = dict(launch_us=round(tr0["mean_us"], 3), residuals=tr0["n_points"],
+                                        algorithmic_bytes=int(tr0["bytes"]),
+                                        achieved=round(tr0["bytes"] / (tr0["mean_us"] * 1e-6) / 1e9, 2))
         out = dict(metric="tracked frames/sec (1241x376, 4-level pyramid)", value=round(fps, 2), unit="frames/s",
                    n_gpus=world, steps=args.steps, warmup=args.warmup,
                    ms_per_step=round(elapsed / (args.steps * max(max(per_rank) // max(args.steps, 1), 1)) * 1e3, 4),
@@ -1473,12 +1514,12 @@ def main():
                                if args.sequences > 0 else "distinct synthetic sequences" if args.distinct_sequences
                                else "every rank tracks its own copy of synthetic sequence 0 (equal work per GPU)"),
                    roofline=roof,
-                   lm_evals_per_frame=round(float(np.mean(evals)), 2),
+                   lm_evals_per_frame=round(float(np.mean(evals)), 2) if evals else None,
                    host_us_per_frame={k: round(v, 1) for k, v in host_timing.items()},
                    keyframes=trk.stats()["n_keyframes"])
         out["details_file"] = args.details
         try:   # whatever fails below, the contract line is printed (a failing side measurement is named in it)
-            if world == 1 and args.sequences == 0 and my_seq_ids and not args.no_prefetch and not args.no_causal:
+            if args.full and world == 1 and args.sequences == 0 and my_seq_ids and not args.no_prefetch and not args.no_causal:
                 # The causal rate: the same warm-up + steps with NO frame announced ahead (what a live camera allows). The poses of
                 # this pass must repeat the timed run's bit for bit (announcing only moves work earlier).
                 keep_kf, keep_abs = poses_kf.copy(), poses_abs.copy()
@@ -1503,6 +1544,7 @@ def main():
                 out["step_us"] = dict(median=round(float(np.median(us)), 1), p10=round(float(np.percentile(us, 10)), 1),
                                       p90=round(float(np.percentile(us, 90)), 1), min=round(float(us.min()), 1), max=round(float(us.max()), 1),
                                       slowest_step=int(np.argmax(us)), first_step=round(float(us[0]), 1))
+            if args.full and args.sequences == 0 and my_seq_ids:
                 # does the tracker track? absolute poses of the first pass over the drive against the synthetic ground truth
                 # (ref: run_odometry_kitti_offline.cpp:361-372 prints this mean translation error)
                 m = min(n_total, args.unique_frames - 1)
@@ -1519,7 +1561,7 @@ def main():
                 fr = [per_rank[r] / t if t > 0 else 0.0 for r, t in enumerate(rank_elapsed)]
                 out["per_rank"] = dict(frames=per_rank, seconds=[round(t, 4) for t in rank_elapsed], frames_per_s=[round(f, 1) for f in fr],
                                        slowest_over_fastest_seconds=round(max(rank_elapsed) / max(min(rank_elapsed), 1e-9), 3))
-            if args.sequences == 0 and n_total > args.unique_frames - 1:
+            if args.full and args.sequences == 0 and n_total > args.unique_frames - 1:
                 # determinism of the timed run: every later pass over the drive (re-initialised on frame 0) repeats the first one
                 per = args.unique_frames - 1
                 same = all(np.array_equal(poses_kf[0, k], poses_kf[0, k % per]) and np.array_equal(poses_abs[0, k], poses_abs[0, k % per])
@@ -1536,7 +1578,7 @@ def main():
                     mine = gatherer.poses(0, seq_id=my_seq_ids[0])
                     want = poses_abs[0, args.warmup:].reshape(-1, 4, 4).transpose(0, 2, 1)[:, :3, :]
                     out["pose_gather"]["rank0_rows_match_tracked_poses"] = bool(np.array_equal(mine, want))
-            if world == 1 and args.cpu_frames > 0:
+            if args.full and world == 1 and args.cpu_frames > 0:
                 if os.environ.get("ODO_LOG_GIVEUPS"):
                     print("[bench phase] cpu_baseline + plain GPU pass", file=sys.stderr, flush=True)
                 n = min(args.cpu_frames, args.steps, args.unique_frames - 1)
@@ -1590,7 +1632,7 @@ def main():
                 # ~25 later), so the ratios are taken on the same frames, not against the whole-run rate
                 out["speedup_vs_cpu"] = round(gpu_same_fps / ref["frames_per_s"], 1)
                 out["speedup_vs_cpu_fused"] = round(gpu_same_fps / fus["frames_per_s"], 1)
-            if world == 1 and not args.no_extras:
+            if world == 1 and extras:
                 import contextlib
                 with contextlib.redirect_stdout(sys.stderr):  # the mirrored classes print the reference's own messages
                     legs = set(args.extras.split(","))

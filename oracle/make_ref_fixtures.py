@@ -375,6 +375,57 @@ def ref_depth_lm_schedule(L, errs, lam, precision, max_iters):
     return rec[:n].copy(), fin.value, it.value
 
 
+FRESH_SCAN = dict(boundary=4, ssd_th=900.0, fx=718.856, baseline=float(np.float32(386.1448) / np.float32(718.856)))
+
+
+def fresh_inputs():
+    """Inputs the other fixtures do not hold (tests/test_ref_pin.py's fresh-input check): 20 random pairs with random masks and
+    full-mantissa values, four principal points, 50 + 50 error sequences for the two LM loops, one camera."""
+    inp = {}
+    rng = np.random.default_rng(99)
+    for t in range(20):
+        rows, cols = int(rng.integers(12, 40)), int(rng.integers(24, 160))
+        lb = (rng.random((rows, cols), np.float32) * 255).astype(np.float32)
+        rb = (lb + rng.normal(0, 4.0, lb.shape).astype(np.float32)).astype(np.float32) if t % 2 else np.roll(lb, -3, 1).copy()
+        val = np.zeros((rows, cols), np.uint8)
+        val[4:rows - 4, 4:cols - 4] = rng.random((rows - 8, cols - 8)) < 0.2
+        inp.update({f"scan{t}_left_blur": lb, f"scan{t}_right_blur": rb, f"scan{t}_val": val})
+    inp["cx_c"] = np.array([607.1928, 185.2157, 0.0, 1e6], np.float32)
+    rng2 = np.random.default_rng(123)
+    for t in range(50):
+        inp[f"lm{t}_errs"] = (rng2.uniform(100, 500) * np.cumprod(rng2.uniform(0.9, 1.08, int(rng2.integers(3, 40))))).astype(np.float32)
+    for t in range(50):
+        inp[f"dlm{t}_errs"] = (rng2.uniform(20, 300) * np.cumprod(rng2.uniform(0.9, 1.08, int(rng2.integers(3, 60))))).astype(np.float32)
+    inp["cam_in"] = np.array([1100.0, 1090.5, 0.25, 959.5, 539.5])
+    return inp
+
+
+def fresh_outputs(L, inp):
+    """What the reference lines make of fresh_inputs(): the scan (disparity, inverse depth, smallest SSD, its column), GetCxLevel on
+    levels 0-7, both LM loops' schedules (lambda 0.01, precision 0.995, 30 / 50 iterations) and the camera pyramid's 5 levels."""
+    out = {}
+    for t in range(20):
+        disp, dep, best, col = ref_scan(L, inp[f"scan{t}_left_blur"], inp[f"scan{t}_right_blur"], inp[f"scan{t}_val"],
+                                        FRESH_SCAN["boundary"], FRESH_SCAN["ssd_th"], FRESH_SCAN["baseline"])
+        out.update({f"scan{t}_disp": disp, f"scan{t}_dep": dep, f"scan{t}_best_ssd": best, f"scan{t}_best_col": col})
+    out["cx_out"] = np.array([[L.ref_cx_level(C.c_float(c), l) for l in range(8)] for c in inp["cx_c"]], np.float32)
+    for t in range(50):
+        rec, fin = ref_lm_schedule(L, inp[f"lm{t}_errs"], 0.01, 0.995, 30)
+        out.update({f"lm{t}_rec": rec, f"lm{t}_fin": np.int32(fin)})
+    for t in range(50):
+        rec, fin, it = ref_depth_lm_schedule(L, inp[f"dlm{t}_errs"], 0.01, 0.995, 50)
+        out.update({f"dlm{t}_rec": rec, f"dlm{t}_fin": np.int32(fin), f"dlm{t}_it": np.int32(it)})
+    cam = np.zeros((5, 5))
+    L.ref_camera_pyramid(*[float(v) for v in inp["cam_in"]], 5, cam.ctypes.data_as(C.POINTER(C.c_double)))
+    out["cam_out"] = cam
+    return out
+
+
+def write_fresh_fixture(L):
+    inp = fresh_inputs()
+    np.savez_compressed(os.path.join(GOLD, "ref_fresh_ref.npz"), **inp, **fresh_outputs(L, inp))
+
+
 def scenes():
     """Two stereo pairs; the blurred pair and the selection mask of each (the scan's INPUTS) come from the oracle. (a) u8-origin: a
     textured image shifted by integer disparities — the shape of the real path, every blurred value a multiple of 1/16; (b) the
@@ -494,6 +545,8 @@ def main():
         n_break += int(rec[-1, 4]) if len(rec) else 0
     np.savez_compressed(os.path.join(GOLD, "depth_lm_schedule_ref.npz"), errs=errs, meta=meta, recs=recs, outs=outs)
     print(f"wrote depth_lm_schedule_ref.npz ({len(sq)} sequences, {n_break} ending in a break)")
+    write_fresh_fixture(L)
+    print("wrote ref_fresh_ref.npz (20 scans, 4 x 8 principal points, 50 + 50 LM schedules, one camera pyramid)")
     n_a = int(sc["a"][4].sum())
     n_b = int(sc["b"][4].sum())
     print(f"wrote tests/golden/ssd_ref.npz ({n_a} + {n_b} scanned points, {K} tree KATs of which {n_diff} separate the tree "

@@ -70,9 +70,9 @@ def test_bench_two_ranks_default_weak_scaling():
 
 
 def test_bench_two_ranks_carries_configs3_and_exchange_evidence():
-    """The default N > 1 line: per-rank rates, the exchange's own evidence (ranks seen by a collective of the gather's backend,
+    """The --full N > 1 line: per-rank rates, the exchange's own evidence (ranks seen by a collective of the gather's backend,
     distinct devices), and configs[3] in miniature (3 sequences over the 2 ranks, batched rank 0) as an extra key."""
-    out = _run_bench(["--steps", "8", "--warmup", "2", "--unique-frames", "12", "--gather-every", "4", "--configs3", "3"], no_extras=False)
+    out = _run_bench(["--steps", "8", "--warmup", "2", "--unique-frames", "12", "--gather-every", "4", "--configs3", "3", "--full"], no_extras=False)
     assert out["n_gpus"] == 2 and out["pose_gather"]["complete"]
     assert out["pose_gather"]["ranks_seen"] == 2 and out["pose_gather"]["backend"] == "gloo"
     assert out["pose_gather"]["distinct_devices"] == 1           # this test shares ONE device between the ranks on purpose

@@ -154,44 +154,39 @@ def test_fixture_inputs_are_what_the_oracle_front_end_produces(ssd, key):
     assert np.array_equal(d["disp"], ssd[f"{key}_disp"]) and np.array_equal(d["dep"], ssd[f"{key}_dep"])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="the reference checkout exists in the build container only")
 def test_oracle_scan_matches_live_reference_build_on_fresh_inputs(tmp_path_factory):
-    """In the build container the reference lines are compiled again — hash-checked, into a temporary directory OUTSIDE the
-    repository, so nothing of the reference ever lies in the tree that travels — and run on inputs the fixture does not hold:
-    20 random pairs, random masks, full-mantissa values."""
+    """The reference lines on inputs the other fixtures do not hold — 20 random pairs, random masks, full-mantissa values; four
+    principal points; 50 + 50 error sequences through both LM loops; one camera — against the oracle. What the reference lines made
+    of them is stored in tests/golden/ref_fresh_ref.npz (oracle/make_ref_fixtures.py); where the reference checkout exists they are
+    compiled again — hash-checked, into a temporary directory OUTSIDE the repository, so nothing of the reference ever lies in the
+    tree that travels — and must reproduce every stored output."""
     from oracle import make_ref_fixtures as M
-    L = M.load(M.build(str(tmp_path_factory.mktemp("odo_ref"))))
-    rng = np.random.default_rng(99)
-    for trial in range(20):
-        rows, cols = int(rng.integers(12, 40)), int(rng.integers(24, 160))
-        lb = (rng.random((rows, cols), np.float32) * 255).astype(np.float32)
-        rb = (lb + rng.normal(0, 4.0, lb.shape).astype(np.float32)).astype(np.float32) if trial % 2 else np.roll(lb, -3, 1).copy()
-        val = np.zeros((rows, cols), np.uint8)
-        val[4:rows - 4, 4:cols - 4] = rng.random((rows - 8, cols - 8)) < 0.2
-        base = float(np.float32(386.1448) / np.float32(718.856))
-        disp, dep, best, col = M.ref_scan(L, lb, rb, val, 4, 900.0, base)
-        r = O.disparity_scan(lb, rb, val, 4, 900.0, 718.856, base)
+    g = dict(np.load(os.path.join(GOLD, "ref_fresh_ref.npz")))
+    if os.path.isdir(M.REF):
+        L = M.load(M.build(str(tmp_path_factory.mktemp("odo_ref"))))
+        for k, v in M.fresh_outputs(L, g).items():
+            assert np.array_equal(v, g[k]), f"the reference lines no longer produce the stored {k}"
+    S = M.FRESH_SCAN
+    for t in range(20):
+        lb, rb, val = g[f"scan{t}_left_blur"], g[f"scan{t}_right_blur"], g[f"scan{t}_val"]
+        best, col = g[f"scan{t}_best_ssd"], g[f"scan{t}_best_col"]
+        r = O.disparity_scan(lb, rb, val, S["boundary"], S["ssd_th"], S["fx"], S["baseline"])
         assert np.array_equal(r["best_ssd"], best) and np.array_equal(r["best_col"][best < 1e10], col[best < 1e10])
-        assert np.array_equal(r["disp"], disp) and np.array_equal(r["dep"], dep)
-    for c in (607.1928, 185.2157, 0.0, 1e6):
+        assert np.array_equal(r["disp"], g[f"scan{t}_disp"]) and np.array_equal(r["dep"], g[f"scan{t}_dep"])
+    for i, c in enumerate(g["cx_c"]):
         for l in range(8):
-            assert O.lib().orc_cx_level(C.c_float(c), l) == L.ref_cx_level(C.c_float(c), l)
-    rng2 = np.random.default_rng(123)
-    for trial in range(50):   # fresh error sequences through the reference's LM loop lines and the oracle's
-        errs = (rng2.uniform(100, 500) * np.cumprod(rng2.uniform(0.9, 1.08, int(rng2.integers(3, 40))))).astype(np.float32)
-        want, fin = M.ref_lm_schedule(L, errs, 0.01, 0.995, 30)
-        rec, n, f2 = _schedule(O.lib().orc_lm_schedule, errs, 0.01, 0.995, 30)
-        assert n == len(want) and f2 == fin and np.array_equal(rec, want)
-    for trial in range(50):   # and through the inverse-depth LM's
-        errs = (rng2.uniform(20, 300) * np.cumprod(rng2.uniform(0.9, 1.08, int(rng2.integers(3, 60))))).astype(np.float32)
-        want, fin, it = M.ref_depth_lm_schedule(L, errs, 0.01, 0.995, 50)
-        rec, n, f2, i2 = _depth_schedule(O.lib().orc_depth_lm_schedule, errs, 0.01, 0.995, 50)
-        assert n == len(want) and f2 == fin and i2 == it and np.array_equal(rec, want)
-    out = np.zeros((5, 5))
-    L.ref_camera_pyramid(1100.0, 1090.5, 0.25, 959.5, 539.5, 5, out.ctypes.data_as(C.POINTER(C.c_double)))
+            assert np.float32(O.lib().orc_cx_level(C.c_float(c), l)) == g["cx_out"][i, l]
+    for t in range(50):   # the LM loop lines and the oracle's
+        rec, n, f2 = _schedule(O.lib().orc_lm_schedule, g[f"lm{t}_errs"], 0.01, 0.995, 30)
+        want = g[f"lm{t}_rec"]
+        assert n == len(want) and f2 == g[f"lm{t}_fin"] and np.array_equal(rec, want)
+    for t in range(50):   # and the inverse-depth LM's
+        rec, n, f2, i2 = _depth_schedule(O.lib().orc_depth_lm_schedule, g[f"dlm{t}_errs"], 0.01, 0.995, 50)
+        want = g[f"dlm{t}_rec"]
+        assert n == len(want) and f2 == g[f"dlm{t}_fin"] and i2 == g[f"dlm{t}_it"] and np.array_equal(rec, want)
     P = np.zeros((3, 4))
-    P[0, 0], P[1, 1], P[0, 1], P[0, 2], P[1, 2], P[2, 2] = 1100.0, 1090.5, 0.25, 959.5, 539.5, 1.0
-    assert np.array_equal(O.camera_intrinsics(P, 5), out)
+    P[0, 0], P[1, 1], P[0, 1], P[0, 2], P[1, 2], P[2, 2] = *g["cam_in"], 1.0
+    assert np.array_equal(O.camera_intrinsics(P, 5), g["cam_out"])
 
 
 def test_reference_lines_are_never_built_inside_the_repository():

@@ -8,6 +8,7 @@
 #   4. --pmc SQ_* of the dense-kernel microbenchmark (issue-bound evidence) + its plain output (A/B table)
 #   5. the VALU instruction-rate microbenchmark
 set -u
+ROOT=$(cd "$(dirname "$0")/.." && pwd)   # the repository
 TAG=${1:-r02}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 rm -rf $OUT   # (gpurun MERGES what a call writes into the caller's gpurun_out/: use a fresh tag per collection there, or delete
@@ -18,7 +19,7 @@ cd /tmp && export TMPDIR=/tmp
 # them down the launch-per-iteration path — 4 % of the jobs unprofiled (ODO_LOG_GIVEUPS=1 prints the split at exit). The profiled runs
 # keep the unprofiled run's path:
 export ODO_DEPTH_PERSIST_ALWAYS=1
-BENCH="python3 $GRAFT_REPO_ROOT/bench.py --cpu-frames 0 --no-child-processes --details $OUT/bench_profiled_details.json --extras dense,disparity,single,batched,saturated"
+BENCH="python3 $ROOT/bench.py --full --cpu-frames 0 --no-child-processes --details $OUT/bench_profiled_details.json --extras dense,disparity,single,batched,saturated"
 timeout -k 5 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $BENCH --steps 1000 --warmup 50 > $OUT/bench_profiled.json 2> $OUT/bench_profiled.err < /dev/null
 # 1b. the driver's own short run (python bench.py --steps 20 --warmup 5), side legs off: the averages bench.py's roofline line must agree with
 timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats20 -- python3 $GRAFT_REPO_ROOT/bench.py --cpu-frames 0 --no-extras --details $OUT/bench_profiled_steps20_details.json --steps 20 --warmup 5 > $OUT/bench_profiled_steps20.json 2> $OUT/bench_profiled_steps20.err < /dev/null
@@ -39,7 +40,7 @@ timeout -k 5 120 /tmp/valu_rates > $OUT/valu_rates.log 2>&1 < /dev/null
 # 6. (round 6, VERDICT r05 task 2) the dense 1080p leg alone — configs[2] — with its per-dispatch trace kept, so that level 0 of
 #    lm_dense_eval_kernel is its own row (tools/summarize_profile.py grids: rows per kernel AND grid size), and one SQ pass of the
 #    same command; 7. the SQ pass of the headline (the LM chain's wait / issue split)
-DENSE="python3 $GRAFT_REPO_ROOT/bench.py --cpu-frames 0 --no-child-processes --no-causal --extras dense --no-stress --details $OUT/bench_dense_details.json --steps 20 --warmup 5"
+DENSE="python3 $ROOT/bench.py --full --cpu-frames 0 --no-child-processes --no-causal --extras dense --no-stress --details $OUT/bench_dense_details.json --steps 20 --warmup 5"
 SQ="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY"
 timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_dense -- $DENSE > $OUT/bench_dense.json 2> $OUT/bench_dense.err < /dev/null
 for f in $(find $OUT/stats_dense -name "*_kernel_trace.csv"); do mv $f ${f%_kernel_trace.csv}_dispatches.csv; done
