@@ -31,6 +31,7 @@ typedef struct odo_lm odo_lm;
 typedef struct odo_depth odo_depth;
 typedef struct odo_tracker odo_tracker;
 typedef struct odo_camera odo_camera;
+typedef struct odo_map odo_map;
 
 /* Level-0 pinhole intrinsics (fy = fx). NULL wherever accepted = the KITTI-00 constants the reference
  * hard-codes (ref: include/image_processing_global.h:35-36: 718.856f, 607.1928, 185.2157). */
@@ -413,6 +414,43 @@ int odo_tracker_hint_next_pair(odo_tracker* t, const float* next_left_dev, const
  * returns nothing, queued or yet to be issued by the helper thread, reads a caller-owned frame buffer: call it before freeing or
  * overwriting frames that were announced but never tracked (odo_tracker_destroy / odo_tracker_init do it themselves). */
 int odo_tracker_quiesce(odo_tracker* t);
+/* Keyframe point-cloud map (replaces GlobalMap, ref: include/global_map.h, and the keyframe export of save_to_vis,
+ * ref: run_odometry_kitti_offline.cpp:259-265,432-471, which writes every keyframe's images, depth and mask as PNGs for another
+ * program to build the cloud from). Points are {x, y, z, intensity} fp32 in world coordinates plus {keyframe, pixel} int32;
+ * keyframe = the map's own 0-based insertion counter, pixel = y * cols + x. One insertion takes the pixels with
+ * (val == NULL || val != 0) && inverse depth valid (|d| >= 0.01) && d > 0, in row-major order; camera point = the LM's
+ * back-projection at level 0 (odo_math.h point_xyz); world point = A * camera point, fp32 in the order ((a0 X + a4 Y) + a8 Z) + a12.
+ * voxel_size > 0: key k = floor(world / voxel_size) per axis; a point with any |k| >= 2^20 is dropped (dropped_range); a point is
+ * kept iff no earlier point of this or an earlier insertion had its key (dropped_voxel); points already in the map are never
+ * replaced. voxel_size = 0: every candidate is kept. Kept points are appended in (insertion, pixel) order; once the map holds
+ * `capacity` points the rest are dropped (dropped_capacity), and an insertion into a full map changes nothing but the insertion
+ * counter. The result is a pure function of the inputs. */
+/* rows x cols: the frames' size; capacity: points (1 .. 2^28). Device memory: 24 B per point + 32 B per hash slot (a power of two
+ * >= 2 (capacity + rows * cols), voxel filter on only) + ~17 B per pixel. */
+int odo_map_create(odo_ctx* ctx, int rows, int cols, long capacity, float voxel_size, odo_map** out);
+/* One keyframe into the map (GlobalMap::InsertKeyFrame): device buffers of rows x cols; val_dev NULL = no mask, img_dev NULL =
+ * intensity 0, K NULL = the KITTI-00 constants. abs_pose: camera-to-world, the convention of odo_tracker_track's abs_pose.
+ * Asynchronous on ctx's stream (four launches, no host synchronisation); ordered after every earlier insertion. */
+int odo_map_insert_dev(odo_map* m, const uint8_t* val_dev, const float* dep_dev, const float* img_dev, const odo_intrinsics* K,
+                       const float abs_pose_colmajor[16]);
+/* Points in the map; waits for pending insertions. -1 on error. */
+long odo_map_size(odo_map* m);
+/* Points first .. first + count - 1 to the host (save_to_vis' export): 4 floats each, and 2 ints each when kf_pixel != NULL. */
+int odo_map_download(odo_map* m, long first, long count, float* xyzi, int* kf_pixel);
+/* out: size, insertions, candidates, dropped_voxel, dropped_range, dropped_capacity (waits for pending insertions). */
+int odo_map_stats(odo_map* m, long out[6]);
+/* The camera-to-world pose insertion `keyframe` was made with (GlobalMap's keyframe poses). */
+int odo_map_keyframe_pose(const odo_map* m, int keyframe, float abs_pose_colmajor[16]);
+/* Empty map: points, voxels, counters and the insertion counter start from nothing. */
+int odo_map_clear(odo_map* m);
+/* -1 while the map is attached to a tracker. */
+int odo_map_destroy(odo_map* m);
+/* The tracker inserts every keyframe into m (GlobalMap::InsertKeyFrame where the runner keeps its keyframes, ref:
+ * run_odometry_kitti_offline.cpp:259-265): frame 0 in odo_tracker_init, each promotion in odo_tracker_track, with the frame's
+ * mask, inverse depth, level-0 image and abs_pose. The insertions run on a stream of the map's own and are never waited for by
+ * the host while tracking; odo_tracker_quiesce / init / destroy drain them. Poses are unchanged. Same device and frame size as
+ * the tracker; one tracker per map. NULL detaches (pending insertions complete first). */
+int odo_tracker_attach_map(odo_tracker* t, odo_map* m);
 /* Counters of the last tracked frame: LM evaluations, depth-LM iterations, valid depth points, keyframes so far. */
 int odo_tracker_stats(const odo_tracker* t, int* lm_evals, int* depth_iters, int* n_valid_depth, int* n_keyframes);
 /* Device pointers to the last frame's outputs (rows x cols): validity mask (u8), disparity, inverse depth. */

@@ -178,6 +178,15 @@ SIGNATURES = {
     "odo_camera_undistort_rectify": (C.c_int, [_vp, _fp, C.c_int, C.c_int, _fp, C.c_float]),
     "odo_camera_undistort_rectify_dev": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_float]),
     "odo_camera_destroy": (C.c_int, [_vp]),
+    "odo_map_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_long, C.c_float, C.POINTER(_vp)]),
+    "odo_map_insert_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(Intrinsics), _fp]),
+    "odo_map_size": (C.c_long, [_vp]),
+    "odo_map_download": (C.c_int, [_vp, C.c_long, C.c_long, _fp, _ip]),
+    "odo_map_stats": (C.c_int, [_vp, C.POINTER(C.c_long)]),
+    "odo_map_keyframe_pose": (C.c_int, [_vp, C.c_int, _fp]),
+    "odo_map_clear": (C.c_int, [_vp]),
+    "odo_map_destroy": (C.c_int, [_vp]),
+    "odo_tracker_attach_map": (C.c_int, [_vp, _vp]),
 }
 
 _lib = None

@@ -673,6 +673,15 @@ class Tracker:
                                                    C.byref(n)), "odo_tracker_time_residual")
         return dict(mean_us=mean.value, min_us=mn.value, bytes=b.value, n_points=n.value)
 
+    def attach_map(self, m):
+        """Every keyframe from now on goes into PointMap `m` (None detaches; pending insertions complete first)."""
+        L.check(self.lib.odo_tracker_attach_map(self.h, m.h if m is not None else None), "odo_tracker_attach_map")
+        if getattr(self, "_map", None) is not None and self._map is not m:
+            self._map._tracker = None
+        self._map = m
+        if m is not None:
+            m._tracker = self
+
     def close(self):
         if getattr(self, "h", None):
             # frames announced with hint_next may still be read by launches the helper thread has yet to issue (the job posted
@@ -690,6 +699,112 @@ class Tracker:
             self.close()
         except Exception:
             pass
+
+
+class PointMap:
+    """Device-resident keyframe point cloud with voxel filtering (odo_map_*; replaces GlobalMap and save_to_vis' export).
+    ctx_or_tracker: a Context, or a Tracker whose stream standalone insertions then use (attach with Tracker.attach_map)."""
+
+    def __init__(self, ctx_or_tracker, rows, cols, capacity, voxel_size):
+        self.lib = L.load()
+        self._owner = ctx_or_tracker   # keeps the stream's owner alive as long as the map
+        ctx = ctx_or_tracker._ctx if isinstance(ctx_or_tracker, Tracker) else ctx_or_tracker.h
+        self.rows, self.cols = rows, cols
+        self._ctx = ctx
+        self._tracker = None
+        h = C.c_void_p()
+        L.check(self.lib.odo_map_create(ctx, rows, cols, capacity, voxel_size, C.byref(h)), "odo_map_create")
+        self.h = h
+
+    def _dev(self, a, dtype):
+        """A device handle as is; a numpy array uploaded into a temporary buffer (freed once the insertion has read it)."""
+        if a is None:
+            return None, None
+        if isinstance(a, np.ndarray):
+            a = np.ascontiguousarray(a, dtype=dtype)
+            assert a.shape == (self.rows, self.cols), a.shape
+            p = C.c_void_p()
+            L.check(self.lib.odo_dev_alloc(self._ctx, a.nbytes, C.byref(p)), "odo_dev_alloc")
+            L.check(self.lib.odo_dev_upload(self._ctx, p, a.ctypes.data_as(C.c_void_p), a.nbytes), "odo_dev_upload")
+            return p, p
+        return a, None
+
+    def insert(self, val, dep, img, K, abs_pose):
+        """One keyframe (GlobalMap::InsertKeyFrame): numpy arrays (uploaded) or device handles; val / img may be None.
+        K = (f0, cx0, cy0) or None (KITTI-00); abs_pose = 4x4 camera-to-world."""
+        tmp = []
+        try:
+            ptrs = []
+            for a, dt in ((val, np.uint8), (dep, np.float32), (img, np.float32)):
+                p, t = self._dev(a, dt)
+                ptrs.append(p)
+                if t is not None:
+                    tmp.append(t)
+            k = C.byref(L.Intrinsics(*K)) if K is not None else None
+            pose = _colmajor(abs_pose)
+            L.check(self.lib.odo_map_insert_dev(self.h, ptrs[0], ptrs[1], ptrs[2], k, _fp(pose)), "odo_map_insert_dev")
+        finally:
+            for p in tmp:   # odo_dev_free waits for the context's stream: the insertion has read them
+                self.lib.odo_dev_free(self._ctx, p)
+
+    def __len__(self):
+        n = self.lib.odo_map_size(self.h)
+        if n < 0:
+            raise L.OdoError("odo_map_size: " + L.last_error())
+        return n
+
+    def points(self):
+        """(N, 4) float32 x, y, z, intensity in world coordinates and (N, 2) int32 keyframe, pixel."""
+        n = len(self)
+        xyzi = np.zeros((n, 4), np.float32)
+        kp = np.zeros((n, 2), np.int32)
+        L.check(self.lib.odo_map_download(self.h, 0, n, _fp(xyzi), kp.ctypes.data_as(C.POINTER(C.c_int))), "odo_map_download")
+        return xyzi, kp
+
+    def stats(self):
+        o = (C.c_long * 6)()
+        L.check(self.lib.odo_map_stats(self.h, o), "odo_map_stats")
+        return dict(zip(("size", "insertions", "candidates", "dropped_voxel", "dropped_range", "dropped_capacity"), list(o)))
+
+    def keyframe_pose(self, i):
+        v = np.zeros(16, np.float32)
+        L.check(self.lib.odo_map_keyframe_pose(self.h, i, _fp(v)), "odo_map_keyframe_pose")
+        return _from_colmajor(v)
+
+    def clear(self):
+        L.check(self.lib.odo_map_clear(self.h), "odo_map_clear")
+
+    def save_ply(self, path):
+        """Binary little-endian PLY: float x y z, uchar red green blue (the intensity clamped to 0..255)."""
+        xyzi, _ = self.points()
+        write_ply(path, xyzi)
+
+    def close(self):
+        if getattr(self, "h", None):
+            if self._tracker is not None and getattr(self._tracker, "h", None):
+                self._tracker.attach_map(None)
+            self.lib.odo_map_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def write_ply(path, xyzi):
+    """(N, 4) float32 x, y, z, intensity -> binary little-endian PLY with float x y z and uchar red green blue (grey)."""
+    xyzi = np.asarray(xyzi, np.float32).reshape(-1, 4)
+    rec = np.zeros(len(xyzi), np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("r", "u1"), ("g", "u1"), ("b", "u1")]))
+    rec["x"], rec["y"], rec["z"] = xyzi[:, 0], xyzi[:, 1], xyzi[:, 2]
+    grey = np.clip(np.nan_to_num(xyzi[:, 3]), 0, 255).astype(np.uint8)
+    rec["r"] = rec["g"] = rec["b"] = grey
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+              "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n") % len(xyzi)
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(rec.tobytes())
 
 
 class TrackerBatch:

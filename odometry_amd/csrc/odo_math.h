@@ -112,6 +112,23 @@ ODO_HD bool warp_point_uv(const PointK& p, const float* T, const LevelK& k, floa
   *v = (float)(k.fl * (double)t1 / (double)t2 + (double)k.cy);
   return true;
 }
+// Keyframe map (odo_map_*, map.hip.h): a camera point moved into the world by the camera-to-world pose A (column-major 4x4),
+// in the operation order of warp_point_uv above. Replaces the host-side back-projection of save_to_vis (ref:
+// run_odometry_kitti_offline.cpp:432-471), which leaves the cloud to another program.
+ODO_HD void world_point(float X, float Y, float Z, const float* A, float* xw, float* yw, float* zw) {
+  *xw = ((A[0] * X + A[4] * Y) + A[8] * Z) + A[12];
+  *yw = ((A[1] * X + A[5] * Y) + A[9] * Z) + A[13];
+  *zw = ((A[2] * X + A[6] * Y) + A[10] * Z) + A[14];
+}
+// Voxel index of one world coordinate: floor(v / size), IEEE fp32 divide. False when |k| >= 2^20 (or v / size is not a
+// number): the point lies outside the 21-bit-per-axis key range of the map's voxel hash.
+ODO_HD bool voxel_index(float v, float size, int* k) {
+  const float q = floorf(v / size);
+  if (!(fabsf(q) < 1048576.0f)) return false;
+  *k = (int)q;
+  return true;
+}
+
 // ... then floor. Returns false when the point is skipped (ref: image_processing_global.h:54-59). ui/vi = floor(u), floor(v).
 ODO_HD bool warp_point(const PointK& p, const float* T, const LevelK& k, int rows, int cols, int* ui, int* vi) {
   float u, v;

@@ -3302,6 +3302,7 @@ extern "C" int odo_depth_report(const odo_depth* d, int* iters, float* cost, int
   return 0;
 }
 
+#include "map_api.hip.h"
 #include "tracker.hip.h"
 #include "batch.hip.h"
 #include "gather.hip.h"

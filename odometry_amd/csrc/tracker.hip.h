@@ -70,6 +70,13 @@ struct odo_tracker {
   int arm_pending, arm_on;   // the next Solve is to be armed from the wait loop (tracker_poll_next) / has been armed and waits for its word
   int next_ready;            // 1: ev_next was seen complete by the host while it waited for the Solve (tracker_poll_next): the next Solve's
                              // launches then go out without a wait packet in front of them (1.5 us of host time + the packet's processing)
+  // Keyframe map (odo_tracker_attach_map): every keyframe is inserted on the map's own stream, never waited for by the host while
+  // tracking. What hands its inputs back to a writer waits for it first: the slot's next depth job (d_val[slot], stream B) through
+  // ev_map[slot], the next promotion (the keyframe pyramids go back to the frame buffers) through tracker_map_fence.
+  odo_map* map;                // nullptr: no map, and nothing below is used
+  hipEvent_t ev_map[2];        // the map's stream: the insertion that read d_val[slot] is complete
+  std::atomic<int> map_wait[2];  // 1: the slot's next depth job waits for ev_map[slot] first (read by the helper thread)
+  int map_kf_slot;             // ev_map[map_kf_slot] covers the last insertion that read kf_img / kf_dep; -1: none pending
 };
 
 static void tracker_worker_main(odo_tracker* t);
@@ -118,6 +125,11 @@ extern "C" int odo_tracker_destroy(odo_tracker* t) {
   }
   if (t->ev_cur_img) (void)hipEventDestroy(t->ev_cur_img);
   if (t->ev_next) (void)hipEventDestroy(t->ev_next);
+  if (t->map) {
+    (void)map_sync(t->map);
+    t->map->attached = nullptr;
+  }
+  for (hipEvent_t e : t->ev_map) if (e) (void)hipEventDestroy(e);
   odo_ctx_destroy(t->ctx_c);
   odo_ctx_destroy(t->ctx_b);
   odo_ctx_destroy(t->ctx_a);
@@ -153,6 +165,7 @@ extern "C" int odo_tracker_create(int device, const odo_tracker_params* p, odo_t
   t->chain_used = t->chain_wasted = 0;
   t->dbg_pre_us = t->dbg_spin_us = t->dbg_chain_us = t->dbg_verdict_us = t->dbg_post_us = t->dbg_relaunch_us = 0.0; t->dbg_n = t->dbg_relaunch_n = 0;
   t->depth_ahead = getenv("ODO_NO_DEPTH_AHEAD") ? 0 : 1;
+  t->map = nullptr; t->ev_map[0] = t->ev_map[1] = nullptr; t->map_wait[0].store(0); t->map_wait[1].store(0); t->map_kf_slot = -1;
   t->p = *p;
   float eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   memcpy(t->pose_to_kf, eye, sizeof(eye));
@@ -208,6 +221,8 @@ static int tracker_job_begin(odo_tracker* t, TrackerJob* j) {
   j->err = 0;
   if (depth_check_size(t->depth, p.rows, p.cols)) return -1;
   if (depth_ensure(t->depth, p.rows, p.cols)) return -1;
+  if (t->map_wait[j->slot].exchange(0, std::memory_order_acquire))   // a map insertion still reads this slot's d_val
+    HIP_OK(hipStreamWaitEvent(t->ctx_b->stream, t->ev_map[j->slot], 0));
   if (depth_job_begin(t->depth, &j->dj, j->left, j->right, p.rows, p.cols, t->d_val[j->slot], t->d_disp[j->slot], t->d_dep[j->slot], 2))
     return -1;
   j->stage = 1;
@@ -353,9 +368,61 @@ extern "C" int odo_tracker_quiesce(odo_tracker* t) {
   HIP_OK(hipStreamSynchronize(t->ctx_a->stream));
   HIP_OK(hipStreamSynchronize(t->ctx_b->stream));
   HIP_OK(hipStreamSynchronize(t->ctx_c->stream));
+  if (t->map) {                            // pending keyframe insertions
+    if (map_sync(t->map)) return -1;
+    t->map_wait[0].store(0); t->map_wait[1].store(0); t->map_kf_slot = -1;
+  }
   t->lm->job.active = 0;                   // a Solve started early for an announced frame is dropped
   t->lm->chained.active = 0;
   t->prefetched = t->hint_next = t->hint_next_right = nullptr;  // announcements are void
+  return 0;
+}
+
+// The keyframe just promoted (or frame 0) into the attached map: mask d_val[slot], inverse depth = kf_dep level 0, intensity =
+// kf_img level 0, pose abs_pose (ref: run_odometry_kitti_offline.cpp:259-265, what save_to_vis exports). Its inputs are complete:
+// the host has seen the depth job's completion word (d_val, kf_dep) and the Solve's result, which the build of kf_img precedes.
+// So the map's stream waits for nothing, and nothing lands on stream A in front of the next Solve.
+static int tracker_map_insert(odo_tracker* t, int slot, const float* abs_pose) {
+  odo_map* m = t->map;
+  if (map_insert(m, t->d_val[slot], t->kf_dep->dev + t->kf_dep->off[0], t->kf_img->dev + t->kf_img->off[0], &t->p.K, abs_pose, m->own))
+    return -1;
+  HIP_OK(hipEventRecord(t->ev_map[slot], m->own));
+  t->map_wait[slot].store(1, std::memory_order_release);
+  t->map_kf_slot = slot;
+  return 0;
+}
+// Before a promotion hands the keyframe pyramids back to the frame buffers: the last insertion that reads them is complete (it was
+// enqueued a frame or more ago, so the host almost never waits here).
+static int tracker_map_fence(odo_tracker* t) {
+  if (t->map_kf_slot < 0) return 0;
+  const hipEvent_t e = t->ev_map[t->map_kf_slot];
+  t->map_kf_slot = -1;
+  if (hipEventQuery(e) != hipSuccess) {
+    (void)hipGetLastError();   // (hipErrorNotReady is not an error)
+    HIP_OK(hipEventSynchronize(e));
+  }
+  return 0;
+}
+
+extern "C" int odo_tracker_attach_map(odo_tracker* t, odo_map* m) {
+  if (!t) return fail("NULL tracker");
+  if (m == t->map) return 0;
+  if (m && m->attached) return fail("odo_tracker_attach_map: the map is attached to another tracker");
+  if (m && (m->device != t->ctx_a->device || m->rows != t->p.rows || m->cols != t->p.cols))
+    return fail("odo_tracker_attach_map: the map (device %d, %dx%d) does not match the tracker (device %d, %dx%d)", m->device, m->rows,
+                m->cols, t->ctx_a->device, t->p.rows, t->p.cols);
+  HIP_OK(hipSetDevice(t->ctx_a->device));
+  if (t->map) {   // detach: the insertions already enqueued complete first
+    if (map_sync(t->map)) return -1;
+    t->map_wait[0].store(0); t->map_wait[1].store(0); t->map_kf_slot = -1;
+    t->map->attached = nullptr;
+    t->map = nullptr;
+  }
+  if (m) {
+    for (hipEvent_t& e : t->ev_map) if (!e) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    m->attached = t;
+    t->map = m;
+  }
   return 0;
 }
 
@@ -386,6 +453,7 @@ extern "C" int odo_tracker_init(odo_tracker* t, const float* left, const float* 
   t->frame_id = 0;
   t->last_valid = j->stats.n_valid;
   t->last_depth_iters = j->stats.iters;
+  if (t->map && tracker_map_insert(t, j->slot, abs_pose0)) return -1;
   return 0;
 }
 
@@ -640,6 +708,7 @@ extern "C" int odo_tracker_track(odo_tracker* t, const float* left, const float*
   if (jk->rc) { t->lm->job.active = 0; return fail("    depth failed! (%s)", jk->msg); }   // :230-232
   int new_kf = 0;
   if (promote) {
+    if (t->map && tracker_map_fence(t)) return -1;
     std::swap(t->kf_img, t->cur_img);                                                  // :259 (the :251 rebuild == the :205 pyramid)
     std::swap(t->kf_dep, t->pre_dep[jk->slot]);
     memcpy(t->kf_abs, cur, sizeof(cur));                                               // :260
@@ -649,6 +718,7 @@ extern "C" int odo_tracker_track(odo_tracker* t, const float* left, const float*
   }
   if (!reset_done) odo_lm_reset(t->lm, T, 0.01f);                                      // :261 / :268 (both branches)
   if (early && promote && start_next_solve() < 0) return -1;   // against the new keyframe, as soon as its lists are adopted
+  if (new_kf && t->map && tracker_map_insert(t, jk->slot, cur)) return -1;   // (behind the next Solve's launches)
   if (pose_to_keyframe) memcpy(pose_to_keyframe, T, sizeof(T));
   if (abs_pose) memcpy(abs_pose, cur, sizeof(cur));
   if (is_new_keyframe) *is_new_keyframe = new_kf;
