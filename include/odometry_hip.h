@@ -451,6 +451,34 @@ int odo_map_destroy(odo_map* m);
  * the host while tracking; odo_tracker_quiesce / init / destroy drain them. Poses are unchanged. Same device and frame size as
  * the tracker; one tracker per map. NULL detaches (pending insertions complete first). */
 int odo_tracker_attach_map(odo_tracker* t, odo_map* m);
+/* ---- RGB-D tracking: a sensor depth frame in place of the stereo pair's ComputeDepth ----
+ * The reference's plan (README: "RGB-D odometry using the existing code blocks ... monocular RGB as well as Depth outputs from
+ * the sensor (TUM RGB-D dataset or Intel Realsense)"): the frame loop of odo_tracker_track with the depth of each frame taken from
+ * a sensor. Inputs per frame: a grey image (fp32 rows x cols, as the stereo tracker's left image) and a depth frame (uint16 rows x
+ * cols, dense row-major, device-resident; raw 0 = no reading). The depth job of a frame:
+ *   1. selection: the point selection of ComputeDepth (ref: src/depth_estimate.cpp:300-342) on the 3x3-blurred grey image — the
+ *      16 x 32 block grid inside `boundary`, block median + grad_th, the first <= 80 pixels per block in raster order;
+ *   2. each selected pixel p, r = raw[p]: r == 0 -> invalid; else d = depth_scale / (float)r (one IEEE fp32 divide), invalid if
+ *      1.0f / d > max_depth || 1.0f / d < min_depth (the write-back filter, ref: src/depth_estimate.cpp:183, stated on d); invalid
+ *      if a 4-neighbour q inside the image with raw[q] != 0 has (float)|raw[q] - r| > max_depth_step * (float)r (one fp32
+ *      rounding; neighbours outside the image are skipped; INFINITY turns the guard off). Valid: val = 1, dep = d; otherwise
+ *      val = 0, dep = 0. Unselected pixels: val = 0, dep = 0; disp = 0 everywhere;
+ *   3. statistics (odo_depth_report on odo_tracker_depth): n_selected, n_matched = selected with r != 0, n_valid; iters = 0,
+ *      cost = 0; status -1 ("depth failed") when n_valid < 500 (ref: src/depth_estimate.cpp:192), with the stereo tracker's
+ *      consequences in init and track.
+ * Everything behind the depth job — depth pyramid, keyframe-candidate lists, the helper thread, announced frames, the keyframe
+ * policy, attached maps — is the stereo tracker's. */
+/* Uses p's size, levels, lm_*, grad_th, boundary (>= 1: the selection's gradient reads the pixels next to its grid), min_depth /
+ * max_depth, K, keyframe weights / threshold, smooth_image and overlap_depth; ignores the stereo and depth-LM fields and implies
+ * any_size. depth_scale: raw units per metre (TUM 5000, RealSense 1000), finite and > 0; max_depth_step >= 0 (INFINITY: off). */
+int odo_tracker_create_rgbd(int device, const odo_tracker_params* p, float depth_scale, float max_depth_step, odo_tracker** out);
+/* odo_tracker_init / odo_tracker_track / odo_tracker_hint_next_pair for an RGB-D tracker (same contracts; the depth frame takes
+ * the right image's place). odo_tracker_hint_next (grey only), outputs, stats, timing, quiesce and attach_map work on either
+ * tracker; the stereo entries refuse an RGB-D tracker and these refuse a stereo one, without enqueueing anything. */
+int odo_tracker_init_rgbd(odo_tracker* t, const float* gray_dev, const uint16_t* depth_dev, const float abs_pose0_colmajor[16]);
+int odo_tracker_track_rgbd(odo_tracker* t, const float* gray_dev, const uint16_t* depth_dev, float pose_to_keyframe[16],
+                           float abs_pose[16], int* is_new_keyframe, float* motion_mag, int* solve_status);
+int odo_tracker_hint_next_rgbd(odo_tracker* t, const float* next_gray_dev, const uint16_t* next_depth_dev);
 /* Counters of the last tracked frame: LM evaluations, depth-LM iterations, valid depth points, keyframes so far. */
 int odo_tracker_stats(const odo_tracker* t, int* lm_evals, int* depth_iters, int* n_valid_depth, int* n_keyframes);
 /* Device pointers to the last frame's outputs (rows x cols): validity mask (u8), disparity, inverse depth. */

@@ -291,6 +291,69 @@ inline bool read_png_gray8(const std::string& path, std::vector<uint8_t>& pixels
   return true;
 }
 
+// 16-bit grey PNG (colour type 0, bit depth 16): the storage format of TUM RGB-D / RealSense depth frames (raw sensor units, 0 = no
+// reading). Samples are big-endian; the filters work on bytes with a filter distance of 2. Same size and inflate guards as
+// read_png_gray8; false for any other format.
+inline bool read_png_gray16(const std::string& path, std::vector<uint16_t>& pixels, int& width, int& height) {
+  std::ifstream f(path, std::ios::binary);
+  if (!f.is_open()) return false;
+  std::vector<uint8_t> d((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+  static const uint8_t sig[8] = {137, 80, 78, 71, 13, 10, 26, 10};
+  if (d.size() < 8 + 25 || std::memcmp(d.data(), sig, 8) != 0) return false;
+  size_t pos = 8;
+  std::vector<uint8_t> idat;
+  width = height = 0;
+  bool have_ihdr = false;
+  while (pos + 12 <= d.size()) {
+    const uint32_t len = detail::be32(&d[pos]);
+    const char* type = (const char*)&d[pos + 4];
+    if (pos + 12 + (size_t)len > d.size()) return false;
+    const uint8_t* body = &d[pos + 8];
+    if (!std::memcmp(type, "IHDR", 4)) {
+      if (len != 13) return false;
+      width = (int)detail::be32(body);
+      height = (int)detail::be32(body + 4);
+      if (body[8] != 16 || body[9] != 0 || body[10] != 0 || body[11] != 0 || body[12] != 0) return false;  // 16-bit grey only
+      have_ihdr = true;
+    } else if (!std::memcmp(type, "IDAT", 4)) {
+      idat.insert(idat.end(), body, body + len);
+    } else if (!std::memcmp(type, "IEND", 4)) {
+      break;
+    }
+    pos += 12 + (size_t)len;
+  }
+  if (!have_ihdr || width <= 0 || height <= 0 || width > 65535 || height > 65535) return false;
+  const size_t stride = 2 * (size_t)width;   // bytes per row, without the filter byte
+  const size_t raw_size = (stride + 1) * (size_t)height;
+  std::vector<uint8_t> raw;
+  raw.reserve(raw_size);
+  if (!detail::inflate(idat.data(), idat.size(), raw, raw_size)) return false;
+  if (raw.size() != raw_size) return false;
+  std::vector<uint8_t> rows(stride * (size_t)height);   // unfiltered bytes
+  for (int y = 0; y < height; y++) {
+    const uint8_t ft = raw[(size_t)y * (stride + 1)];
+    const uint8_t* src = &raw[(size_t)y * (stride + 1) + 1];
+    uint8_t* cur = &rows[(size_t)y * stride];
+    const uint8_t* up = y ? &rows[(size_t)(y - 1) * stride] : nullptr;
+    for (size_t x = 0; x < stride; x++) {
+      const int a = x >= 2 ? cur[x - 2] : 0, b = up ? up[x] : 0, c = (x >= 2 && up) ? up[x - 2] : 0;
+      int v = src[x];
+      switch (ft) {
+        case 0: break;
+        case 1: v += a; break;
+        case 2: v += b; break;
+        case 3: v += (a + b) / 2; break;
+        case 4: v += detail::paeth(a, b, c); break;
+        default: return false;
+      }
+      cur[x] = (uint8_t)v;
+    }
+  }
+  pixels.resize((size_t)width * height);
+  for (size_t i = 0; i < pixels.size(); i++) pixels[i] = (uint16_t)((rows[2 * i] << 8) | rows[2 * i + 1]);
+  return true;
+}
+
 // imread(GRAYSCALE) -> convertTo(CV_32F): fp32 pixels in 0..255 (ref: :342-348).
 inline bool read_png_gray_f32(const std::string& path, std::vector<float>& pixels, int& width, int& height) {
   std::vector<uint8_t> u8;

@@ -187,6 +187,10 @@ SIGNATURES = {
     "odo_map_clear": (C.c_int, [_vp]),
     "odo_map_destroy": (C.c_int, [_vp]),
     "odo_tracker_attach_map": (C.c_int, [_vp, _vp]),
+    "odo_tracker_create_rgbd": (C.c_int, [C.c_int, C.POINTER(TrackerParams), C.c_float, C.c_float, C.POINTER(_vp)]),
+    "odo_tracker_init_rgbd": (C.c_int, [_vp, _vp, _vp, _fp]),
+    "odo_tracker_track_rgbd": (C.c_int, [_vp, _vp, _vp, _fp, _fp, _ip, _fp, _ip]),
+    "odo_tracker_hint_next_rgbd": (C.c_int, [_vp, _vp, _vp]),
 }
 
 _lib = None

@@ -526,21 +526,25 @@ class Tracker:
 
     def __init__(self, device=0, **overrides):
         self.lib = L.load()
-        self.params = L.TrackerParams()
-        L.check(self.lib.odo_tracker_default_params(C.byref(self.params)), "odo_tracker_default_params")
-        for k, v in overrides.items():
-            if k == "lm_max_iters":
-                for i, m in enumerate(v):
-                    self.params.lm_max_iters[i] = m
-            elif k == "K":
-                self.params.K = L.Intrinsics(*v)
-            else:
-                setattr(self.params, k, v)
+        self.params = self._params(overrides)
         h = C.c_void_p()
         L.check(self.lib.odo_tracker_create(device, C.byref(self.params), C.byref(h)), "odo_tracker_create")
         self.h = h
         self._ctx = C.c_void_p(self.lib.odo_tracker_ctx(h))
         self._bufs = []
+
+    def _params(self, overrides):
+        params = L.TrackerParams()
+        L.check(self.lib.odo_tracker_default_params(C.byref(params)), "odo_tracker_default_params")
+        for k, v in overrides.items():
+            if k == "lm_max_iters":
+                for i, m in enumerate(v):
+                    params.lm_max_iters[i] = m
+            elif k == "K":
+                params.K = L.Intrinsics(*v)
+            else:
+                setattr(params, k, v)
+        return params
 
     def upload_frame(self, img):
         img = _f32(img)
@@ -699,6 +703,73 @@ class Tracker:
             self.close()
         except Exception:
             pass
+
+
+class RgbdTracker(Tracker):
+    """The frame loop with sensor depth (odo_tracker_create_rgbd): a grey image and a uint16 depth frame per frame instead of a
+    stereo pair. depth_scale: raw units per metre (TUM 5000, RealSense 1000); max_depth_step: the edge guard's relative step
+    (float("inf"): off). Everything else — overrides, outputs, stats, timing, attach_map — as Tracker."""
+
+    def __init__(self, device=0, depth_scale=5000.0, max_depth_step=0.05, **overrides):
+        self.lib = L.load()
+        self.params = self._params(overrides)
+        h = C.c_void_p()
+        L.check(self.lib.odo_tracker_create_rgbd(device, C.byref(self.params), float(depth_scale), float(max_depth_step), C.byref(h)),
+                "odo_tracker_create_rgbd")
+        self.h = h
+        self._ctx = C.c_void_p(self.lib.odo_tracker_ctx(h))
+        self._bufs = []
+        self.depth_scale, self.max_depth_step = float(depth_scale), float(max_depth_step)
+
+    def upload_depth(self, raw):
+        """A uint16 depth frame (rows x cols) into a device buffer owned by the tracker."""
+        raw = np.ascontiguousarray(raw, np.uint16)
+        p = C.c_void_p()
+        L.check(self.lib.odo_dev_alloc(self._ctx, raw.nbytes, C.byref(p)), "odo_dev_alloc")
+        L.check(self.lib.odo_dev_upload(self._ctx, p, raw.ctypes.data_as(C.c_void_p), raw.nbytes), "odo_dev_upload")
+        self._bufs.append(p)
+        return p
+
+    def init(self, gray_dev, depth_dev, abs_pose0=None):
+        pose = _colmajor(np.eye(4) if abs_pose0 is None else abs_pose0)
+        L.check(self.lib.odo_tracker_init_rgbd(self.h, gray_dev, depth_dev, _fp(pose)), "odo_tracker_init_rgbd")
+
+    def track(self, gray_dev, depth_dev):
+        T = np.zeros(16, np.float32)
+        A = np.zeros(16, np.float32)
+        nk, ss = C.c_int(0), C.c_int(0)
+        mag = C.c_float(0)
+        st = self.lib.odo_tracker_track_rgbd(self.h, gray_dev, depth_dev, _fp(T), _fp(A), C.byref(nk), C.byref(mag), C.byref(ss))
+        if st != 0:
+            raise L.OdoError("odo_tracker_track_rgbd: " + L.last_error())
+        return dict(pose_to_keyframe=_from_colmajor(T), abs_pose=_from_colmajor(A), new_keyframe=bool(nk.value),
+                    motion=mag.value, solve_status=ss.value)
+
+    def hint_next(self, gray_dev, depth_dev=None):
+        """Announce the next frame: grey image only (pyramid prefetch + early start of the next Solve) or with its depth frame (the
+        depth stream then works a frame ahead as well)."""
+        if depth_dev is None:
+            L.check(self.lib.odo_tracker_hint_next(self.h, gray_dev), "odo_tracker_hint_next")
+        else:
+            L.check(self.lib.odo_tracker_hint_next_rgbd(self.h, gray_dev, depth_dev), "odo_tracker_hint_next_rgbd")
+
+    def track_into(self, gray_dev, depth_dev, pose_to_kf, abs_pose):
+        """Lean variant for timing loops: results land in caller-owned float32[16] column-major buffers."""
+        if not hasattr(self, "_nk"):
+            self._nk, self._ss, self._mag = C.c_int(0), C.c_int(0), C.c_float(0)
+        st = self.lib.odo_tracker_track_rgbd(self.h, gray_dev, depth_dev, _fp(pose_to_kf), _fp(abs_pose), C.byref(self._nk),
+                                             C.byref(self._mag), C.byref(self._ss))
+        if st != 0:
+            raise L.OdoError("odo_tracker_track_rgbd: " + L.last_error())
+        return self._nk.value
+
+    def depth_report(self):
+        """The last frame's depth statistics (odo_depth_report): iters, cost, n_selected, n_matched, n_valid."""
+        d = C.c_void_p(self.lib.odo_tracker_depth(self.h))
+        it, n1, n2, n3 = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        cost = C.c_float(0)
+        L.check(self.lib.odo_depth_report(d, C.byref(it), C.byref(cost), C.byref(n1), C.byref(n2), C.byref(n3)), "odo_depth_report")
+        return dict(iters=it.value, cost=cost.value, n_selected=n1.value, n_matched=n2.value, n_valid=n3.value)
 
 
 class PointMap:

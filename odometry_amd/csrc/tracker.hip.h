@@ -3,10 +3,14 @@
 // next frame's image pyramid).
 // Included by odometry_hip.hip after the pyramid / LM / depth objects are defined.
 #pragma once
+#include <stddef.h>
+#include <algorithm>
+#include <cmath>
 
 // One frame's stream-B work: ComputeDepth of the pair, the depth pyramid, the keyframe-candidate point lists. Two of them
 // exist (slot 0 / 1, each with its own outputs) so that the depth stream can work on the NEXT frame while the pose LM is
-// still on this one (odo_tracker_hint_next_pair).
+// still on this one (odo_tracker_hint_next_pair). An RGB-D tracker's job converts a sensor depth frame instead of ComputeDepth
+// (rgbd_job_begin); the frame rides in `right`.
 struct TrackerJob {
   const float *left, *right;
   odo_pyr* img;           // the frame's image pyramid (source of the candidate lists)
@@ -77,6 +81,10 @@ struct odo_tracker {
   hipEvent_t ev_map[2];        // the map's stream: the insertion that read d_val[slot] is complete
   std::atomic<int> map_wait[2];  // 1: the slot's next depth job waits for ev_map[slot] first (read by the helper thread)
   int map_kf_slot;             // ev_map[map_kf_slot] covers the last insertion that read kf_img / kf_dep; -1: none pending
+  // Depth source (odo_tracker_create_rgbd): 1 = a uint16 sensor depth frame per frame instead of the right image. Only the stream-B
+  // job's front differs (rgbd_job_begin / rgbd_job_stats); everything behind it is the stereo tracker's.
+  int rgbd;
+  float depth_scale, max_depth_step;
 };
 
 static void tracker_worker_main(odo_tracker* t);
@@ -137,8 +145,7 @@ extern "C" int odo_tracker_destroy(odo_tracker* t) {
   return 0;
 }
 
-extern "C" int odo_tracker_create(int device, const odo_tracker_params* p, odo_tracker** out) {
-  if (!p || !out) return fail("odo_tracker_create: NULL arg");
+static int tracker_create(int device, const odo_tracker_params* p, int rgbd, float depth_scale, float max_depth_step, odo_tracker** out) {
   *out = nullptr;
   odo_tracker* t = new (std::nothrow) odo_tracker();
   if (!t) return fail("out of memory");
@@ -166,6 +173,7 @@ extern "C" int odo_tracker_create(int device, const odo_tracker_params* p, odo_t
   t->dbg_pre_us = t->dbg_spin_us = t->dbg_chain_us = t->dbg_verdict_us = t->dbg_post_us = t->dbg_relaunch_us = 0.0; t->dbg_n = t->dbg_relaunch_n = 0;
   t->depth_ahead = getenv("ODO_NO_DEPTH_AHEAD") ? 0 : 1;
   t->map = nullptr; t->ev_map[0] = t->ev_map[1] = nullptr; t->map_wait[0].store(0); t->map_wait[1].store(0); t->map_kf_slot = -1;
+  t->rgbd = rgbd; t->depth_scale = depth_scale; t->max_depth_step = max_depth_step;
   t->p = *p;
   float eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   memcpy(t->pose_to_kf, eye, sizeof(eye));
@@ -180,9 +188,12 @@ extern "C" int odo_tracker_create(int device, const odo_tracker_params* p, odo_t
             odo_ctx_create(device, &t->ctx_b) == 0 && odo_ctx_create(device, &t->ctx_c) == 0;
   ok = ok && odo_lm_create(t->ctx_a, p->lm_lambda, p->lm_precision, p->lm_max_iters, p->levels, eye, p->lm_robust,
                            p->lm_huber_delta, &p->K, &t->lm) == 0;
+  // (an RGB-D tracker's estimator only blurs, selects and carries the statistics: its boundary may be below the 8-tap pattern's 2, and
+  //  it never issues the depth LM's persistent launch)
   ok = ok && odo_depth_create(t->ctx_b, p->grad_th, p->ssd_th, p->photo_th, p->min_depth, p->max_depth, p->depth_lambda,
-                              p->depth_huber_delta, p->depth_precision, p->depth_max_iters, p->boundary, &p->K, p->baseline,
-                              p->max_residuals, p->max_disparity, p->any_size, &t->depth) == 0;
+                              p->depth_huber_delta, p->depth_precision, p->depth_max_iters, rgbd ? std::max(p->boundary, 2) : p->boundary,
+                              &p->K, p->baseline, p->max_residuals, p->max_disparity, p->any_size, &t->depth) == 0;
+  if (ok && rgbd) { t->depth->boundary = p->boundary; t->depth->persist = t->depth->persist_cfg = 0; }
   ok = ok && pyr_alloc(t->ctx_a, p->rows, p->cols, p->levels, ODO_PYR_IMAGE, &t->cur_img, false) == 0;
   ok = ok && pyr_alloc(t->ctx_a, p->rows, p->cols, p->levels, ODO_PYR_IMAGE, &t->next_img, false) == 0;
   ok = ok && pyr_alloc(t->ctx_b, p->rows, p->cols, p->levels, ODO_PYR_IMAGE, &t->kf_img, false) == 0;
@@ -214,6 +225,58 @@ extern "C" int odo_tracker_create(int device, const odo_tracker_params* p, odo_t
   return 0;
 }
 
+extern "C" int odo_tracker_create(int device, const odo_tracker_params* p, odo_tracker** out) {
+  if (!p || !out) return fail("odo_tracker_create: NULL arg");
+  return tracker_create(device, p, 0, 0.0f, 0.0f, out);
+}
+
+extern "C" int odo_tracker_create_rgbd(int device, const odo_tracker_params* p, float depth_scale, float max_depth_step, odo_tracker** out) {
+  if (!p || !out) return fail("odo_tracker_create_rgbd: NULL arg");
+  *out = nullptr;
+  if (!(std::isfinite(depth_scale) && depth_scale > 0.0f)) return fail("odo_tracker_create_rgbd: depth_scale must be finite and > 0");
+  if (!(max_depth_step >= 0.0f)) return fail("odo_tracker_create_rgbd: max_depth_step must be >= 0 (INFINITY: no edge guard)");
+  // the point selection's gradient reads the pixels next to every pixel of its grid: the grid must keep one pixel off the edges
+  if (p->boundary < 1) return fail("odo_tracker_create_rgbd: boundary must be >= 1 (the selection's gradient reads +-1)");
+  odo_tracker_params q = *p;
+  q.any_size = 1;
+  return tracker_create(device, &q, 1, depth_scale, max_depth_step, out);
+}
+
+// The RGB-D front end in place of ComputeDepth (include/odometry_hip.h, odo_tracker_create_rgbd): blur of the grey frame (its launch
+// zero-fills val / disp / dep) and the point selection, both the stereo job's own launches, then the sensor-depth conversion of the
+// selected pixels (rgbd_kernels.hip). The depth frame is j->right.
+static_assert(kRgbdSlots == kSelBlocks * kSelCap && kRgbdSelCap == kSelCap && kRgbdBlock == kDlmBlock && kRgbdBlocks == kDlmBlocks,
+              "the sensor-depth kernels walk the selection's slots and write depth_finalize_kernel's count layout");
+static_assert(sizeof(RgbdStats) == sizeof(DepthLmStats) && offsetof(RgbdStats, n_valid) == offsetof(DepthLmStats, n_valid) &&
+              offsetof(RgbdStats, status) == offsetof(DepthLmStats, status), "RgbdStats is DepthLmStats' layout");
+static int rgbd_job_begin(odo_tracker* t, TrackerJob* j) {
+  const odo_tracker_params& p = t->p;
+  odo_depth* d = t->depth;
+  hipStream_t s = t->ctx_b->stream;
+  uint8_t* val = t->d_val[j->slot];
+  float* dep = t->d_dep[j->slot];
+  hipLaunchKernelGGL(blur3x3_kernel, grid2d(p.cols, p.rows, 1), dim3(256), 0, s, j->left, d->d_bl, j->left, d->d_bl, p.rows, p.cols, val,
+                     t->d_disp[j->slot], dep);
+  // (no mask from the selection: the conversion writes every selected pixel's val)
+  hipLaunchKernelGGL(depth_select_kernel, dim3(kSelBlocks), dim3(kSelThreads), 0, s, (const float*)d->d_bl, p.rows, p.cols, d->boundary,
+                     d->grad_th, (uint8_t*)nullptr, d->d_pts, d->d_cnt);
+  RgbdDepthArgs a;
+  a.raw = (const uint16_t*)j->right; a.pts = d->d_pts; a.cnt = d->d_cnt; a.rows = p.rows; a.cols = p.cols;
+  a.depth_scale = t->depth_scale; a.max_depth_step = t->max_depth_step; a.min_depth = p.min_depth; a.max_depth = p.max_depth;
+  a.val = val; a.dep = dep; a.counts = d->d_counts;
+  launch_rgbd_depth(a, s);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+// The statistics and the completion word that depth_finish waits for (depth_job_stats of the stereo job).
+static int rgbd_job_stats(odo_tracker* t) {
+  odo_depth* d = t->depth;
+  d->token++;
+  launch_rgbd_stats(d->d_counts, (RgbdStats*)d->d_stats_map, d->d_prog + 4, d->token, t->ctx_b->stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 // ComputeDepth of the pair and the frame's keyframe-candidate pyramids, all on stream B (ref: :226-252), as a
 // resumable job: begin enqueues the front, pump issues one more launch when the device is ready for it.
 static int tracker_job_begin(odo_tracker* t, TrackerJob* j) {
@@ -223,14 +286,15 @@ static int tracker_job_begin(odo_tracker* t, TrackerJob* j) {
   if (depth_ensure(t->depth, p.rows, p.cols)) return -1;
   if (t->map_wait[j->slot].exchange(0, std::memory_order_acquire))   // a map insertion still reads this slot's d_val
     HIP_OK(hipStreamWaitEvent(t->ctx_b->stream, t->ev_map[j->slot], 0));
-  if (depth_job_begin(t->depth, &j->dj, j->left, j->right, p.rows, p.cols, t->d_val[j->slot], t->d_disp[j->slot], t->d_dep[j->slot], 2))
+  if (t->rgbd ? rgbd_job_begin(t, j)
+              : depth_job_begin(t->depth, &j->dj, j->left, j->right, p.rows, p.cols, t->d_val[j->slot], t->d_disp[j->slot], t->d_dep[j->slot], 2))
     return -1;
   j->stage = 1;
   return 0;
 }
 static void tracker_job_pump_one(odo_tracker* t, TrackerJob* j) {
   if (j->stage != 1) return;
-  const int r = depth_job_pump(t->depth, &j->dj);
+  const int r = t->rgbd ? 1 : depth_job_pump(t->depth, &j->dj);   // (an RGB-D front end is enqueued whole by tracker_job_begin)
   if (r < 0) { j->err = 1; j->stage = 3; return; }
   if (r > 0) {
     const odo_tracker_params& p = t->p;
@@ -246,7 +310,7 @@ static void tracker_job_pump_one(odo_tracker* t, TrackerJob* j) {
     } else {
       t->lm->cand[j->slot].tag = -1;
     }
-    if (depth_job_stats(t->depth, &j->dj)) j->err = 1;  // completion word AFTER the pyramids: it covers them too
+    if (t->rgbd ? rgbd_job_stats(t) : depth_job_stats(t->depth, &j->dj)) j->err = 1;  // completion word AFTER the pyramids: it covers them too
     j->stage = 3;
   }
 }
@@ -426,8 +490,8 @@ extern "C" int odo_tracker_attach_map(odo_tracker* t, odo_map* m) {
   return 0;
 }
 
-extern "C" int odo_tracker_init(odo_tracker* t, const float* left, const float* right, const float abs_pose0[16]) {
-  if (!t || !left || !right || !abs_pose0) return fail("odo_tracker_init: NULL arg");
+// Frame 0 of a sequence, either depth source (right: the right image, or an RGB-D tracker's depth frame).
+static int tracker_init(odo_tracker* t, const float* left, const float* right, const float abs_pose0[16]) {
   HIP_OK(hipSetDevice(t->ctx_a->device));
   // Re-initialisation of a tracker that has been tracking: a job posted ahead for the previous sequence's next frame, the
   // tail of the last frame (a prefetched next pyramid, straggling LM launches, an early Solve) may still be running.
@@ -455,6 +519,17 @@ extern "C" int odo_tracker_init(odo_tracker* t, const float* left, const float* 
   t->last_depth_iters = j->stats.iters;
   if (t->map && tracker_map_insert(t, j->slot, abs_pose0)) return -1;
   return 0;
+}
+
+extern "C" int odo_tracker_init(odo_tracker* t, const float* left, const float* right, const float abs_pose0[16]) {
+  if (!t || !left || !right || !abs_pose0) return fail("odo_tracker_init: NULL arg");
+  if (t->rgbd) return fail("odo_tracker_init: an RGB-D tracker (odo_tracker_create_rgbd) takes odo_tracker_init_rgbd");
+  return tracker_init(t, left, right, abs_pose0);
+}
+extern "C" int odo_tracker_init_rgbd(odo_tracker* t, const float* gray_dev, const uint16_t* depth_dev, const float abs_pose0[16]) {
+  if (!t || !gray_dev || !depth_dev || !abs_pose0) return fail("odo_tracker_init_rgbd: NULL arg");
+  if (!t->rgbd) return fail("odo_tracker_init_rgbd: a stereo tracker (odo_tracker_create) takes odo_tracker_init");
+  return tracker_init(t, gray_dev, (const float*)depth_dev, abs_pose0);
 }
 
 // Inverse of a 4x4 (Eigen Matrix4f::inverse(), ref: run_odometry_kitti_offline.cpp:218): Gauss-Jordan in fp64,
@@ -493,9 +568,9 @@ static void motion_angles(const float* T, float ang[3]) {
   ang[2] = atan2f(R[3] - R[1], R[0] + R[4]);
 }
 
-extern "C" int odo_tracker_track(odo_tracker* t, const float* left, const float* right, float pose_to_keyframe[16],
-                                 float abs_pose[16], int* is_new_keyframe, float* motion_mag, int* solve_status) {
-  if (!t || !left || !right) return fail("odo_tracker_track: NULL arg");
+// One frame of the loop, either depth source (right: the right image, or an RGB-D tracker's depth frame).
+static int tracker_track(odo_tracker* t, const float* left, const float* right, float pose_to_keyframe[16], float abs_pose[16],
+                         int* is_new_keyframe, float* motion_mag, int* solve_status) {
   const odo_tracker_params& p = t->p;
   const auto f0 = std::chrono::steady_clock::now();
   HIP_OK(hipSetDevice(t->ctx_a->device));
@@ -743,6 +818,19 @@ extern "C" int odo_tracker_track(odo_tracker* t, const float* left, const float*
   return 0;
 }
 
+extern "C" int odo_tracker_track(odo_tracker* t, const float* left, const float* right, float pose_to_keyframe[16],
+                                 float abs_pose[16], int* is_new_keyframe, float* motion_mag, int* solve_status) {
+  if (!t || !left || !right) return fail("odo_tracker_track: NULL arg");
+  if (t->rgbd) return fail("odo_tracker_track: an RGB-D tracker (odo_tracker_create_rgbd) takes odo_tracker_track_rgbd");
+  return tracker_track(t, left, right, pose_to_keyframe, abs_pose, is_new_keyframe, motion_mag, solve_status);
+}
+extern "C" int odo_tracker_track_rgbd(odo_tracker* t, const float* gray_dev, const uint16_t* depth_dev, float pose_to_keyframe[16],
+                                      float abs_pose[16], int* is_new_keyframe, float* motion_mag, int* solve_status) {
+  if (!t || !gray_dev || !depth_dev) return fail("odo_tracker_track_rgbd: NULL arg");
+  if (!t->rgbd) return fail("odo_tracker_track_rgbd: a stereo tracker (odo_tracker_create) takes odo_tracker_track");
+  return tracker_track(t, gray_dev, (const float*)depth_dev, pose_to_keyframe, abs_pose, is_new_keyframe, motion_mag, solve_status);
+}
+
 // Host-clock averages per tracked frame since the last call (microseconds): whole track() call, Solve (stream A, calling
 // thread), the stream-B job (helper thread), and the time the calling thread waited for the helper after its own work.
 extern "C" int odo_tracker_timing(odo_tracker* t, double out[4]) {
@@ -764,8 +852,17 @@ extern "C" int odo_tracker_hint_next(odo_tracker* t, const float* next_left_dev)
 // (the depth stream runs a frame ahead of the pose LM, so a short Solve no longer waits for it).
 extern "C" int odo_tracker_hint_next_pair(odo_tracker* t, const float* next_left_dev, const float* next_right_dev) {
   if (!t) return fail("NULL tracker");
+  if (t->rgbd) return fail("odo_tracker_hint_next_pair: an RGB-D tracker (odo_tracker_create_rgbd) takes odo_tracker_hint_next_rgbd");
   t->hint_next = next_left_dev;
   t->hint_next_right = next_left_dev ? next_right_dev : nullptr;
+  return 0;
+}
+// The same for an RGB-D tracker: the next frame's grey image and depth frame.
+extern "C" int odo_tracker_hint_next_rgbd(odo_tracker* t, const float* next_gray_dev, const uint16_t* next_depth_dev) {
+  if (!t) return fail("NULL tracker");
+  if (!t->rgbd) return fail("odo_tracker_hint_next_rgbd: a stereo tracker (odo_tracker_create) takes odo_tracker_hint_next_pair");
+  t->hint_next = next_gray_dev;
+  t->hint_next_right = next_gray_dev ? (const float*)next_depth_dev : nullptr;
   return 0;
 }
 

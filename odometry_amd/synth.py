@@ -16,6 +16,8 @@ KITTI_CX = 607.1928
 KITTI_CY = 185.2157
 KITTI_BASELINE = 386.1448 / 718.856
 KITTI_ROWS, KITTI_COLS = 376, 1241
+TUM_F, TUM_CX, TUM_CY = 525.0, 319.5, 239.5   # TUM RGB-D-shaped sensor (640 x 480)
+TUM_ROWS, TUM_COLS = 480, 640
 
 
 def _value_noise(rng, size, octaves, first_cell):
@@ -232,6 +234,30 @@ def make_sequence(n_frames, seed=0, rows=KITTI_ROWS, cols=KITTI_COLS, f=KITTI_F,
         out["right"].append(Rimg)
         if with_depth:
             out["depth"].append(Z)
+    return out
+
+
+def sensor_depth(Z, depth_scale=1000.0, max_range=30.0):
+    """An RGB-D sensor's uint16 depth frame of the z-depth Z (metres): round(Z * depth_scale) where Z <= max_range and the value fits
+    in 16 bits, else 0 (no reading)."""
+    raw = np.rint(np.asarray(Z, np.float64) * depth_scale)
+    ok = np.isfinite(raw) & (np.asarray(Z) <= max_range) & (raw <= 65535)
+    return np.where(ok, raw, 0).astype(np.uint16)
+
+
+def make_rgbd_sequence(n_frames, seed=0, drive="natural", fwd_range=(0.1, 0.2), depth_scale=1000.0, max_range=30.0, rows=TUM_ROWS,
+                       cols=TUM_COLS, f=TUM_F, cx=TUM_CX, cy=TUM_CY):
+    """An RGB-D drive: grey frames of the named drive's scene (Scene.render) and the sensor's depth frames (sensor_depth), along the
+    drive's trajectory with fwd_range metres per frame. TUM-shaped by default. Returns dict(gray=[...], depth=[uint16 ...],
+    poses=[c2w ...], K=dict(f0, cx0, cy0), depth_scale, max_range)."""
+    scene = drive_scene(drive, seed)
+    kw = {k: v for k, v in DRIVES[drive].items() if k not in ("scene", "fwd_range")}
+    poses = trajectory(n_frames, seed, fwd_range=fwd_range, **kw)
+    out = dict(gray=[], depth=[], poses=poses, K=dict(f0=f, cx0=cx, cy0=cy), depth_scale=depth_scale, max_range=max_range)
+    for T in poses:
+        img, Z = scene.render(T, rows, cols, f, cx, cy, 0.0)
+        out["gray"].append(img)
+        out["depth"].append(sensor_depth(Z, depth_scale, max_range))
     return out
 
 
