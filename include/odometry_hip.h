@@ -32,6 +32,7 @@ typedef struct odo_depth odo_depth;
 typedef struct odo_tracker odo_tracker;
 typedef struct odo_camera odo_camera;
 typedef struct odo_map odo_map;
+typedef struct odo_rgbd_frontend odo_rgbd_frontend;
 
 /* Level-0 pinhole intrinsics (fy = fx). NULL wherever accepted = the KITTI-00 constants the reference
  * hard-codes (ref: include/image_processing_global.h:35-36: 718.856f, 607.1928, 185.2157). */
@@ -506,6 +507,68 @@ int odo_tracker_arm_stats(const odo_tracker* t, long* started, long* returned);
 odo_lm* odo_tracker_lm(odo_tracker* t);
 odo_depth* odo_tracker_depth(odo_tracker* t);   /* its depth estimator (odo_depth_persistent_stats, odo_depth_report) */
 odo_ctx* odo_tracker_ctx(odo_tracker* t);
+
+/* ---- RGB-D front end: raw sensor frames -> the RGB-D tracker's inputs ----------------------------------------------------------
+ * A sensor delivers interleaved 8-bit colour and a uint16 depth frame in the DEPTH imager's pixel grid (its own intrinsics, often
+ * its own resolution, centimetres beside the colour imager); odo_tracker_*_rgbd take an fp32 grey image and a uint16 depth frame in
+ * the GREY camera's grid. The front end makes the second from the first on the device, three launches per frame on a stream of
+ * its own, into a ring of output slots, so that frame k + 1 is prepared while the tracker works on frame k.
+ * All floating point is fp32, one rounding per operation.
+ * Grey. Colour frame rows x cols, 3 or 4 interleaved uint8 channels in the order RGB(A) or BGR(A), dense rows:
+ *   grey = (float)((R * 4899 + G * 9617 + B * 1868 + 8192) >> 14) in integer arithmetic (the 8-bit BT.601 fixed-point rule; the
+ *   weights sum to 16384, so R = G = B = v gives v). A fourth channel is ignored.
+ * Registration. Depth frame depth_rows x depth_cols, 0 = no reading, depth_scale_in raw units per metre, pinhole (depth_fx,
+ * depth_fy, depth_cx, depth_cy); target: rows x cols, K, depth_scale_out raw units per metre; colour_from_depth E = [R | t]
+ * (metres): P_c = R P_d + t. For every depth pixel (x, y) with r = raw[y][x] != 0:
+ *   1. z = (float)r / depth_scale_in;
+ *   2. for s in {-0.5, 0, +0.5}: X = (((float)x + s) - depth_cx) / depth_fx * z, Y = (((float)y + s) - depth_cy) / depth_fy * z
+ *      (left to right), then row i of the transform as ((R[i][0] X + R[i][1] Y) + R[i][2] z) + t[i]: the two footprint corners
+ *      (X0, Y0, Z0) (s = -0.5), (X1, Y1, Z1) (s = +0.5) and the centre depth Zm (s = 0);
+ *   3. dropped (dropped_behind) unless Z0 > 0 && Z1 > 0 && Zm > 0;
+ *   4. q = rintf(Zm * depth_scale_out); dropped (dropped_range) unless 1 <= q <= 65535;
+ *   5. u0 = f0 * (X0 / Z0) + cx0, u1 = f0 * (X1 / Z1) + cx0, likewise v0, v1 with Y and cy0; dropped (dropped_range) if any is
+ *      not finite. Columns ceil(min(u0, u1)) .. ceil(max(u0, u1)) - 1 and rows likewise: the target pixels whose centres lie in
+ *      the half-open footprint. A range wider or taller than 4 drops the pixel (dropped_splat); an empty range writes nothing and
+ *      is not a drop; the part of the range inside the image receives q;
+ *   6. a target pixel's value is the minimum q it received, 0 if it received none.
+ * With E = identity, equal intrinsics and equal scales the output equals the input bit for bit, and the result does not depend on
+ * the order of the writes. Lens distortion of either imager and colour cameras with fx != fy are outside this model. */
+typedef struct {
+  int depth_rows, depth_cols;
+  float depth_fx, depth_fy, depth_cx, depth_cy;
+  float depth_scale_in;
+  int rows, cols;              /* the tracker's frame */
+  odo_intrinsics K;
+  float depth_scale_out;
+  float colour_from_depth[12]; /* row-major 3 x 4, metres */
+  int colour_channels;         /* 3 | 4 */
+  int colour_bgr;              /* 0: RGB(A), 1: BGR(A) */
+  int slots;                   /* output ring, 2 ... 8 */
+} odo_rgbd_frontend_params;
+/* Validates everything (sizes > 0, finite positive focal lengths and scales, finite principal points and extrinsic, channels 3 | 4,
+ * slots 2 .. 8) before it touches the device. Device memory: 6 B per target pixel and slot + 4 B per target pixel (+ one raw frame per slot once submit_host is used). Uploads of
+ * odo_rgbd_frontend_submit_host run on ctx's stream; ctx must outlive the front end. One host thread at a time per front end. */
+int odo_rgbd_frontend_create(odo_ctx* ctx, const odo_rgbd_frontend_params* p, odo_rgbd_frontend** out);
+/* Enqueues one frame on the front end's stream and returns at once. *gray_out / *depth_out: the ring slot the results go to (rows x
+ * cols fp32 / uint16, dense). colour_dev (4-byte aligned) and depth_dev must be complete when the call is made and stay unchanged
+ * until the slot is complete. A slot is reused `slots` submits later: the caller must not have a slot's buffers announced to, or
+ * in use by, a tracker when the slot comes round again (the "unchanged until consumed" rule of odo_tracker_hint_next_pair).
+ * Refuses (-1, nothing enqueued) while `slots` frames are outstanding that the caller never waited for; waiting for a frame
+ * accounts for every earlier frame as well. */
+int odo_rgbd_frontend_submit_dev(odo_rgbd_frontend* f, const uint8_t* colour_dev, const uint16_t* depth_dev, const float** gray_out,
+                                 const uint16_t** depth_out);
+/* The same from host memory (row pitches in bytes): uploads through the context's pinned staging path (the caller's buffers may
+ * be reused on return unless they are odo_host_alloc blocks: then after the upload's ticket), then the kernels. */
+int odo_rgbd_frontend_submit_host(odo_rgbd_frontend* f, const uint8_t* colour, size_t colour_pitch, const uint16_t* depth,
+                                  size_t depth_pitch, const float** gray_out, const uint16_t** depth_out);
+/* Host wait until the slot with that grey buffer is complete; its two buffers may then be handed to odo_tracker_init_rgbd /
+ * _track_rgbd / _hint_next_rgbd. -1 if no frame was ever submitted to that slot. */
+int odo_rgbd_frontend_wait(odo_rgbd_frontend* f, const float* gray_out);
+/* out: n_depth (depth pixels with r != 0), n_filled (target pixels with a value), dropped_behind, dropped_range, dropped_splat,
+ * frame number (0-based count of submits). Waits for the slot. */
+int odo_rgbd_frontend_stats(odo_rgbd_frontend* f, const float* gray_out, long out[6]);
+/* Frames in flight are completed first. */
+int odo_rgbd_frontend_destroy(odo_rgbd_frontend* f);
 
 /* ---- S sequences in lock step on one GPU (the data-parallel axis of SURVEY section 8e inside one device) -----------------
  * One odo_tracker tracks one sequence as a serial chain of ~70 short launches per frame, which leaves most of the chip

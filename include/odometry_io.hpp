@@ -354,6 +354,70 @@ inline bool read_png_gray16(const std::string& path, std::vector<uint16_t>& pixe
   return true;
 }
 
+// 8-bit colour PNG (colour type 2 = RGB or 6 = RGBA, bit depth 8, non-interlaced): the storage format of TUM RGB-D rgb/*.png and of
+// RealSense colour captures. pixels: interleaved, `channels` (3 or 4) bytes per pixel in the file's order R, G, B(, A), dense rows —
+// what odo_rgbd_frontend_submit_host takes with colour_bgr = 0. Same size and inflate guards as read_png_gray8; false for any other
+// format (16-bit, grey, palette, interlaced) or a malformed file.
+inline bool read_png_rgb8(const std::string& path, std::vector<uint8_t>& pixels, int& width, int& height, int& channels) {
+  std::ifstream f(path, std::ios::binary);
+  if (!f.is_open()) return false;
+  std::vector<uint8_t> d((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+  static const uint8_t sig[8] = {137, 80, 78, 71, 13, 10, 26, 10};
+  if (d.size() < 8 + 25 || std::memcmp(d.data(), sig, 8) != 0) return false;
+  size_t pos = 8;
+  std::vector<uint8_t> idat;
+  width = height = channels = 0;
+  bool have_ihdr = false;
+  while (pos + 12 <= d.size()) {
+    const uint32_t len = detail::be32(&d[pos]);
+    const char* type = (const char*)&d[pos + 4];
+    if (pos + 12 + (size_t)len > d.size()) return false;
+    const uint8_t* body = &d[pos + 8];
+    if (!std::memcmp(type, "IHDR", 4)) {
+      if (len != 13) return false;
+      width = (int)detail::be32(body);
+      height = (int)detail::be32(body + 4);
+      if (body[8] != 8 || (body[9] != 2 && body[9] != 6) || body[10] != 0 || body[11] != 0 || body[12] != 0) return false;
+      channels = body[9] == 2 ? 3 : 4;
+      have_ihdr = true;
+    } else if (!std::memcmp(type, "IDAT", 4)) {
+      idat.insert(idat.end(), body, body + len);
+    } else if (!std::memcmp(type, "IEND", 4)) {
+      break;
+    }
+    pos += 12 + (size_t)len;
+  }
+  if (!have_ihdr || width <= 0 || height <= 0 || width > 65535 || height > 65535) return false;
+  const size_t bpp = (size_t)channels;               // the filters' distance in bytes
+  const size_t stride = bpp * (size_t)width;         // bytes per row, without the filter byte
+  const size_t raw_size = (stride + 1) * (size_t)height;
+  std::vector<uint8_t> raw;
+  raw.reserve(raw_size);
+  if (!detail::inflate(idat.data(), idat.size(), raw, raw_size)) return false;
+  if (raw.size() != raw_size) return false;
+  pixels.assign(stride * (size_t)height, 0);
+  for (int y = 0; y < height; y++) {
+    const uint8_t ft = raw[(size_t)y * (stride + 1)];
+    const uint8_t* src = &raw[(size_t)y * (stride + 1) + 1];
+    uint8_t* cur = &pixels[(size_t)y * stride];
+    const uint8_t* up = y ? &pixels[(size_t)(y - 1) * stride] : nullptr;
+    for (size_t x = 0; x < stride; x++) {
+      const int a = x >= bpp ? cur[x - bpp] : 0, b = up ? up[x] : 0, c = (x >= bpp && up) ? up[x - bpp] : 0;
+      int v = src[x];
+      switch (ft) {
+        case 0: break;
+        case 1: v += a; break;
+        case 2: v += b; break;
+        case 3: v += (a + b) / 2; break;
+        case 4: v += detail::paeth(a, b, c); break;
+        default: return false;
+      }
+      cur[x] = (uint8_t)v;
+    }
+  }
+  return true;
+}
+
 // imread(GRAYSCALE) -> convertTo(CV_32F): fp32 pixels in 0..255 (ref: :342-348).
 inline bool read_png_gray_f32(const std::string& path, std::vector<float>& pixels, int& width, int& height) {
   std::vector<uint8_t> u8;

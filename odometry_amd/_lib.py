@@ -36,6 +36,13 @@ class TrackerParams(C.Structure):
                 ("smooth_image", C.c_int), ("overlap_depth", C.c_int)]
 
 
+class RgbdFrontendParams(C.Structure):
+    _fields_ = [("depth_rows", C.c_int), ("depth_cols", C.c_int), ("depth_fx", C.c_float), ("depth_fy", C.c_float),
+                ("depth_cx", C.c_float), ("depth_cy", C.c_float), ("depth_scale_in", C.c_float),
+                ("rows", C.c_int), ("cols", C.c_int), ("K", Intrinsics), ("depth_scale_out", C.c_float),
+                ("colour_from_depth", C.c_float * 12), ("colour_channels", C.c_int), ("colour_bgr", C.c_int), ("slots", C.c_int)]
+
+
 _fp = C.POINTER(C.c_float)
 _dp = C.POINTER(C.c_double)
 _u8p = C.POINTER(C.c_uint8)
@@ -191,6 +198,12 @@ SIGNATURES = {
     "odo_tracker_init_rgbd": (C.c_int, [_vp, _vp, _vp, _fp]),
     "odo_tracker_track_rgbd": (C.c_int, [_vp, _vp, _vp, _fp, _fp, _ip, _fp, _ip]),
     "odo_tracker_hint_next_rgbd": (C.c_int, [_vp, _vp, _vp]),
+    "odo_rgbd_frontend_create": (C.c_int, [_vp, C.POINTER(RgbdFrontendParams), C.POINTER(_vp)]),
+    "odo_rgbd_frontend_submit_dev": (C.c_int, [_vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
+    "odo_rgbd_frontend_submit_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_size_t, C.POINTER(_vp), C.POINTER(_vp)]),
+    "odo_rgbd_frontend_wait": (C.c_int, [_vp, _vp]),
+    "odo_rgbd_frontend_stats": (C.c_int, [_vp, _vp, C.POINTER(C.c_long)]),
+    "odo_rgbd_frontend_destroy": (C.c_int, [_vp]),
 }
 
 _lib = None

@@ -864,6 +864,104 @@ class PointMap:
             pass
 
 
+class RgbdFrontend:
+    """Raw sensor frames -> the RGB-D tracker's inputs on the device (odo_rgbd_frontend_*): interleaved 8-bit colour to fp32 grey and
+    the depth imager's uint16 frame registered to the grey camera, on a stream of its own, into a ring of `slots` outputs.
+    tracker_or_ctx: a Context, or a Tracker (host frames then go up on its stream). depth_K = (fx, fy, cx, cy) of the depth imager,
+    K = (f0, cx0, cy0) of the tracker's frame, colour_from_depth: 3x4 or 4x4 [R | t] in metres (None: identity)."""
+
+    STATS = ("n_depth", "n_filled", "dropped_behind", "dropped_range", "dropped_splat", "frame")
+
+    def __init__(self, tracker_or_ctx, depth_size, depth_K, depth_scale_in, size, K, depth_scale_out, colour_from_depth=None,
+                 colour_channels=3, colour_bgr=False, slots=3):
+        self.lib = L.load()
+        self._owner = tracker_or_ctx   # keeps the stream's owner alive as long as the front end
+        ctx = tracker_or_ctx._ctx if isinstance(tracker_or_ctx, Tracker) else tracker_or_ctx.h
+        self._ctx = ctx
+        E = np.eye(4) if colour_from_depth is None else np.asarray(colour_from_depth, np.float64)
+        p = L.RgbdFrontendParams()
+        p.depth_rows, p.depth_cols = depth_size
+        p.depth_fx, p.depth_fy, p.depth_cx, p.depth_cy = depth_K
+        p.depth_scale_in = depth_scale_in
+        p.rows, p.cols = size
+        p.K = L.Intrinsics(*K)
+        p.depth_scale_out = depth_scale_out
+        for i, v in enumerate(E[:3, :4].reshape(-1)):
+            p.colour_from_depth[i] = v
+        p.colour_channels, p.colour_bgr, p.slots = colour_channels, int(bool(colour_bgr)), slots
+        self.params = p
+        self.rows, self.cols, self.channels = p.rows, p.cols, colour_channels
+        self.depth_rows, self.depth_cols = p.depth_rows, p.depth_cols
+        self._bufs = []
+        h = C.c_void_p()
+        L.check(self.lib.odo_rgbd_frontend_create(ctx, C.byref(p), C.byref(h)), "odo_rgbd_frontend_create")
+        self.h = h
+
+    def upload(self, arr):
+        """A raw frame (uint8 colour or uint16 depth) into a device buffer owned by the front end (`close` frees it): a handle for
+        `submit`."""
+        arr = np.ascontiguousarray(arr)
+        p = C.c_void_p()
+        L.check(self.lib.odo_dev_alloc(self._ctx, arr.nbytes, C.byref(p)), "odo_dev_alloc")
+        L.check(self.lib.odo_dev_upload(self._ctx, p, arr.ctypes.data_as(C.c_void_p), arr.nbytes), "odo_dev_upload")
+        self._bufs.append(p)
+        return p
+
+    def submit(self, colour, depth):
+        """Enqueues one frame and returns (gray_dev, depth_dev) of its slot at once. numpy arrays (rows x cols x channels uint8 and
+        depth_rows x depth_cols uint16; any row pitch) take the host path, device handles the device path."""
+        g, d = C.c_void_p(), C.c_void_p()
+        if isinstance(colour, np.ndarray) != isinstance(depth, np.ndarray):
+            raise TypeError("colour and depth must both be numpy arrays or both be device handles")
+        if isinstance(colour, np.ndarray):
+            if colour.dtype != np.uint8 or colour.shape != (self.rows, self.cols, self.channels):
+                raise ValueError(f"colour frame {colour.dtype} {colour.shape}")
+            if depth.dtype != np.uint16 or depth.shape != (self.depth_rows, self.depth_cols):
+                raise ValueError(f"depth frame {depth.dtype} {depth.shape}")
+            if colour.strides[1:] != (self.channels, 1) or colour.strides[0] < self.cols * self.channels:
+                colour = np.ascontiguousarray(colour)
+            if depth.strides[1] != 2 or depth.strides[0] < 2 * self.depth_cols:
+                depth = np.ascontiguousarray(depth)
+            L.check(self.lib.odo_rgbd_frontend_submit_host(self.h, colour.ctypes.data_as(C.c_void_p), colour.strides[0],
+                                                           depth.ctypes.data_as(C.c_void_p), depth.strides[0], C.byref(g), C.byref(d)),
+                    "odo_rgbd_frontend_submit_host")
+        else:
+            L.check(self.lib.odo_rgbd_frontend_submit_dev(self.h, colour, depth, C.byref(g), C.byref(d)),
+                    "odo_rgbd_frontend_submit_dev")
+        return g, d
+
+    def wait(self, gray_dev):
+        L.check(self.lib.odo_rgbd_frontend_wait(self.h, gray_dev), "odo_rgbd_frontend_wait")
+
+    def stats(self, gray_dev):
+        o = (C.c_long * 6)()
+        L.check(self.lib.odo_rgbd_frontend_stats(self.h, gray_dev, o), "odo_rgbd_frontend_stats")
+        return dict(zip(self.STATS, list(o)))
+
+    def download(self, gray_dev, depth_dev):
+        """A slot's results on the host (waits for the slot): (rows x cols float32, rows x cols uint16)."""
+        self.wait(gray_dev)
+        gray = np.empty((self.rows, self.cols), np.float32)
+        dep = np.empty((self.rows, self.cols), np.uint16)
+        L.check(self.lib.odo_dev_download(self._ctx, gray.ctypes.data_as(C.c_void_p), gray_dev, gray.nbytes), "odo_dev_download")
+        L.check(self.lib.odo_dev_download(self._ctx, dep.ctypes.data_as(C.c_void_p), depth_dev, dep.nbytes), "odo_dev_download")
+        return gray, dep
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.odo_rgbd_frontend_destroy(self.h)
+            self.h = None
+            for p in self._bufs:
+                self.lib.odo_dev_free(self._ctx, p)
+            self._bufs = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def write_ply(path, xyzi):
     """(N, 4) float32 x, y, z, intensity -> binary little-endian PLY with float x y z and uchar red green blue (grey)."""
     xyzi = np.asarray(xyzi, np.float32).reshape(-1, 4)

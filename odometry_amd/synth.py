@@ -261,6 +261,71 @@ def make_rgbd_sequence(n_frames, seed=0, drive="natural", fwd_range=(0.1, 0.2), 
     return out
 
 
+def rig_extrinsic(t_m=(0.0, 0.0, 0.0), rot_rad=(0.0, 0.0, 0.0)):
+    """colour_from_depth as a 4x4: P_c = R P_d + t with R = Rz Ry Rx of the angles about x, y, z (radians), t in metres."""
+    rx, ry, rz = rot_rad
+    cx_, sx_, cy_, sy_, cz_, sz_ = np.cos(rx), np.sin(rx), np.cos(ry), np.sin(ry), np.cos(rz), np.sin(rz)
+    Rx = np.array([[1, 0, 0], [0, cx_, -sx_], [0, sx_, cx_]])
+    Ry = np.array([[cy_, 0, sy_], [0, 1, 0], [-sy_, 0, cy_]])
+    Rz = np.array([[cz_, -sz_, 0], [sz_, cz_, 0], [0, 0, 1]])
+    E = np.eye(4)
+    E[:3, :3] = Rz @ Ry @ Rx
+    E[:3, 3] = t_m
+    return E
+
+
+def colour_from_gray(gray, channels=3, bgr=False, tint_seed=None):
+    """An interleaved uint8 colour frame of a grey image (values 0..255): the grey value in R, G and B, or — with tint_seed — a
+    seeded gain and offset per channel so that the three differ; a fourth channel holds seeded noise (a front end ignores it)."""
+    g = np.asarray(gray, np.float64)
+    if tint_seed is None:
+        rgb = [g, g, g]
+        rng = np.random.default_rng(0x7157)
+    else:
+        rng = np.random.default_rng(0x7157 + tint_seed)
+        rgb = [g * rng.uniform(0.6, 1.2) + rng.uniform(-20.0, 20.0) for _ in range(3)]
+    planes = [np.clip(np.rint(c), 0, 255).astype(np.uint8) for c in (rgb[::-1] if bgr else rgb)]
+    if channels == 4:
+        planes.append(rng.integers(0, 256, g.shape).astype(np.uint8))
+    return np.ascontiguousarray(np.stack(planes, -1))
+
+
+def make_raw_rgbd_sequence(n_frames, seed=0, drive="natural", fwd_range=(0.1, 0.2), depth_scale=1000.0, max_range=30.0, rows=TUM_ROWS,
+                           cols=TUM_COLS, f=TUM_F, cx=TUM_CX, cy=TUM_CY, depth_size=None, depth_f=None, depth_c=None,
+                           colour_from_depth=None, channels=3, bgr=False, tint_seed=None, frames=None):
+    """What an RGB-D sensor delivers along the drive of make_rgbd_sequence: per frame an interleaved uint8 colour frame rendered at
+    the colour camera (rows x cols, f, cx, cy; colour_from_gray of the grey rendering) and a uint16 depth frame rendered AT THE DEPTH
+    IMAGER: depth_size = (rows, cols), focal length depth_f, principal point depth_c = (cx, cy) (default: the image centre), pose
+    T @ colour_from_depth (4x4, P_c = R P_d + t; default identity). Defaults make the depth imager the colour camera.
+    frames: the frame indices to render (default all). Returns dict(colour=[...], raw_depth=[...], gray=[fp32 grey renderings],
+    depth_gt=[the registered ground truth: sensor_depth of the colour camera's Z], frames=[indices], poses (all n_frames), K,
+    depth_K=(fx, fy, cx, cy), colour_from_depth, depth_scale, max_range)."""
+    scene = drive_scene(drive, seed)
+    kw = {k: v for k, v in DRIVES[drive].items() if k not in ("scene", "fwd_range")}
+    poses = trajectory(n_frames, seed, fwd_range=fwd_range, **kw)
+    drows, dcols = (rows, cols) if depth_size is None else depth_size
+    fd = f if depth_f is None else depth_f
+    if depth_c is not None:
+        cxd, cyd = depth_c
+    elif depth_size is None and depth_f is None:
+        cxd, cyd = cx, cy
+    else:
+        cxd, cyd = (dcols - 1) / 2.0, (drows - 1) / 2.0
+    E = np.eye(4) if colour_from_depth is None else np.asarray(colour_from_depth, np.float64)
+    idx = list(range(n_frames)) if frames is None else list(frames)
+    out = dict(colour=[], raw_depth=[], gray=[], depth_gt=[], frames=idx, poses=poses, K=dict(f0=f, cx0=cx, cy0=cy),
+               depth_K=(fd, fd, cxd, cyd), colour_from_depth=E, depth_scale=depth_scale, max_range=max_range)
+    for k in idx:
+        T = poses[k]
+        img, Z = scene.render(T, rows, cols, f, cx, cy, 0.0)
+        _, Zd = scene.render(T @ E, drows, dcols, fd, cxd, cyd, 0.0)
+        out["gray"].append(img)
+        out["colour"].append(colour_from_gray(img, channels, bgr, tint_seed))
+        out["raw_depth"].append(sensor_depth(Zd, depth_scale, max_range))
+        out["depth_gt"].append(sensor_depth(Z, depth_scale, max_range))
+    return out
+
+
 def semi_dense_inverse_depth(Z, left, grad_th=12.0, max_depth=30.0, stride_keep=1.0, seed=0):
     """Ground-truth inverse-depth map restricted to high-gradient pixels (semi-dense), 0 elsewhere —
     a stand-in for DepthEstimator output when a test needs a known-good keyframe depth."""
