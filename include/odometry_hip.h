@@ -32,6 +32,7 @@ typedef struct odo_depth odo_depth;
 typedef struct odo_tracker odo_tracker;
 typedef struct odo_camera odo_camera;
 typedef struct odo_map odo_map;
+typedef struct odo_volume odo_volume;
 typedef struct odo_rgbd_frontend odo_rgbd_frontend;
 
 /* Level-0 pinhole intrinsics (fy = fx). NULL wherever accepted = the KITTI-00 constants the reference
@@ -507,6 +508,76 @@ int odo_tracker_arm_stats(const odo_tracker* t, long* started, long* returned);
 odo_lm* odo_tracker_lm(odo_tracker* t);
 odo_depth* odo_tracker_depth(odo_tracker* t);   /* its depth estimator (odo_depth_persistent_stats, odo_depth_report) */
 odo_ctx* odo_tracker_ctx(odo_tracker* t);
+
+/* ---- TSDF volume: tracked RGB-D depth frames fused into dense geometry ------------------------------------------------------------
+ * The second half of the reference's plan (README: an RGB-D odometry that "outputs camera trajectories as well as reconstructed 3D
+ * geometry"): every depth frame with a known pose is integrated into a dense truncated signed distance grid (Curless & Levoy;
+ * KinectFusion's map), and the surface is read back as an oriented point cloud. All floating point is fp32, one rounding per
+ * operation; a voxel's new value depends on its old value and the frame only (no atomics, no order dependence inside a frame;
+ * frames are ordered by the stream), and a voxel that is skipped is neither loaded nor stored.
+ * Grid. nx x ny x nz voxels, x fastest; voxel (i, j, k) has centre o + ((float)i + 0.5f) * vs per axis. A voxel is 4 bytes: int16 q
+ * (truncated signed distance * 32767) and uint16 w (weight; 0 = never observed); cleared: q = 0, w = 0.
+ * Integration of one frame (raw uint16 rows x cols in the grey camera's grid, camera-to-world abs_pose). The host forms the
+ * world-to-camera M = [R^T | -R^T t] in fp64 from the fp32 entries (the translation as -((r0 t0 + r1 t1) + r2 t2)) and rounds each
+ * entry to fp32 once; R is taken as given. Per voxel centre (X, Y, Z):
+ *   1. xc = ((m0 X + m4 Y) + m8 Z) + m12, yc and zc likewise; skipped unless zc > 0;
+ *   2. u = f0 * (xc / zc) + cx0, v = f0 * (yc / zc) + cy0; xi = floorf(u + 0.5f), yi = floorf(v + 0.5f), compared AS FLOATS against
+ *      [0, cols), [0, rows) (NaN: skipped);
+ *   3. r = raw[yi * cols + xi]; skipped if r == 0; D = (float)r / depth_scale; skipped if D > max_depth;
+ *   4. sdf = D - zc (projective, along the optical axis); skipped if sdf < -mu; s = fminf(1.0f, sdf / mu) * 32767.0f;
+ *   5. W = (float)w; F = ((float)q * W + s) / (W + 1.0f); q' = (int16)rintf(F) (ties to even); w' = min(w + 1, max_weight).
+ * Counters of an integration: voxels updated, and of those the ones with |sdf| <= mu.
+ * Extraction. For every voxel a in raster order (k, then j, then i) and its +x, +y, +z neighbour b, in that order, inside the grid:
+ * the edge carries a point iff w_a > 0 && w_b > 0 && (q_a > 0) != (q_b > 0). alpha = (float)q_a / ((float)q_a - (float)q_b); the
+ * point is a's centre with alpha * vs added on the edge's axis. Normal: with Q = (float)q and "usable" = inside the grid and
+ * w > 0, g(v) per axis = Q[v + e] - Q[v - e] if both neighbours are usable, else 2.0f * (Q[v + e] - Q[v]) if only v + e is, else
+ * 2.0f * (Q[v] - Q[v - e]) if only v - e is; a voxel with an axis on which neither is usable has no gradient. If a and b both have
+ * one: n = g_a + alpha * (g_b - g_a) per component, len = sqrtf((nx nx + ny ny) + nz nz), n / len if len > 0; otherwise
+ * (0, 0, 0). The normal points from the surface into observed free space. Output per point: {x, y, z, 0} and
+ * {nx, ny, nz, (float)min(w_a, w_b)}, in (voxel, axis) order; points beyond `capacity` are counted as dropped, not written. The
+ * result is a pure function of the volume. */
+typedef struct {
+  int nx, ny, nz;          /* every dimension >= 2, nx * ny * nz <= 2^30; device memory: 4 B per voxel */
+  float voxel_size;        /* metres, finite > 0 */
+  float origin[3];         /* world position of the grid's minimum corner */
+  float mu;                /* truncation distance, metres, > 0 */
+  float max_depth;         /* metres: readings beyond it are ignored */
+  int max_weight;          /* 1 .. 65535 */
+  int rows, cols;          /* the depth frames' size */
+  odo_intrinsics K;        /* of the grey camera (the depth frames are registered to it) */
+  float depth_scale;       /* raw units per metre */
+} odo_volume_params;
+/* Validates everything before it touches the device. */
+int odo_volume_create(odo_ctx* ctx, const odo_volume_params* p, odo_volume** out);
+/* One depth frame (device-resident) into the volume. Asynchronous on ctx's stream (two launches, no host synchronisation), ordered
+ * after every earlier operation on the volume; the depth buffer must stay unchanged until odo_volume_sync or the next call that
+ * waits. A pose with a non-finite entry (the abs_pose of a failed Solve) is refused: -1, nothing enqueued, counters unchanged. */
+int odo_volume_integrate_dev(odo_volume* v, const uint16_t* depth_dev, const float abs_pose_colmajor[16]);
+/* Waits for every pending integration. */
+int odo_volume_sync(odo_volume* v);
+/* The surface as oriented points (waits; three launches into buffers the volume owns, then the copy): xyz0 / nrmw receive 4 floats
+ * per point, at most `capacity` (0 .. 2^28) points; *n_points = points written, *n_dropped (may be NULL) = points beyond capacity.
+ * The volume is not modified. */
+int odo_volume_extract(odo_volume* v, long capacity, float* xyz0, float* nrmw, long* n_points, long* n_dropped);
+/* The whole grid to the host, nx * ny * nz values each in raster order (either may be NULL); waits for pending integrations. */
+int odo_volume_download(odo_volume* v, int16_t* q, uint16_t* w);
+/* out: frames integrated since create / clear, voxels updated by the last integration, of those the ones in the band
+ * (|sdf| <= mu), voxel updates since create / clear (waits for pending integrations). */
+int odo_volume_stats(odo_volume* v, long out[4]);
+/* Empty volume: every voxel and every counter start from nothing. */
+int odo_volume_clear(odo_volume* v);
+/* -1 while the volume is attached to a tracker. */
+int odo_volume_destroy(odo_volume* v);
+/* RGB-D trackers only (a stereo tracker is refused, nothing enqueued); same device and frame size; one tracker per volume; NULL
+ * detaches after the pending integrations complete. With a volume attached, odo_tracker_init_rgbd and every odo_tracker_track_rgbd
+ * whose Solve succeeded (solve_status == 0; a failed Solve leaves abs_pose NaN) enqueue one integration of that frame's depth with
+ * the returned abs_pose on the volume's own stream, without a host wait on the frame's path; a frame whose depth JOB failed (return
+ * -1) still has a good pose and a good sensor frame and is integrated. Poses, masks and keyframe decisions are bit-identical to
+ * those without a volume. Because the integration reads the caller's depth buffer, a tracker with a volume attached asks for one
+ * thing more: a tracked frame's depth buffer must stay unchanged until the next odo_tracker_track_rgbd / init_rgbd / quiesce /
+ * destroy has returned — those calls make sure, through an event a whole frame old, that the previous frame's integration has
+ * finished before they return (the front end's ring of four slots used two frames ahead satisfies this). */
+int odo_tracker_attach_volume(odo_tracker* t, odo_volume* v);
 
 /* ---- RGB-D front end: raw sensor frames -> the RGB-D tracker's inputs ----------------------------------------------------------
  * A sensor delivers interleaved 8-bit colour and a uint16 depth frame in the DEPTH imager's pixel grid (its own intrinsics, often

@@ -43,6 +43,12 @@ class RgbdFrontendParams(C.Structure):
                 ("colour_from_depth", C.c_float * 12), ("colour_channels", C.c_int), ("colour_bgr", C.c_int), ("slots", C.c_int)]
 
 
+class VolumeParams(C.Structure):
+    _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("voxel_size", C.c_float), ("origin", C.c_float * 3),
+                ("mu", C.c_float), ("max_depth", C.c_float), ("max_weight", C.c_int), ("rows", C.c_int), ("cols", C.c_int),
+                ("K", Intrinsics), ("depth_scale", C.c_float)]
+
+
 _fp = C.POINTER(C.c_float)
 _dp = C.POINTER(C.c_double)
 _u8p = C.POINTER(C.c_uint8)
@@ -204,6 +210,15 @@ SIGNATURES = {
     "odo_rgbd_frontend_wait": (C.c_int, [_vp, _vp]),
     "odo_rgbd_frontend_stats": (C.c_int, [_vp, _vp, C.POINTER(C.c_long)]),
     "odo_rgbd_frontend_destroy": (C.c_int, [_vp]),
+    "odo_volume_create": (C.c_int, [_vp, C.POINTER(VolumeParams), C.POINTER(_vp)]),
+    "odo_volume_integrate_dev": (C.c_int, [_vp, _vp, _fp]),
+    "odo_volume_sync": (C.c_int, [_vp]),
+    "odo_volume_extract": (C.c_int, [_vp, C.c_long, _fp, _fp, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "odo_volume_download": (C.c_int, [_vp, C.POINTER(C.c_int16), C.POINTER(C.c_uint16)]),
+    "odo_volume_stats": (C.c_int, [_vp, C.POINTER(C.c_long)]),
+    "odo_volume_clear": (C.c_int, [_vp]),
+    "odo_volume_destroy": (C.c_int, [_vp]),
+    "odo_tracker_attach_volume": (C.c_int, [_vp, _vp]),
 }
 
 _lib = None

@@ -763,6 +763,16 @@ class RgbdTracker(Tracker):
             raise L.OdoError("odo_tracker_track_rgbd: " + L.last_error())
         return self._nk.value
 
+    def attach_volume(self, v):
+        """Every frame with a good pose from now on is integrated into TsdfVolume `v` (None detaches; pending integrations complete
+        first). A tracked frame's depth buffer must then stay unchanged until the next track / init / close has returned."""
+        L.check(self.lib.odo_tracker_attach_volume(self.h, v.h if v is not None else None), "odo_tracker_attach_volume")
+        if getattr(self, "_vol", None) is not None and self._vol is not v:
+            self._vol._tracker = None
+        self._vol = v
+        if v is not None:
+            v._tracker = self
+
     def depth_report(self):
         """The last frame's depth statistics (odo_depth_report): iters, cost, n_selected, n_matched, n_valid."""
         d = C.c_void_p(self.lib.odo_tracker_depth(self.h))
@@ -855,6 +865,101 @@ class PointMap:
             if self._tracker is not None and getattr(self._tracker, "h", None):
                 self._tracker.attach_map(None)
             self.lib.odo_map_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TsdfVolume:
+    """Device-resident truncated signed distance volume (odo_volume_*): depth frames with known poses fused into a dense grid, the
+    surface read back as oriented points. ctx_or_tracker: a Context, or a Tracker whose stream standalone integrations then use
+    (attach with RgbdTracker.attach_volume). dims = (nx, ny, nz), origin = the grid's minimum corner (world, metres), size = (rows,
+    cols) of the depth frames, K = (f0, cx0, cy0), depth_scale: raw units per metre."""
+
+    STATS = ("frames", "updated", "in_band", "cumulative")
+
+    def __init__(self, ctx_or_tracker, dims, voxel_size, origin, mu, max_depth, max_weight, size, K, depth_scale):
+        self.lib = L.load()
+        self._owner = ctx_or_tracker   # keeps the stream's owner alive as long as the volume
+        ctx = ctx_or_tracker._ctx if isinstance(ctx_or_tracker, Tracker) else ctx_or_tracker.h
+        self._ctx = ctx
+        self._tracker = None
+        p = L.VolumeParams()
+        p.nx, p.ny, p.nz = dims
+        p.voxel_size = voxel_size
+        for i in range(3):
+            p.origin[i] = origin[i]
+        p.mu, p.max_depth, p.max_weight = mu, max_depth, max_weight
+        p.rows, p.cols = size
+        p.K = L.Intrinsics(*K)
+        p.depth_scale = depth_scale
+        self.params = p
+        self.dims = (p.nx, p.ny, p.nz)
+        self.rows, self.cols = p.rows, p.cols
+        h = C.c_void_p()
+        L.check(self.lib.odo_volume_create(ctx, C.byref(p), C.byref(h)), "odo_volume_create")
+        self.h = h
+
+    def integrate(self, depth, abs_pose):
+        """One depth frame: a uint16 numpy array (uploaded into a temporary buffer) or a device handle; abs_pose = 4x4 camera-to-world."""
+        pose = _colmajor(abs_pose)
+        if isinstance(depth, np.ndarray):
+            depth = np.ascontiguousarray(depth, np.uint16)
+            assert depth.shape == (self.rows, self.cols), depth.shape
+            p = C.c_void_p()
+            L.check(self.lib.odo_dev_alloc(self._ctx, depth.nbytes, C.byref(p)), "odo_dev_alloc")
+            try:
+                L.check(self.lib.odo_dev_upload(self._ctx, p, depth.ctypes.data_as(C.c_void_p), depth.nbytes), "odo_dev_upload")
+                L.check(self.lib.odo_volume_integrate_dev(self.h, p, _fp(pose)), "odo_volume_integrate_dev")
+            finally:   # odo_dev_free waits for the context's stream: the integration has read the frame
+                self.lib.odo_dev_free(self._ctx, p)
+        else:
+            L.check(self.lib.odo_volume_integrate_dev(self.h, depth, _fp(pose)), "odo_volume_integrate_dev")
+
+    def sync(self):
+        L.check(self.lib.odo_volume_sync(self.h), "odo_volume_sync")
+
+    def extract(self, capacity=1 << 20, with_dropped=False):
+        """The surface: (n, 4) float32 x, y, z, 0 and (n, 4) float32 nx, ny, nz, weight, at most `capacity` points (with_dropped:
+        also the number of points beyond it)."""
+        xyz0 = np.zeros((max(capacity, 1), 4), np.float32)
+        nrmw = np.zeros((max(capacity, 1), 4), np.float32)
+        n, d = C.c_long(0), C.c_long(0)
+        L.check(self.lib.odo_volume_extract(self.h, capacity, _fp(xyz0), _fp(nrmw), C.byref(n), C.byref(d)), "odo_volume_extract")
+        out = xyz0[:n.value].copy(), nrmw[:n.value].copy()
+        return out + (d.value,) if with_dropped else out
+
+    def grid(self):
+        """(q int16, w uint16), each of shape (nz, ny, nx)."""
+        nx, ny, nz = self.dims
+        q = np.zeros((nz, ny, nx), np.int16)
+        w = np.zeros((nz, ny, nx), np.uint16)
+        L.check(self.lib.odo_volume_download(self.h, q.ctypes.data_as(C.POINTER(C.c_int16)), w.ctypes.data_as(C.POINTER(C.c_uint16))),
+                "odo_volume_download")
+        return q, w
+
+    def stats(self):
+        o = (C.c_long * 4)()
+        L.check(self.lib.odo_volume_stats(self.h, o), "odo_volume_stats")
+        return dict(zip(self.STATS, list(o)))
+
+    def clear(self):
+        L.check(self.lib.odo_volume_clear(self.h), "odo_volume_clear")
+
+    def save_ply(self, path, capacity=1 << 22):
+        """Binary little-endian PLY of the extracted surface: float x y z nx ny nz."""
+        xyz0, nrmw = self.extract(capacity)
+        write_ply_normals(path, xyz0, nrmw)
+
+    def close(self):
+        if getattr(self, "h", None):
+            if self._tracker is not None and getattr(self._tracker, "h", None):
+                self._tracker.attach_volume(None)
+            self.lib.odo_volume_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -971,6 +1076,22 @@ def write_ply(path, xyzi):
     rec["r"] = rec["g"] = rec["b"] = grey
     header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
               "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n") % len(xyzi)
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(rec.tobytes())
+
+
+def write_ply_normals(path, xyz, normals):
+    """(N, >= 3) positions and (N, >= 3) normals -> binary little-endian PLY with float x y z nx ny nz."""
+    xyz = np.asarray(xyz, np.float32)
+    normals = np.asarray(normals, np.float32)
+    assert xyz.ndim == 2 and normals.shape[0] == xyz.shape[0] and xyz.shape[1] >= 3 and normals.shape[1] >= 3
+    rec = np.zeros(len(xyz), np.dtype([(k, "<f4") for k in ("x", "y", "z", "nx", "ny", "nz")]))
+    for c, k in enumerate(("x", "y", "z")):
+        rec[k] = xyz[:, c]
+        rec["n" + k] = normals[:, c]
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % len(xyz)) + "".join(
+        "property float %s\n" % k for k in ("x", "y", "z", "nx", "ny", "nz")) + "end_header\n"
     with open(path, "wb") as f:
         f.write(header.encode("ascii"))
         f.write(rec.tobytes())

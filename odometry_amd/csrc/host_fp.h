@@ -134,4 +134,17 @@ inline uint64_t image(const void* src, size_t src_pitch, size_t row_bytes, int r
   return h;
 }
 
+// World-to-camera M = [R^T | -R^T t] of a camera-to-world pose A = [R | t] (column-major fp32 in and out; the TSDF volume's
+// projection, volume_api.hip.h): formed in fp64 from the fp32 entries — the translation as -((r0 t0 + r1 t1) + r2 t2), in that
+// order — and each entry rounded to fp32 once. R is taken as given (no check that it is orthonormal).
+inline void invert_rigid(const float* A, float* M) {
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) M[c * 4 + r] = A[r * 4 + c];
+    const double d = ((double)A[r * 4 + 0] * (double)A[12] + (double)A[r * 4 + 1] * (double)A[13]) + (double)A[r * 4 + 2] * (double)A[14];
+    M[12 + r] = (float)-d;
+    M[r * 4 + 3] = 0.0f;
+  }
+  M[15] = 1.0f;
+}
+
 }  // namespace hostfp

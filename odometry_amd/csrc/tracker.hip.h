@@ -81,6 +81,12 @@ struct odo_tracker {
   hipEvent_t ev_map[2];        // the map's stream: the insertion that read d_val[slot] is complete
   std::atomic<int> map_wait[2];  // 1: the slot's next depth job waits for ev_map[slot] first (read by the helper thread)
   int map_kf_slot;             // ev_map[map_kf_slot] covers the last insertion that read kf_img / kf_dep; -1: none pending
+  // TSDF volume (odo_tracker_attach_volume, RGB-D trackers): every frame with a good pose is integrated on the volume's own stream.
+  // The integration reads the CALLER's depth frame, so a call returns only once the integration enqueued a call earlier is complete
+  // (ev_vol alternates; tracker_vol_integrate).
+  odo_volume* vol;             // nullptr: no volume, and nothing below is used
+  hipEvent_t ev_vol[2];        // the volume's stream: behind integration n, slot n & 1
+  long vol_n;                  // integrations enqueued since the last drain
   // Depth source (odo_tracker_create_rgbd): 1 = a uint16 sensor depth frame per frame instead of the right image. Only the stream-B
   // job's front differs (rgbd_job_begin / rgbd_job_stats); everything behind it is the stereo tracker's.
   int rgbd;
@@ -138,6 +144,11 @@ extern "C" int odo_tracker_destroy(odo_tracker* t) {
     t->map->attached = nullptr;
   }
   for (hipEvent_t e : t->ev_map) if (e) (void)hipEventDestroy(e);
+  if (t->vol) {
+    (void)volume_sync(t->vol);
+    t->vol->attached = nullptr;
+  }
+  for (hipEvent_t e : t->ev_vol) if (e) (void)hipEventDestroy(e);
   odo_ctx_destroy(t->ctx_c);
   odo_ctx_destroy(t->ctx_b);
   odo_ctx_destroy(t->ctx_a);
@@ -173,6 +184,7 @@ static int tracker_create(int device, const odo_tracker_params* p, int rgbd, flo
   t->dbg_pre_us = t->dbg_spin_us = t->dbg_chain_us = t->dbg_verdict_us = t->dbg_post_us = t->dbg_relaunch_us = 0.0; t->dbg_n = t->dbg_relaunch_n = 0;
   t->depth_ahead = getenv("ODO_NO_DEPTH_AHEAD") ? 0 : 1;
   t->map = nullptr; t->ev_map[0] = t->ev_map[1] = nullptr; t->map_wait[0].store(0); t->map_wait[1].store(0); t->map_kf_slot = -1;
+  t->vol = nullptr; t->ev_vol[0] = t->ev_vol[1] = nullptr; t->vol_n = 0;
   t->rgbd = rgbd; t->depth_scale = depth_scale; t->max_depth_step = max_depth_step;
   t->p = *p;
   float eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
@@ -436,6 +448,10 @@ extern "C" int odo_tracker_quiesce(odo_tracker* t) {
     if (map_sync(t->map)) return -1;
     t->map_wait[0].store(0); t->map_wait[1].store(0); t->map_kf_slot = -1;
   }
+  if (t->vol) {                            // pending integrations (they read caller-owned depth frames)
+    if (volume_sync(t->vol)) return -1;
+    t->vol_n = 0;
+  }
   t->lm->job.active = 0;                   // a Solve started early for an announced frame is dropped
   t->lm->chained.active = 0;
   t->prefetched = t->hint_next = t->hint_next_right = nullptr;  // announcements are void
@@ -490,6 +506,53 @@ extern "C" int odo_tracker_attach_map(odo_tracker* t, odo_map* m) {
   return 0;
 }
 
+// This frame's depth into the attached volume, on the volume's stream (which waits for nothing: the caller's depth frame is complete,
+// the tracker's own depth job has been reading it). Enqueued behind the next Solve's launches, so nothing lands in front of the
+// pose-LM chain. abs_pose NULL or not finite (a failed Solve): nothing is integrated. Then the integration enqueued a call ago must be
+// complete — an event a whole frame old, so the host almost never waits — because its depth frame is the caller's again once this
+// call returns.
+static int tracker_vol_integrate(odo_tracker* t, const uint16_t* depth, const float* abs_pose) {
+  odo_volume* v = t->vol;
+  long before = t->vol_n - 1;   // the last integration of an earlier call
+  if (abs_pose && pose_finite(abs_pose)) {
+    if (volume_integrate(v, depth, abs_pose, v->own)) return -1;
+    HIP_OK(hipEventRecord(t->ev_vol[t->vol_n & 1], v->own));
+    t->vol_n++;
+  }
+  if (before >= 0) {
+    const hipEvent_t e = t->ev_vol[before & 1];
+    if (hipEventQuery(e) != hipSuccess) {
+      (void)hipGetLastError();   // (hipErrorNotReady is not an error)
+      HIP_OK(hipEventSynchronize(e));
+    }
+  }
+  return 0;
+}
+
+extern "C" int odo_tracker_attach_volume(odo_tracker* t, odo_volume* v) {
+  if (!t) return fail("NULL tracker");
+  if (v == t->vol) return 0;
+  if (v && !t->rgbd) return fail("odo_tracker_attach_volume: a stereo tracker has no sensor depth frames to integrate (RGB-D trackers only)");
+  if (v && v->attached) return fail("odo_tracker_attach_volume: the volume is attached to another tracker");
+  if (v && (v->device != t->ctx_a->device || v->p.rows != t->p.rows || v->p.cols != t->p.cols))
+    return fail("odo_tracker_attach_volume: the volume (device %d, %dx%d) does not match the tracker (device %d, %dx%d)", v->device,
+                v->p.rows, v->p.cols, t->ctx_a->device, t->p.rows, t->p.cols);
+  HIP_OK(hipSetDevice(t->ctx_a->device));
+  if (t->vol) {   // detach: the integrations already enqueued complete first
+    if (volume_sync(t->vol)) return -1;
+    t->vol_n = 0;
+    t->vol->attached = nullptr;
+    t->vol = nullptr;
+  }
+  if (v) {
+    for (hipEvent_t& e : t->ev_vol) if (!e) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    v->attached = t;
+    t->vol = v;
+    t->vol_n = 0;
+  }
+  return 0;
+}
+
 // Frame 0 of a sequence, either depth source (right: the right image, or an RGB-D tracker's depth frame).
 static int tracker_init(odo_tracker* t, const float* left, const float* right, const float abs_pose0[16]) {
   HIP_OK(hipSetDevice(t->ctx_a->device));
@@ -518,6 +581,7 @@ static int tracker_init(odo_tracker* t, const float* left, const float* right, c
   t->last_valid = j->stats.n_valid;
   t->last_depth_iters = j->stats.iters;
   if (t->map && tracker_map_insert(t, j->slot, abs_pose0)) return -1;
+  if (t->vol && tracker_vol_integrate(t, (const uint16_t*)right, abs_pose0)) return -1;
   return 0;
 }
 
@@ -780,7 +844,12 @@ static int tracker_track(odo_tracker* t, const float* left, const float* right, 
   t->out_slot = jk->slot;
   t->last_depth_iters = jk->stats.iters;
   t->last_valid = jk->stats.n_valid;
-  if (jk->rc) { t->lm->job.active = 0; return fail("    depth failed! (%s)", jk->msg); }   // :230-232
+  if (jk->rc) {                                                                        // :230-232
+    t->lm->job.active = 0;
+    // (the pose and the sensor frame of a frame whose depth JOB failed — too few valid selected points — are good: it is integrated)
+    if (t->vol) (void)tracker_vol_integrate(t, (const uint16_t*)right, st == 0 ? cur : nullptr);
+    return fail("    depth failed! (%s)", jk->msg);
+  }
   int new_kf = 0;
   if (promote) {
     if (t->map && tracker_map_fence(t)) return -1;
@@ -794,6 +863,7 @@ static int tracker_track(odo_tracker* t, const float* left, const float* right, 
   if (!reset_done) odo_lm_reset(t->lm, T, 0.01f);                                      // :261 / :268 (both branches)
   if (early && promote && start_next_solve() < 0) return -1;   // against the new keyframe, as soon as its lists are adopted
   if (new_kf && t->map && tracker_map_insert(t, jk->slot, cur)) return -1;   // (behind the next Solve's launches)
+  if (t->vol && tracker_vol_integrate(t, (const uint16_t*)right, st == 0 ? cur : nullptr)) return -1;
   if (pose_to_keyframe) memcpy(pose_to_keyframe, T, sizeof(T));
   if (abs_pose) memcpy(abs_pose, cur, sizeof(cur));
   if (is_new_keyframe) *is_new_keyframe = new_kf;

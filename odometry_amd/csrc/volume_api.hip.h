@@ -1,0 +1,253 @@
+// volume_api.hip.h — the TSDF volume (odo_volume_*): the host object over the kernels of volume_kernels.hip. Every tracked RGB-D
+// depth frame is fused into a dense truncated signed distance grid (Curless & Levoy), and the surface is read back out of it as an
+// oriented point cloud: the "reconstructed 3D geometry" of the reference's README. Included by odometry_hip.hip before
+// tracker.hip.h (an RGB-D tracker integrates its frames).
+#pragma once
+#include "volume.hip.h"
+
+struct odo_volume {
+  odo_ctx* ctx;                 // standalone integrations (odo_volume_integrate_dev) run on its stream
+  int device;
+  hipStream_t own;              // the attached tracker's integrations, extractions, downloads, clears
+  hipEvent_t ev_last;           // behind the last operation that changed the volume, on `last`
+  hipStream_t last;             // stream of that operation, nullptr: none yet
+  odo_volume_params p;
+  long n_vox;
+  uint32_t* d_vox;
+  unsigned long long* d_blk;    // integrate: the blocks' rows
+  VolCounters* d_ctr;
+  // extraction (sized on first use, the point buffers grown on demand)
+  unsigned long long *d_wave, *d_off;
+  int* d_cnt;
+  float4 *d_xyz0, *d_nrmw;
+  long ext_capacity;
+  long n_frames;                // integrations since create / clear
+  odo_tracker* attached;
+};
+
+static int volume_release(odo_volume* v) {
+  void* ps[] = {v->d_vox, v->d_blk, v->d_ctr, v->d_wave, v->d_off, v->d_cnt, v->d_xyz0, v->d_nrmw};
+  for (void* p : ps) if (p) (void)hipFree(p);
+  if (v->ev_last) (void)hipEventDestroy(v->ev_last);
+  if (v->own) (void)hipStreamDestroy(v->own);
+  delete v;
+  return 0;
+}
+
+// Everything that changed the volume so far is ordered before the next operation on stream s.
+static int volume_order_on(odo_volume* v, hipStream_t s) {
+  if (v->last && v->last != s) HIP_OK(hipStreamWaitEvent(s, v->ev_last, 0));
+  return 0;
+}
+static int volume_mark(odo_volume* v, hipStream_t s) {
+  HIP_OK(hipEventRecord(v->ev_last, s));
+  v->last = s;
+  return 0;
+}
+// Waits for every pending integration; afterwards the volume's own stream is idle and ordered after them.
+static int volume_sync(odo_volume* v) {
+  HIP_OK(hipSetDevice(v->device));
+  if (volume_order_on(v, v->own)) return -1;
+  HIP_OK(hipStreamSynchronize(v->own));
+  return 0;
+}
+static int volume_reset(odo_volume* v) {
+  if (volume_order_on(v, v->own)) return -1;
+  HIP_OK(hipMemsetAsync(v->d_vox, 0, sizeof(uint32_t) * (size_t)v->n_vox, v->own));
+  HIP_OK(hipMemsetAsync(v->d_ctr, 0, sizeof(VolCounters), v->own));
+  v->n_frames = 0;
+  return volume_mark(v, v->own);
+}
+
+extern "C" int odo_volume_create(odo_ctx* ctx, const odo_volume_params* p, odo_volume** out) {
+  if (!ctx || !p || !out) return fail("odo_volume_create: NULL arg");
+  *out = nullptr;
+  if (p->nx < 2 || p->ny < 2 || p->nz < 2 || (long long)p->nx * p->ny * p->nz > (1LL << 30))
+    return fail("odo_volume_create: bad grid %dx%dx%d (every dimension >= 2, at most 2^30 voxels)", p->nx, p->ny, p->nz);
+  if (!(std::isfinite(p->voxel_size) && p->voxel_size > 0.0f)) return fail("odo_volume_create: voxel_size must be finite and > 0");
+  for (int c = 0; c < 3; c++) if (!std::isfinite(p->origin[c])) return fail("odo_volume_create: origin must be finite");
+  if (!(std::isfinite(p->mu) && p->mu > 0.0f)) return fail("odo_volume_create: mu must be finite and > 0");
+  if (!(p->max_depth > 0.0f)) return fail("odo_volume_create: max_depth must be > 0");
+  if (p->max_weight < 1 || p->max_weight > 65535) return fail("odo_volume_create: max_weight %d out of range (1 .. 65535)", p->max_weight);
+  if (p->rows < 1 || p->cols < 1 || (long long)p->rows * p->cols > (1 << 28)) return fail("odo_volume_create: bad size %dx%d", p->rows, p->cols);
+  if (!(std::isfinite(p->depth_scale) && p->depth_scale > 0.0f)) return fail("odo_volume_create: depth_scale must be finite and > 0");
+  if (!(std::isfinite(p->K.f0) && std::isfinite(p->K.cx0) && std::isfinite(p->K.cy0))) return fail("odo_volume_create: K must be finite");
+  HIP_OK(hipSetDevice(ctx->device));
+  odo_volume* v = new (std::nothrow) odo_volume();
+  if (!v) return fail("out of memory");
+  v->ctx = ctx; v->device = ctx->device; v->own = nullptr; v->ev_last = nullptr; v->last = nullptr;
+  v->p = *p;
+  v->n_vox = (long)p->nx * p->ny * p->nz;
+  v->d_vox = nullptr; v->d_blk = nullptr; v->d_ctr = nullptr;
+  v->d_wave = v->d_off = nullptr; v->d_cnt = nullptr; v->d_xyz0 = v->d_nrmw = nullptr; v->ext_capacity = 0;
+  v->n_frames = 0; v->attached = nullptr;
+  bool ok = hipStreamCreateWithFlags(&v->own, hipStreamNonBlocking) == hipSuccess &&
+            hipEventCreateWithFlags(&v->ev_last, hipEventDisableTiming) == hipSuccess &&
+            hipMalloc((void**)&v->d_vox, sizeof(uint32_t) * (size_t)v->n_vox) == hipSuccess &&
+            hipMalloc((void**)&v->d_blk, sizeof(unsigned long long) * 2 * kVolMaxBlocks) == hipSuccess &&
+            hipMalloc((void**)&v->d_ctr, sizeof(VolCounters)) == hipSuccess;
+  ok = ok && volume_reset(v) == 0 && volume_sync(v) == 0;
+  if (!ok) {
+    (void)hipGetLastError();
+    const long n = v->n_vox;
+    volume_release(v);
+    return fail("odo_volume_create: device allocation failed (%ld voxels)", n);
+  }
+  *out = v;
+  return 0;
+}
+
+static VolGrid volume_grid(const odo_volume* v) {
+  VolGrid g;
+  g.vox = v->d_vox; g.nx = v->p.nx; g.ny = v->p.ny; g.nz = v->p.nz;
+  g.vs = v->p.voxel_size; g.ox = v->p.origin[0]; g.oy = v->p.origin[1]; g.oz = v->p.origin[2];
+  return g;
+}
+
+static bool pose_finite(const float* A) {
+  for (int i = 0; i < 16; i++) if (!std::isfinite(A[i])) return false;
+  return true;
+}
+
+// One integration on stream s (async). depth: rows x cols uint16 on the device; A: camera-to-world, finite.
+static int volume_integrate(odo_volume* v, const uint16_t* depth, const float* A, hipStream_t s) {
+  HIP_OK(hipSetDevice(v->device));
+  if (volume_order_on(v, s)) return -1;
+  float M[16];
+  hostfp::invert_rigid(A, M);
+  VolIntegrateArgs a;
+  memset(&a, 0, sizeof(a));
+  a.g = volume_grid(v);
+  a.raw = depth; a.rows = v->p.rows; a.cols = v->p.cols;
+  a.f0 = v->p.K.f0; a.cx0 = v->p.K.cx0; a.cy0 = v->p.K.cy0;
+  a.depth_scale = v->p.depth_scale; a.max_depth = v->p.max_depth; a.mu = v->p.mu; a.max_weight = v->p.max_weight;
+  a.m0 = M[0]; a.m1 = M[1]; a.m2 = M[2]; a.m4 = M[4]; a.m5 = M[5]; a.m6 = M[6];
+  a.m8 = M[8]; a.m9 = M[9]; a.m10 = M[10]; a.m12 = M[12]; a.m13 = M[13]; a.m14 = M[14];
+  a.zc_far = (v->p.max_depth + v->p.mu) * 1.001f;
+  a.tiles_x = (v->p.nx + kVolTileX - 1) / kVolTileX;
+  a.tiles_y = (v->p.ny + kVolTileY - 1) / kVolTileY;
+  a.tiles = (long long)a.tiles_x * a.tiles_y * v->p.nz;
+  a.nblk = (int)std::min<long long>(a.tiles, kVolMaxBlocks);
+  a.step_x = a.nblk % a.tiles_x; a.step_y = (a.nblk / a.tiles_x) % a.tiles_y; a.step_k = (a.nblk / a.tiles_x) / a.tiles_y;
+  a.blk = v->d_blk; a.ctr = v->d_ctr;
+  launch_volume_integrate(a, s);
+  HIP_OK(hipGetLastError());
+  v->n_frames++;
+  return volume_mark(v, s);
+}
+
+extern "C" int odo_volume_integrate_dev(odo_volume* v, const uint16_t* depth_dev, const float abs_pose_colmajor[16]) {
+  if (!v || !depth_dev || !abs_pose_colmajor) return fail("odo_volume_integrate_dev: NULL arg");
+  if (!pose_finite(abs_pose_colmajor)) return fail("odo_volume_integrate_dev: the pose has a non-finite entry (a frame whose Solve failed?)");
+  return volume_integrate(v, depth_dev, abs_pose_colmajor, v->ctx->stream);
+}
+
+extern "C" int odo_volume_sync(odo_volume* v) {
+  if (!v) return fail("NULL volume");
+  return volume_sync(v);
+}
+
+static int volume_counters(odo_volume* v, VolCounters* c) {
+  if (volume_sync(v)) return -1;
+  HIP_OK(hipMemcpyAsync(c, v->d_ctr, sizeof(VolCounters), hipMemcpyDeviceToHost, v->own));
+  HIP_OK(hipStreamSynchronize(v->own));
+  return 0;
+}
+
+extern "C" int odo_volume_stats(odo_volume* v, long out[4]) {
+  if (!v || !out) return fail("odo_volume_stats: NULL arg");
+  VolCounters c;
+  if (volume_counters(v, &c)) return -1;
+  out[0] = v->n_frames; out[1] = (long)c.updated; out[2] = (long)c.band; out[3] = (long)c.cumulative;
+  return 0;
+}
+
+// The three launches into the volume's own buffers; *n_points = points written, *n_dropped = points beyond capacity.
+static int volume_extract_dev(odo_volume* v, long capacity, long* n_points, long* n_dropped) {
+  if (volume_sync(v)) return -1;
+  const int nblk = (int)((v->n_vox + kVolExtBlock - 1) / kVolExtBlock);
+  if (!v->d_cnt) {
+    bool ok = hipMalloc((void**)&v->d_wave, sizeof(unsigned long long) * 3 * (kVolExtBlock / 64) * (size_t)nblk) == hipSuccess &&
+              hipMalloc((void**)&v->d_off, sizeof(unsigned long long) * (size_t)nblk) == hipSuccess &&
+              hipMalloc((void**)&v->d_cnt, sizeof(int) * (size_t)nblk) == hipSuccess;
+    if (!ok) {
+      (void)hipGetLastError();
+      if (v->d_wave) (void)hipFree(v->d_wave);
+      if (v->d_off) (void)hipFree(v->d_off);
+      if (v->d_cnt) (void)hipFree(v->d_cnt);
+      v->d_wave = v->d_off = nullptr; v->d_cnt = nullptr;
+      return fail("odo_volume_extract: device allocation failed (%d blocks)", nblk);
+    }
+  }
+  if (capacity > v->ext_capacity) {
+    if (v->d_xyz0) (void)hipFree(v->d_xyz0);
+    if (v->d_nrmw) (void)hipFree(v->d_nrmw);
+    v->d_xyz0 = v->d_nrmw = nullptr; v->ext_capacity = 0;
+    if (hipMalloc((void**)&v->d_xyz0, sizeof(float4) * (size_t)capacity) != hipSuccess ||
+        hipMalloc((void**)&v->d_nrmw, sizeof(float4) * (size_t)capacity) != hipSuccess) {
+      (void)hipGetLastError();
+      if (v->d_xyz0) (void)hipFree(v->d_xyz0);
+      v->d_xyz0 = v->d_nrmw = nullptr;
+      return fail("odo_volume_extract: device allocation failed (%ld points)", capacity);
+    }
+    v->ext_capacity = capacity;
+  }
+  VolExtractArgs a;
+  memset(&a, 0, sizeof(a));
+  a.g = volume_grid(v);
+  a.n = (int)v->n_vox; a.nblk = nblk; a.capacity = capacity;
+  a.wave_mask = v->d_wave; a.blk = v->d_cnt; a.blk_off = v->d_off; a.ctr = v->d_ctr;
+  a.xyz0 = v->d_xyz0; a.nrmw = v->d_nrmw;
+  launch_volume_extract(a, v->own);
+  HIP_OK(hipGetLastError());
+  VolCounters c;
+  HIP_OK(hipMemcpyAsync(&c, v->d_ctr, sizeof(VolCounters), hipMemcpyDeviceToHost, v->own));
+  HIP_OK(hipStreamSynchronize(v->own));
+  *n_points = (long)c.ext_written;
+  *n_dropped = (long)(c.ext_total - c.ext_written);
+  return 0;
+}
+
+extern "C" int odo_volume_extract(odo_volume* v, long capacity, float* xyz0, float* nrmw, long* n_points, long* n_dropped) {
+  if (!v || !n_points || capacity < 0 || capacity > (1L << 28) || (capacity > 0 && (!xyz0 || !nrmw)))
+    return fail("odo_volume_extract: bad arg (capacity 0 .. 2^28, buffers for `capacity` points)");
+  long n = 0, d = 0;
+  if (volume_extract_dev(v, capacity, &n, &d)) return -1;
+  if (n > 0) {
+    HIP_OK(hipMemcpyAsync(xyz0, v->d_xyz0, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, v->own));
+    HIP_OK(hipMemcpyAsync(nrmw, v->d_nrmw, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, v->own));
+    HIP_OK(hipStreamSynchronize(v->own));
+  }
+  *n_points = n;
+  if (n_dropped) *n_dropped = d;
+  return 0;
+}
+
+extern "C" int odo_volume_download(odo_volume* v, int16_t* q, uint16_t* w) {
+  if (!v || (!q && !w)) return fail("odo_volume_download: NULL arg");
+  if (volume_sync(v)) return -1;
+  std::vector<uint32_t> host;
+  try { host.resize((size_t)v->n_vox); } catch (...) { return fail("out of memory"); }
+  HIP_OK(hipMemcpyAsync(host.data(), v->d_vox, sizeof(uint32_t) * (size_t)v->n_vox, hipMemcpyDeviceToHost, v->own));
+  HIP_OK(hipStreamSynchronize(v->own));
+  for (long i = 0; i < v->n_vox; i++) {
+    if (q) q[i] = (int16_t)(host[(size_t)i] & 0xffffu);
+    if (w) w[i] = (uint16_t)(host[(size_t)i] >> 16);
+  }
+  return 0;
+}
+
+extern "C" int odo_volume_clear(odo_volume* v) {
+  if (!v) return fail("NULL volume");
+  HIP_OK(hipSetDevice(v->device));
+  return volume_reset(v);
+}
+
+extern "C" int odo_volume_destroy(odo_volume* v) {
+  if (!v) return 0;
+  if (v->attached) return fail("odo_volume_destroy: the volume is attached to a tracker (odo_tracker_attach_volume(t, NULL) first)");
+  (void)hipSetDevice(v->device);
+  if (v->last && v->last != v->own) (void)hipEventSynchronize(v->ev_last);
+  (void)hipStreamSynchronize(v->own);
+  return volume_release(v);
+}

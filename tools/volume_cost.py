@@ -1,0 +1,190 @@
+"""What the TSDF volume (odo_volume_*) costs.
+
+  kernels   the workload for a kernel trace: the first frames of the TUM-shaped RGB-D drive integrated with their true poses into the
+            pinned grid (240 x 128 x 200 voxels of 4 cm, 24.6 MB: resident in the Infinity Cache) and into a 512 x 256 x 512 grid of
+            the same voxel size (268 MB: it is not), each followed by extractions. Run it under the profiler, in a run of its own
+            (no counters in that run), then summarise:
+              rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/volume_cost.py kernels
+              python tools/volume_cost.py summary <dir>
+            It prints one JSON line per grid with the counters the algorithmic bytes are made of; --json FILE keeps them for
+            `summary` (without it `summary` prints the times alone).
+  summary   medians of the volume's kernels per grid out of the trace, with the algorithmic bytes
+              integrate = 8 B per updated voxel (load + store) + 2 B per depth pixel
+              extract   = 4 B per voxel + 32 B per point
+            and their share of the achievable HBM bandwidth (6.3 TB/s).
+  track     tools/rgbd_cost.py's tracked loop over the TUM-shaped drive (next frame announced with its depth frame, back and forth
+            over the drive) with no volume, the pinned grid and the large grid attached, runs interleaved mode by mode: frames/s
+            (median, spread), the tracker's host timing, Solves redone on the step launches and depth jobs redone.
+
+  python tools/volume_cost.py kernels [--frames 10] [--extractions 3] [--json FILE]
+  python tools/volume_cost.py summary DIR [--json FILE]
+  python tools/volume_cost.py track [--runs 3] [--steps 200] [--warmup 20] [--frames 100] [--modes none,pinned,large]
+
+A build without the volume is measured with tools/rgbd_cost.py --modes tum (the same drive and loop as `track`'s mode `none`).
+"""
+import argparse
+import csv
+import glob
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+HBM_BYTES_PER_S = 6.3e12   # achievable, not peak (the micro-architecture notes)
+VS, MU, MAX_DEPTH = 0.04, 0.12, 8.0
+GRIDS = dict(pinned=dict(dims=(240, 128, 200), origin=(-4.8, -3.3, 0.4)),
+             large=dict(dims=(512, 256, 512), origin=(-10.24, -5.86, 0.4)))   # the same corridor, the same voxel size
+
+
+def make_volume(owner, grid, size, K):
+    from odometry_amd import api
+    g = GRIDS[grid]
+    return api.TsdfVolume(owner, g["dims"], VS, g["origin"], MU, MAX_DEPTH, 65535, size, K, 1000.0)
+
+
+def kernels(args):
+    from odometry_amd import api, synth
+    seq = synth.make_rgbd_sequence(args.frames, seed=0)
+    K = (seq["K"]["f0"], seq["K"]["cx0"], seq["K"]["cy0"])
+    ctx = api.Context(0)
+    dev = [ctx.upload(d) for d in seq["depth"]]
+    out = {}
+    for grid in ("pinned", "large"):
+        vol = make_volume(ctx, grid, (synth.TUM_ROWS, synth.TUM_COLS), K)
+        upd = []
+        for d, A in zip(dev, seq["poses"]):
+            vol.integrate(d, A)
+            upd.append(vol.stats()["updated"])
+        t0 = time.perf_counter()
+        for d, A in zip(dev, seq["poses"]):    # once more without a host wait between the frames (weights differ, the work does not)
+            vol.integrate(d, A)
+        vol.sync()
+        host_us = 1e6 * (time.perf_counter() - t0) / len(dev)
+        n = 0
+        for _ in range(args.extractions):
+            n = len(vol.extract(1 << 21)[0])
+        nx, ny, nz = GRIDS[grid]["dims"]
+        out[grid] = dict(voxels=nx * ny * nz, updated_per_frame=int(np.median(upd)), points=n, pixels=synth.TUM_ROWS * synth.TUM_COLS,
+                         integrate_host_us_back_to_back=round(host_us, 1))
+        print(json.dumps(dict(grid=grid, **out[grid])), flush=True)
+        vol.close()
+    for d in dev:
+        ctx.free(d)
+    ctx.close()
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(out, f)
+
+
+def summary(args):
+    work = json.load(open(args.json)) if args.json else None
+    rows = []
+    for f in glob.glob(os.path.join(args.dir, "**", "*kernel_trace.csv"), recursive=True):
+        with open(f) as fh:
+            rows += list(csv.DictReader(fh))
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    per = {}
+    for r in rows:
+        name = r["Kernel_Name"].split("(")[0].replace("odo::", "")
+        if name.startswith("volume_"):
+            per.setdefault(name, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    for name in sorted(per):
+        half = len(per[name]) // 2    # `kernels` does the same launches on the pinned grid first, then on the large one
+        for which, d in (("pinned", per[name][:half]), ("large", per[name][half:])):
+            d = np.array(d)
+            line = f"{name:26s} {which:7s} n={len(d):3d}  median {np.median(d):8.2f} us  min {d.min():8.2f}  max {d.max():8.2f}"
+            if work and which in work:
+                w = work[which]
+                b = None
+                if name == "volume_integrate_kernel":
+                    b = 8 * w["updated_per_frame"] + 2 * w["pixels"]
+                elif name == "volume_count_kernel":
+                    b = 4 * w["voxels"]
+                elif name == "volume_scatter_kernel":
+                    b = 32 * w["points"]
+                if b is not None:
+                    bw = b / (np.median(d) * 1e-6)
+                    line += f"  algorithmic {b / 1e6:8.2f} MB -> {bw / 1e12:5.2f} TB/s = {100 * bw / HBM_BYTES_PER_S:5.1f} % of 6.3 TB/s"
+            print(line)
+
+
+def track(args):
+    import rgbd_cost
+    from odometry_amd import api
+    modes = args.modes.split(",")
+    d = rgbd_cost.render(args.frames, "tum")
+    trk = api.RgbdTracker(0, depth_scale=1000.0, max_depth_step=0.05, rows=d["rows"], cols=d["cols"], K=d["K"])
+    dev = [(trk.upload_frame(g), trk.upload_depth(r)) for g, r in zip(d["gray"], d["depth"])]
+    vols = {m: make_volume(trk, m, (d["rows"], d["cols"]), d["K"]) for m in modes if m != "none"}
+    T = np.zeros(16, np.float32)
+    A = np.zeros(16, np.float32)
+    res = {m: [] for m in modes}
+    n = len(dev)
+    last = args.warmup + args.steps
+    order = [k % (2 * n - 2) for k in range(last + 1)]
+    order = [k if k < n else 2 * n - 2 - k for k in order]   # back and forth over the drive, as bench.py does
+    for run in range(args.runs):
+        for mode in modes:
+            vol = vols.get(mode)
+            if vol is not None:
+                vol.clear()
+            trk.attach_volume(vol)
+            _, djob0 = trk.depth_persistent_stats()
+            _, redo0 = trk.persistent_stats()
+            trk.init(*dev[order[0]])
+            kf = 0
+            t0 = None
+            for k in range(1, last + 1):
+                if k == args.warmup + 1:
+                    trk._sync()
+                    trk.timing()   # (resets the averages)
+                    t0 = time.perf_counter()
+                if k + 1 <= last and k + 1 != args.warmup + 1:
+                    trk.hint_next(*dev[order[k + 1]])
+                kf += trk.track_into(*dev[order[k]], T, A)
+            trk._sync()            # (waits for the pending integrations as well)
+            fps = args.steps / (time.perf_counter() - t0)
+            tm = trk.timing()
+            _, djob1 = trk.depth_persistent_stats()
+            groups, redo1 = trk.persistent_stats()
+            res[mode].append(fps)
+            st = vol.stats() if vol is not None else {}
+            print(json.dumps(dict(run=run, mode=mode, fps=round(fps, 1), keyframes=kf + 1, lm_persistent_groups=groups,
+                                  solves_redone=redo1 - redo0, depth_jobs_redone=djob1 - djob0, frames_integrated=st.get("frames"),
+                                  updated_last=st.get("updated"), **{k_: round(v, 1) for k_, v in tm.items()})), flush=True)
+    trk.attach_volume(None)
+    print(json.dumps(dict(summary=True, **{m: dict(median_fps=round(float(np.median(res[m])), 1),
+                                                   spread=[round(min(res[m]), 1), round(max(res[m]), 1)]) for m in modes})))
+    for v in vols.values():
+        v.close()
+    trk.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    k = sub.add_parser("kernels")
+    k.add_argument("--frames", type=int, default=10)
+    k.add_argument("--extractions", type=int, default=3)
+    k.add_argument("--json", default=None)
+    s = sub.add_parser("summary")
+    s.add_argument("dir")
+    s.add_argument("--json", default=None)
+    t = sub.add_parser("track")
+    t.add_argument("--runs", type=int, default=3)
+    t.add_argument("--steps", type=int, default=200)
+    t.add_argument("--warmup", type=int, default=20)
+    t.add_argument("--frames", type=int, default=100)
+    t.add_argument("--modes", default="none,pinned,large")
+    args = ap.parse_args()
+    dict(kernels=kernels, summary=summary, track=track)[args.cmd](args)
+
+
+if __name__ == "__main__":
+    main()
