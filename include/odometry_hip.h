@@ -384,6 +384,12 @@ typedef struct {
 } odo_tracker_params;
 
 int odo_tracker_default_params(odo_tracker_params* p); /* the runner's constants for KITTI 1241x376 */
+/* Frame sizes: with any_size = 0 only 376 x 1241 (the reference's own check, ref: src/depth_estimate.cpp:46-49). With any_size = 1
+ * every rows x cols whose point-selection tile — the 16 x 32 grid inside `boundary` = b — holds
+ *   1 <= ((cols - 2b) / 32) * ((rows - 2b) / 16) <= 4096 pixels (integer divisions), and rows, cols <= 65535.
+ * Odd sizes are supported (every pyramid level halves, rounding down); 3, 4 and 5 levels are tested. The rule is checked when a
+ * frame arrives — odo_tracker_init returns -1 with the message, before anything is launched — not at create; the batched tracker
+ * checks it at create. tests/shape_cases.py lists the sizes the whole trackers are tested at. */
 int odo_tracker_create(int device, const odo_tracker_params* p, odo_tracker** out);
 /* Frame 0 (ref: :95-145): ComputeDepth, pyramids, first keyframe with absolute pose abs_pose0. May be called again at
  * any time to start a new sequence on the same tracker: it drains both streams first and the tracker then behaves
@@ -472,7 +478,9 @@ int odo_tracker_attach_map(odo_tracker* t, odo_map* m);
  * policy, attached maps — is the stereo tracker's. */
 /* Uses p's size, levels, lm_*, grad_th, boundary (>= 1: the selection's gradient reads the pixels next to its grid), min_depth /
  * max_depth, K, keyframe weights / threshold, smooth_image and overlap_depth; ignores the stereo and depth-LM fields and implies
- * any_size. depth_scale: raw units per metre (TUM 5000, RealSense 1000), finite and > 0; max_depth_step >= 0 (INFINITY: off). */
+ * any_size. depth_scale: raw units per metre (TUM 5000, RealSense 1000), finite and > 0; max_depth_step >= 0 (INFINITY: off).
+ * Frame sizes: the tile rule of odo_tracker_create, 1 <= ((cols - 2b) / 32) * ((rows - 2b) / 16) <= 4096 and rows, cols <= 65535,
+ * checked by odo_tracker_init_rgbd (-1 with the message, nothing launched), not here. */
 int odo_tracker_create_rgbd(int device, const odo_tracker_params* p, float depth_scale, float max_depth_step, odo_tracker** out);
 /* odo_tracker_init / odo_tracker_track / odo_tracker_hint_next_pair for an RGB-D tracker (same contracts; the depth frame takes
  * the right image's place). odo_tracker_hint_next (grey only), outputs, stats, timing, quiesce and attach_map work on either

@@ -32,8 +32,9 @@ def ref_world(pix, dep, A, cols=COLS, k=K):
 
 
 class RefMap:
-    def __init__(self, capacity, voxel):
+    def __init__(self, capacity, voxel, cols=COLS, k=K):
         self.cap, self.voxel = capacity, np.float32(voxel)
+        self.cols, self.k = cols, k
         self.xyzi, self.kp = np.zeros((0, 4), np.float32), np.zeros((0, 2), np.int32)
         self.keys = np.zeros(0, np.int64)
         self.st = dict(size=0, insertions=0, candidates=0, dropped_voxel=0, dropped_range=0, dropped_capacity=0)
@@ -44,7 +45,7 @@ class RefMap:
         if self.st["size"] >= self.cap:
             return
         pix = ref_candidates(val, dep)
-        w = ref_world(pix, dep, A)
+        w = ref_world(pix, dep, A, self.cols, self.k)
         self.st["candidates"] += len(pix)
         keep = np.ones(len(pix), bool)
         if self.voxel > 0:
