@@ -138,9 +138,12 @@ def test_second_rig_matches_the_model_bit_for_bit(ctx):
 
 def test_non_finite_poses_and_bad_arguments_are_refused(ctx, seq):
     from odometry_amd import _lib as L
-    p = params(seq, dims=(32, 16, 24))
+    p = params(seq, dims=(32, 16, 24), vs=0.08, origin=(-1.28, 0.9, 3.6))   # the ground, 3.6 to 5.5 m ahead, crosses it
     vol = _volume(ctx, p)
     vol.integrate(seq["depth"][0], seq["poses"][0])
+    q, w, upd, band = integrate_model(*empty_grid(p), seq["depth"][0], seq["poses"][0], p)
+    _grid_equal(vol, q, w, "32 x 16 x 24 after one integration")
+    assert vol.stats() == dict(frames=1, updated=upd, in_band=band, cumulative=upd) and upd > 0
     before = vol.stats(), vol.grid()
     d = ctx.upload(seq["depth"][1])
     for bad in (np.nan, np.inf, -np.inf):
@@ -152,6 +155,7 @@ def test_non_finite_poses_and_bad_arguments_are_refused(ctx, seq):
     assert vol.lib.odo_volume_extract(vol.h, 10, None, None, None, None) == -1
     after = vol.stats(), vol.grid()
     assert before[0] == after[0] and np.array_equal(before[1][0], after[1][0]) and np.array_equal(before[1][1], after[1][1])
+    _grid_equal(vol, q, w, "32 x 16 x 24 after the refused calls")
     ctx.free(d)
     vol.close()
 
