@@ -60,6 +60,15 @@ __device__ __forceinline__ float div_shared(float a, float b, float y) {
   const float r1 = __builtin_fmaf(-b, q1, a);
   return __builtin_fmaf(r1, y, q1);
 }
+// div_shared for a numerator that may be ZERO (x == cx, y == cy: X, Y and the Jacobian entries that carry them as a factor). With
+// a == -0 and b > 0 the residual steps above end on +0 (r0 = fma(-b, -0, -0) = +0, then +0 + -0 = +0) where a / b is -0: the sign of a
+// zero quotient is one of the special values the compiler's sequence leaves to v_div_fixup. The same instruction restores it here
+// (one VALU operation; for every other guarded operand it returns its first argument unchanged). No sum ever depended on that sign
+// (a zero entry of J adds +-0 to accumulators that start at +0); the per-pixel values now equal the plain division's bit for bit
+// (tests/test_gpu_devmath.py, call sites with x == cx).
+__device__ __forceinline__ float div_shared_z(float a, float b, float y) {
+  return __builtin_amdgcn_div_fixupf(div_shared(a, b, y), b, a);
+}
 __device__ __forceinline__ float recip_shared(float b, float y) {  // 1.0f / b: q0 = 1 * y is exact
   const float r0 = __builtin_fmaf(-b, y, 1.0f);
   const float q1 = __builtin_fmaf(r0, y, y);
@@ -91,8 +100,8 @@ static inline int dense_fast_ok(double fl, float cx, float cy, int rows, int col
 __device__ __forceinline__ void point_xyz_shared(int x, int y, float inv_depth, const LevelK& k, float flf, float yfl, float* X,
                                                  float* Y, float* Z) {
   const float z = recip_shared(inv_depth, rcp_refined(inv_depth));   // :198
-  *X = div_shared(z * ((float)x - k.cx), flf, yfl);                  // h:35
-  *Y = div_shared(z * ((float)y - k.cy), flf, yfl);                  // h:36
+  *X = div_shared_z(z * ((float)x - k.cx), flf, yfl);                  // h:35
+  *Y = div_shared_z(z * ((float)y - k.cy), flf, yfl);                  // h:36
   *Z = z;
 }
 __device__ __forceinline__ void point_jacobian_shared(PointK* p, const LevelK& k, float flf) {
@@ -102,11 +111,11 @@ __device__ __forceinline__ void point_jacobian_shared(PointK* p, const LevelK& k
   const float xy = p->X * p->Y, xx = p->X * p->X, yy = p->Y * p->Y, zz = z * z;
   const float yzz = rcp_refined(zz);
   p->fx_z = fx_z;
-  p->jw02 = div_shared(-fx_z * p->X, z, yz);                         // :232
-  p->jw03 = div_shared(-fx_z * xy, z, yz);
+  p->jw02 = div_shared_z(-fx_z * p->X, z, yz);                         // :232
+  p->jw03 = div_shared_z(-fx_z * xy, z, yz);
   p->jw04 = (float)(k.fl * (1.0 + (double)div_shared(xx, zz, yzz)));
   p->jw05 = -fx_z * p->Y;
-  p->jw12 = div_shared(-fx_z * p->Y, z, yz);                         // :233
+  p->jw12 = div_shared_z(-fx_z * p->Y, z, yz);                         // :233
   p->jw13 = (float)(-k.fl * (1.0 + (double)div_shared(yy, zz, yzz)));
   p->jw14 = -p->jw03;
   p->jw15 = fx_z * p->X;

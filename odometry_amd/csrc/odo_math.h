@@ -245,6 +245,12 @@ ODO_HD void accumulate_row(double acc[ODO_NACC], float r, float w, const float J
 
 // ---------------------------------------------------------------------------------------------
 // sin/cos of an fp32 argument, evaluated in fp64 and rounded once (deterministic on host and device).
+// Domain. Accuracy: the two-constant reduction is exact while k * pio2_1 is (k below 2^20), and the results are within 1 ulp of
+// the true value — measured: correctly rounded — for |x| < 2^23; above that the error grows (32 ulp in [2^23, 2^24), wrong digits
+// from 1e12). Determinism: (long long)kf is defined while |kf| < 2^63, i.e. |x| < 1.45e19; an fp32 argument can just exceed that
+// (|x| up to 3.4e38), and there the conversion — hence the quadrant — may differ between host and device. The callers' arguments
+// are rotation angles of one LM step, far inside both; tests/devmath_cases.py holds host, device and oracle to each other bit for
+// bit up to 2^62 and to the true value up to 2^23.
 // ---------------------------------------------------------------------------------------------
 ODO_HD void sincos_f(float xf, float* s_out, float* c_out) {
   const double x = (double)xf;

@@ -2,6 +2,7 @@
 // kernels execute) for the host and steps it serially, so the per-point chain, the SE(3) update and the LM
 // state machine can be checked against the oracle on a machine without a GPU. Never linked into the product.
 #include "../odometry_amd/csrc/odo_math.h"
+#include "devmath_ops.h"
 
 #include <string.h>
 
@@ -119,4 +120,39 @@ int emu_depth_lm_schedule(const float* errs, int n_errs, float lambda0, float pr
   *iters = st.iter;
   return k;
 }
+
+// ---- the device-math harness's operations (tests/devmath_ops.h), case by case on the host: what tests/devmath_harness.hip runs on
+// the device, looped. tests/test_devmath_cpu.py holds these to the oracle, tests/test_gpu_devmath.py holds the device to these.
+void emu_level_k_n(int n, const float* f0, const float* cx0, const float* cy0, const int* level, double* fl, float* cxy) {
+  for (int i = 0; i < n; i++) dm::op_level_k(i, f0, cx0, cy0, level, fl, cxy);
+}
+void emu_sincos_n(int n, const float* x, float* s, float* c) { for (int i = 0; i < n; i++) dm::op_sincos(i, x, s, c); }
+void emu_se3_exp_n(int n, const float* a, float* q, float* M) { for (int i = 0; i < n; i++) dm::op_se3_exp(i, a, q, M); }
+void emu_se3_roundtrip_n(int n, const float* Min, float* q, float* M) { for (int i = 0; i < n; i++) dm::op_se3_roundtrip(i, Min, q, M); }
+void emu_se3_left_update_n(int n, const float* d6, const float* cur, int variant, float* q, float* M) {
+  for (int i = 0; i < n; i++) dm::op_se3_left_update(i, d6, cur, variant, q, M);
+}
+void emu_solve_damped_n(int n, const double* acc, const float* lambda, float* delta) {
+  for (int i = 0; i < n; i++) dm::op_solve_damped(i, acc, lambda, delta);
+}
+void emu_robust_weight_n(int n, const float* r, const int* robust, const float* huber, const float* scale, float* w) {
+  for (int i = 0; i < n; i++) dm::op_robust_weight(i, r, robust, huber, scale, w);
+}
+void emu_apply_step_n(int n, const LmState* in, LmState* out) { for (int i = 0; i < n; i++) dm::op_apply_step(i, in, out); }
+void emu_depth_schedule_n(int n, int cap, const float* errs, const int* n_errs, const float* lambda0, const float* precision,
+                          const int* max_iters, int* rec, int* fin) {
+  for (int i = 0; i < n; i++) dm::op_depth_schedule(i, cap, errs, n_errs, lambda0, precision, max_iters, rec, fin);
+}
+// The LM scripts: lm_begin_solve / lm_begin_level / lm_consume with the level walk of lm_state_machine (devmath_ops.h script_run).
+int emu_lm_script(const dm::LmScript* sc, const double* acc, LmState* out) { return dm::script_run(*sc, acc, out); }
+void emu_lm_script_n(int n, const dm::LmScript* sc, const double* acc, LmState* out, int* count) {
+  for (int i = 0; i < n; i++) count[i] = dm::script_run(sc[i], acc, out);
+}
+void emu_pixels(const dm::PixLevel* L, int mode, int* hit, float* r, float* w, float* J) {
+  for (int y = 4; y < L->rows - 4; y++)
+    for (int x = 4; x < L->cols - 4; x++) dm::op_pixel(*L, mode, x, y, hit, r, w, J);
+}
+int emu_sizeof_lm_state() { return (int)sizeof(LmState); }
+int emu_sizeof_lm_script() { return (int)sizeof(dm::LmScript); }
+int emu_sizeof_pix_level() { return (int)sizeof(dm::PixLevel); }
 }

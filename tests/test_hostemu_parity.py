@@ -19,7 +19,8 @@ def load_emu():
     so = os.path.join(ROOT, "tests", "_build_hostemu.so")
     src = os.path.join(ROOT, "tests", "hostemu.cpp")
     hdr = os.path.join(ROOT, "odometry_amd", "csrc", "odo_math.h")
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
+    ops = os.path.join(ROOT, "tests", "devmath_ops.h")
+    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(src), os.path.getmtime(hdr), os.path.getmtime(ops)):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-shared",
                                "-fPIC", "-o", so, src])
     lib = C.CDLL(so)
