@@ -569,6 +569,40 @@ int odo_volume_sync(odo_volume* v);
 int odo_volume_extract(odo_volume* v, long capacity, float* xyz0, float* nrmw, long* n_points, long* n_dropped);
 /* The whole grid to the host, nx * ny * nz values each in raster order (either may be NULL); waits for pending integrations. */
 int odo_volume_download(odo_volume* v, int16_t* q, uint16_t* w);
+/* The counterpart of odo_volume_download: the whole grid from the host, nx * ny * nz values each in raster order, both arrays
+ * required. Ordered after everything pending and marked like any operation that changes the volume; the frame and update counters
+ * stay as they are. Refused (-1) while the volume is attached to a tracker. Restores a saved reconstruction. */
+int odo_volume_upload(odo_volume* v, const int16_t* q, const uint16_t* w);
+/* The surface as a triangle mesh: marching tetrahedra on the Kuhn split of every cell. A table of 6 x 16
+ * entries derived by rule (odometry_amd/csrc/volume_mesh_table.h), no ambiguous cases, watertight by construction.
+ * Lattice. Nodes are voxel centres. Voxel a = (i, j, k) owns up to seven edges (a, e), e = 0 .. 6 with the directions d_e =
+ * (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1), b = a + d_e inside the grid.
+ * Vertex. (a, e) carries one iff w_a > 0 && w_b > 0 && (q_a > 0) != (q_b > 0): the extraction's rule on seven directions.
+ * alpha = Q_a / (Q_a - Q_b) in fp32 (Q = (float)q); position: on every axis with d_e = 1 centre + alpha * vs (the product rounded,
+ * then the sum), the centre itself on the others; normal: g_a + alpha * (g_b - g_a) with the extraction's gradient and
+ * normalisation unchanged, (0, 0, 0) if a gradient is missing. Output xyz0 = {x, y, z, (float)e}, nrmw = {nx, ny, nz,
+ * (float)min(w_a, w_b)}, in (voxel in raster order, e ascending) order; a vertex's index is its position in that order. A vertex
+ * that no triangle references is still emitted. The rows with e < 3, in order, are odo_volume_extract's points bit for bit.
+ * Cell (i, j, k), i < nx - 1, j < ny - 1, k < nz - 1, has the corners c = dx + 2 dy + 4 dz; it is live iff all eight have w > 0, and
+ * only live cells produce triangles. Six tetrahedra per cell, with the corner paths (0,1,3,7) (0,1,5,7) (0,2,3,7) (0,2,6,7)
+ * (0,4,5,7) (0,4,6,7): every edge of every tetrahedron is one of the seven directions from its lower corner, so it has exactly one
+ * owner (voxel, e), whose vertex exists whenever the cell is live and the edge changes sign.
+ * Triangles of a tetrahedron with path positions p0 .. p3, "positive" = q > 0: none for 0 or 4 positive corners; one isolated corner
+ * s (1 or 3 positive), the others r0 < r1 < r2: one triangle on the edges (s,r0) (s,r1) (s,r2); two and two (positives a < b, the
+ * others c < d): the quad V0 = (a,c) V1 = (a,d) V2 = (b,d) V3 = (b,c) as (V0,V1,V2) and (V0,V2,V3). Winding: counter-clockwise seen
+ * from the positive side (observed free space, where the normals point); it depends on the tetrahedron and the sign pattern only
+ * (the sign of a 3 x 3 determinant of corner offsets, part of the table). Each triangle is then rotated so that its smallest vertex
+ * index comes first. Output int32[3] per triangle in (cell in raster order, tetrahedron 0 .. 5, triangle) order.
+ * q == 0 counts as not positive and gives alpha = -+0: coincident vertices and zero-area triangles are kept.
+ * The call waits for pending integrations and modifies neither the volume nor its integration counters. Capacities 0 .. 2^28; with
+ * a capacity of 0 its buffers may be NULL, and (0, 0) returns the totals. counts = {vertices written, vertices beyond
+ * vertex_capacity, triangles written, triangles beyond triangle_capacity}; written items are the first min(total, capacity) in
+ * the order above. Indices are NEVER remapped: a triangle may name a vertex beyond vertex_capacity, and the mesh is complete iff
+ * counts[1] == 0 && counts[3] == 0. A volume with more than 2^31 - 1 vertices is refused once anything is to be written. Arguments
+ * are validated before any device work. Four launches on the volume's stream, no atomics; scratch of 5 B per voxel (31 MB for
+ * 240 x 128 x 200) from the first call until the volume is destroyed. */
+int odo_volume_mesh(odo_volume* v, long vertex_capacity, long triangle_capacity, float* xyz0, float* nrmw, int32_t* tri,
+                    long counts[4]);
 /* out: frames integrated since create / clear, voxels updated by the last integration, of those the ones in the band
  * (|sdf| <= mu), voxel updates since create / clear (waits for pending integrations). */
 int odo_volume_stats(odo_volume* v, long out[4]);

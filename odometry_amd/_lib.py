@@ -215,6 +215,8 @@ SIGNATURES = {
     "odo_volume_sync": (C.c_int, [_vp]),
     "odo_volume_extract": (C.c_int, [_vp, C.c_long, _fp, _fp, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "odo_volume_download": (C.c_int, [_vp, C.POINTER(C.c_int16), C.POINTER(C.c_uint16)]),
+    "odo_volume_upload": (C.c_int, [_vp, C.POINTER(C.c_int16), C.POINTER(C.c_uint16)]),
+    "odo_volume_mesh": (C.c_int, [_vp, C.c_long, C.c_long, _fp, _fp, C.POINTER(C.c_int32), C.POINTER(C.c_long)]),
     "odo_volume_stats": (C.c_int, [_vp, C.POINTER(C.c_long)]),
     "odo_volume_clear": (C.c_int, [_vp]),
     "odo_volume_destroy": (C.c_int, [_vp]),

@@ -942,6 +942,38 @@ class TsdfVolume:
                 "odo_volume_download")
         return q, w
 
+    def upload(self, q, w):
+        """The whole grid from the host: q int16 and w uint16 of shape (nz, ny, nx) (what grid() returns). Refused while attached."""
+        nx, ny, nz = self.dims
+        q = np.ascontiguousarray(q, np.int16)
+        w = np.ascontiguousarray(w, np.uint16)
+        assert q.shape == (nz, ny, nx) and w.shape == (nz, ny, nx), (q.shape, w.shape)
+        L.check(self.lib.odo_volume_upload(self.h, q.ctypes.data_as(C.POINTER(C.c_int16)), w.ctypes.data_as(C.POINTER(C.c_uint16))),
+                "odo_volume_upload")
+
+    def mesh_counts(self):
+        """(vertices, triangles) of the mesh, nothing written."""
+        o = (C.c_long * 4)()
+        L.check(self.lib.odo_volume_mesh(self.h, 0, 0, None, None, None, o), "odo_volume_mesh")
+        return o[1], o[3]
+
+    def mesh(self, vertex_capacity=None, triangle_capacity=None, with_counts=False):
+        """The surface as triangles (marching tetrahedra): (n, 4) float32 x, y, z, e; (n, 4) float32 nx, ny, nz, weight; (m, 3) int32
+        vertex indices, counter-clockwise seen from free space. Without capacities it asks for the totals first and then calls with
+        exact ones; with them the first `capacity` items are returned, indices unchanged (with_counts: also the four counts)."""
+        if vertex_capacity is None or triangle_capacity is None:
+            nv, nt = self.mesh_counts()
+            vertex_capacity = nv if vertex_capacity is None else vertex_capacity
+            triangle_capacity = nt if triangle_capacity is None else triangle_capacity
+        xyz0 = np.zeros((max(vertex_capacity, 1), 4), np.float32)
+        nrmw = np.zeros((max(vertex_capacity, 1), 4), np.float32)
+        tri = np.zeros((max(triangle_capacity, 1), 3), np.int32)
+        o = (C.c_long * 4)()
+        L.check(self.lib.odo_volume_mesh(self.h, vertex_capacity, triangle_capacity, _fp(xyz0), _fp(nrmw),
+                                         tri.ctypes.data_as(C.POINTER(C.c_int32)), o), "odo_volume_mesh")
+        out = xyz0[:o[0]].copy(), nrmw[:o[0]].copy(), tri[:o[2]].copy()
+        return out + (tuple(o),) if with_counts else out
+
     def stats(self):
         o = (C.c_long * 4)()
         L.check(self.lib.odo_volume_stats(self.h, o), "odo_volume_stats")
@@ -954,6 +986,11 @@ class TsdfVolume:
         """Binary little-endian PLY of the extracted surface: float x y z nx ny nz."""
         xyz0, nrmw = self.extract(capacity)
         write_ply_normals(path, xyz0, nrmw)
+
+    def save_mesh_ply(self, path):
+        """Binary little-endian PLY of the mesh: float x y z nx ny nz per vertex, three int indices per face."""
+        xyz0, nrmw, tri = self.mesh()
+        write_ply_mesh(path, xyz0, nrmw, tri)
 
     def close(self):
         if getattr(self, "h", None):
@@ -1095,6 +1132,28 @@ def write_ply_normals(path, xyz, normals):
     with open(path, "wb") as f:
         f.write(header.encode("ascii"))
         f.write(rec.tobytes())
+
+def write_ply_mesh(path, xyz, normals, tri):
+    """(N, >= 3) positions, (N, >= 3) normals and (M, 3) vertex indices -> binary little-endian PLY: vertex float x y z nx ny nz, face
+    list uchar int vertex_indices."""
+    xyz = np.asarray(xyz, np.float32)
+    normals = np.asarray(normals, np.float32)
+    tri = np.asarray(tri, np.int32).reshape(-1, 3)
+    assert xyz.ndim == 2 and normals.shape[0] == xyz.shape[0] and xyz.shape[1] >= 3 and normals.shape[1] >= 3
+    rec = np.zeros(len(xyz), np.dtype([(k, "<f4") for k in ("x", "y", "z", "nx", "ny", "nz")]))
+    for c, k in enumerate(("x", "y", "z")):
+        rec[k] = xyz[:, c]
+        rec["n" + k] = normals[:, c]
+    faces = np.zeros(len(tri), np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+    faces["n"] = 3
+    faces["v"] = tri
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % len(xyz)) + "".join(
+        "property float %s\n" % k for k in ("x", "y", "z", "nx", "ny", "nz")) + (
+        "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % len(tri))
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(rec.tobytes())
+        f.write(faces.tobytes())
 
 
 class TrackerBatch:

@@ -4,6 +4,7 @@
 // tracker.hip.h (an RGB-D tracker integrates its frames).
 #pragma once
 #include "volume.hip.h"
+#include "volume_mesh.hip.h"
 
 struct odo_volume {
   odo_ctx* ctx;                 // standalone integrations (odo_volume_integrate_dev) run on its stream
@@ -21,12 +22,22 @@ struct odo_volume {
   int* d_cnt;
   float4 *d_xyz0, *d_nrmw;
   long ext_capacity;
+  // mesh (the scratch sized on first use: 5 B per voxel; the output buffers grown on demand)
+  uint8_t* d_mesh_mask;
+  uint32_t* d_mesh_base;
+  unsigned* d_mesh_cnt;
+  unsigned long long* d_mesh_off;
+  MeshCounters* d_mesh_ctr;
+  float4 *d_mesh_xyz0, *d_mesh_nrmw;
+  int* d_mesh_tri;
+  long mesh_vertex_capacity, mesh_triangle_capacity;
   long n_frames;                // integrations since create / clear
   odo_tracker* attached;
 };
 
 static int volume_release(odo_volume* v) {
-  void* ps[] = {v->d_vox, v->d_blk, v->d_ctr, v->d_wave, v->d_off, v->d_cnt, v->d_xyz0, v->d_nrmw};
+  void* ps[] = {v->d_vox, v->d_blk, v->d_ctr, v->d_wave, v->d_off, v->d_cnt, v->d_xyz0, v->d_nrmw,
+                v->d_mesh_mask, v->d_mesh_base, v->d_mesh_cnt, v->d_mesh_off, v->d_mesh_ctr, v->d_mesh_xyz0, v->d_mesh_nrmw, v->d_mesh_tri};
   for (void* p : ps) if (p) (void)hipFree(p);
   if (v->ev_last) (void)hipEventDestroy(v->ev_last);
   if (v->own) (void)hipStreamDestroy(v->own);
@@ -80,6 +91,8 @@ extern "C" int odo_volume_create(odo_ctx* ctx, const odo_volume_params* p, odo_v
   v->n_vox = (long)p->nx * p->ny * p->nz;
   v->d_vox = nullptr; v->d_blk = nullptr; v->d_ctr = nullptr;
   v->d_wave = v->d_off = nullptr; v->d_cnt = nullptr; v->d_xyz0 = v->d_nrmw = nullptr; v->ext_capacity = 0;
+  v->d_mesh_mask = nullptr; v->d_mesh_base = nullptr; v->d_mesh_cnt = nullptr; v->d_mesh_off = nullptr; v->d_mesh_ctr = nullptr;
+  v->d_mesh_xyz0 = v->d_mesh_nrmw = nullptr; v->d_mesh_tri = nullptr; v->mesh_vertex_capacity = v->mesh_triangle_capacity = 0;
   v->n_frames = 0; v->attached = nullptr;
   bool ok = hipStreamCreateWithFlags(&v->own, hipStreamNonBlocking) == hipSuccess &&
             hipEventCreateWithFlags(&v->ev_last, hipEventDisableTiming) == hipSuccess &&
@@ -234,6 +247,89 @@ extern "C" int odo_volume_download(odo_volume* v, int16_t* q, uint16_t* w) {
     if (q) q[i] = (int16_t)(host[(size_t)i] & 0xffffu);
     if (w) w[i] = (uint16_t)(host[(size_t)i] >> 16);
   }
+  return 0;
+}
+
+extern "C" int odo_volume_upload(odo_volume* v, const int16_t* q, const uint16_t* w) {
+  if (!v || !q || !w) return fail("odo_volume_upload: NULL arg (both arrays are required)");
+  if (v->attached) return fail("odo_volume_upload: the volume is attached to a tracker (odo_tracker_attach_volume(t, NULL) first)");
+  std::vector<uint32_t> host;
+  try { host.resize((size_t)v->n_vox); } catch (...) { return fail("out of memory"); }
+  for (long i = 0; i < v->n_vox; i++) host[(size_t)i] = ((uint32_t)w[i] << 16) | (uint32_t)(uint16_t)q[i];
+  HIP_OK(hipSetDevice(v->device));
+  if (volume_order_on(v, v->own)) return -1;
+  HIP_OK(hipMemcpyAsync(v->d_vox, host.data(), sizeof(uint32_t) * (size_t)v->n_vox, hipMemcpyHostToDevice, v->own));
+  if (volume_mark(v, v->own)) return -1;
+  HIP_OK(hipStreamSynchronize(v->own));   // (the staging buffer goes with this call)
+  return 0;
+}
+
+// Grows one of the mesh's output buffers to `count` items of `item` bytes; *have = its capacity in items.
+static int volume_mesh_grow(void** p, long* have, long count, size_t item, const char* what) {
+  if (count <= *have) return 0;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr; *have = 0;
+  if (hipMalloc(p, item * (size_t)count) != hipSuccess) {
+    (void)hipGetLastError();
+    *p = nullptr;
+    return fail("odo_volume_mesh: device allocation failed (%ld %s)", count, what);
+  }
+  *have = count;
+  return 0;
+}
+
+extern "C" int odo_volume_mesh(odo_volume* v, long vertex_capacity, long triangle_capacity, float* xyz0, float* nrmw, int32_t* tri,
+                               long counts[4]) {
+  if (!v || !counts || vertex_capacity < 0 || vertex_capacity > (1L << 28) || triangle_capacity < 0 || triangle_capacity > (1L << 28) ||
+      (vertex_capacity > 0 && (!xyz0 || !nrmw)) || (triangle_capacity > 0 && !tri))
+    return fail("odo_volume_mesh: bad arg (capacities 0 .. 2^28, buffers for `vertex_capacity` vertices and `triangle_capacity` triangles)");
+  if (volume_sync(v)) return -1;
+  const int nblk = (int)((v->n_vox + kMeshBlock - 1) / kMeshBlock);
+  if (!v->d_mesh_ctr) {
+    bool ok = hipMalloc((void**)&v->d_mesh_mask, (size_t)v->n_vox) == hipSuccess &&
+              hipMalloc((void**)&v->d_mesh_base, sizeof(uint32_t) * (size_t)v->n_vox) == hipSuccess &&
+              hipMalloc((void**)&v->d_mesh_cnt, sizeof(unsigned) * 2 * (size_t)nblk) == hipSuccess &&
+              hipMalloc((void**)&v->d_mesh_off, sizeof(unsigned long long) * 2 * (size_t)nblk) == hipSuccess &&
+              hipMalloc((void**)&v->d_mesh_ctr, sizeof(MeshCounters)) == hipSuccess;
+    if (!ok) {
+      (void)hipGetLastError();
+      void* ps[] = {v->d_mesh_mask, v->d_mesh_base, v->d_mesh_cnt, v->d_mesh_off, v->d_mesh_ctr};
+      for (void* p : ps) if (p) (void)hipFree(p);
+      v->d_mesh_mask = nullptr; v->d_mesh_base = nullptr; v->d_mesh_cnt = nullptr; v->d_mesh_off = nullptr; v->d_mesh_ctr = nullptr;
+      return fail("odo_volume_mesh: device allocation failed (scratch for %ld voxels)", v->n_vox);
+    }
+  }
+  long have = v->mesh_vertex_capacity;
+  if (volume_mesh_grow((void**)&v->d_mesh_xyz0, &have, vertex_capacity, sizeof(float4), "vertices")) { v->mesh_vertex_capacity = 0; return -1; }
+  have = v->mesh_vertex_capacity;
+  if (volume_mesh_grow((void**)&v->d_mesh_nrmw, &have, vertex_capacity, sizeof(float4), "vertices")) { v->mesh_vertex_capacity = 0; return -1; }
+  v->mesh_vertex_capacity = have;
+  if (volume_mesh_grow((void**)&v->d_mesh_tri, &v->mesh_triangle_capacity, triangle_capacity, 3 * sizeof(int32_t), "triangles")) return -1;
+  VolMeshArgs a;
+  memset(&a, 0, sizeof(a));
+  a.g = volume_grid(v);
+  a.n = (int)v->n_vox; a.nblk = nblk; a.vertex_capacity = vertex_capacity; a.triangle_capacity = triangle_capacity;
+  a.edge_mask = v->d_mesh_mask; a.vertex_base = v->d_mesh_base; a.blk = v->d_mesh_cnt; a.blk_off = v->d_mesh_off; a.ctr = v->d_mesh_ctr;
+  a.xyz0 = v->d_mesh_xyz0; a.nrmw = v->d_mesh_nrmw; a.tri = v->d_mesh_tri;
+  launch_volume_mesh_count(a, v->own);
+  HIP_OK(hipGetLastError());
+  MeshCounters c;
+  HIP_OK(hipMemcpyAsync(&c, v->d_mesh_ctr, sizeof(MeshCounters), hipMemcpyDeviceToHost, v->own));
+  HIP_OK(hipStreamSynchronize(v->own));
+  if (c.v_written > 0 || c.t_written > 0) {
+    if (c.v_total > 0x7fffffffull)
+      return fail("odo_volume_mesh: %llu vertices: an index does not fit an int32 (totals are returned with both capacities 0)", c.v_total);
+    launch_volume_mesh_emit(a, c.t_written > 0, v->own);
+    HIP_OK(hipGetLastError());
+    if (c.v_written > 0) {
+      HIP_OK(hipMemcpyAsync(xyz0, v->d_mesh_xyz0, sizeof(float4) * (size_t)c.v_written, hipMemcpyDeviceToHost, v->own));
+      HIP_OK(hipMemcpyAsync(nrmw, v->d_mesh_nrmw, sizeof(float4) * (size_t)c.v_written, hipMemcpyDeviceToHost, v->own));
+    }
+    if (c.t_written > 0) HIP_OK(hipMemcpyAsync(tri, v->d_mesh_tri, 3 * sizeof(int32_t) * (size_t)c.t_written, hipMemcpyDeviceToHost, v->own));
+    HIP_OK(hipStreamSynchronize(v->own));
+  }
+  counts[0] = (long)c.v_written; counts[1] = (long)(c.v_total - c.v_written);
+  counts[2] = (long)c.t_written; counts[3] = (long)(c.t_total - c.t_written);
   return 0;
 }
 

@@ -2,7 +2,8 @@
 
   kernels   the workload for a kernel trace: the first frames of the TUM-shaped RGB-D drive integrated with their true poses into the
             pinned grid (240 x 128 x 200 voxels of 4 cm, 24.6 MB: resident in the Infinity Cache) and into a 512 x 256 x 512 grid of
-            the same voxel size (268 MB: it is not), each followed by extractions. Run it under the profiler, in a run of its own
+            the same voxel size (268 MB: it is not), each followed by extractions and meshes (api.TsdfVolume.mesh(): count + scan
+            for the totals, then count + scan + vertices + triangles with exact capacities). Run it under the profiler, in a run of its own
             (no counters in that run), then summarise:
               rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/volume_cost.py kernels
               python tools/volume_cost.py summary <dir>
@@ -11,6 +12,8 @@
   summary   medians of the volume's kernels per grid out of the trace, with the algorithmic bytes
               integrate = 8 B per updated voxel (load + store) + 2 B per depth pixel
               extract   = 4 B per voxel + 32 B per point
+              mesh      = count 4 + 1 B per voxel; vertices 1 + 4 B per voxel + 32 B per vertex; triangles 4 B per voxel + 12 B
+                          per triangle
             and their share of the achievable HBM bandwidth (6.3 TB/s).
   track     tools/rgbd_cost.py's tracked loop over the TUM-shaped drive (next frame announced with its depth frame, back and forth
             over the drive) with no volume, the pinned grid and the large grid attached, runs interleaved mode by mode: frames/s
@@ -69,8 +72,13 @@ def kernels(args):
         n = 0
         for _ in range(args.extractions):
             n = len(vol.extract(1 << 21)[0])
+        nv = nt = 0
+        for _ in range(args.extractions):
+            xyz0, _, tri = vol.mesh()
+            nv, nt = len(xyz0), len(tri)
         nx, ny, nz = GRIDS[grid]["dims"]
-        out[grid] = dict(voxels=nx * ny * nz, updated_per_frame=int(np.median(upd)), points=n, pixels=synth.TUM_ROWS * synth.TUM_COLS,
+        out[grid] = dict(voxels=nx * ny * nz, updated_per_frame=int(np.median(upd)), points=n, vertices=nv, triangles=nt,
+                         pixels=synth.TUM_ROWS * synth.TUM_COLS,
                          integrate_host_us_back_to_back=round(host_us, 1))
         print(json.dumps(dict(grid=grid, **out[grid])), flush=True)
         vol.close()
@@ -108,6 +116,12 @@ def summary(args):
                     b = 4 * w["voxels"]
                 elif name == "volume_scatter_kernel":
                     b = 32 * w["points"]
+                elif name == "volume_mesh_count_kernel":
+                    b = 5 * w["voxels"]
+                elif name == "volume_mesh_vertex_kernel" and "vertices" in w:
+                    b = 5 * w["voxels"] + 32 * w["vertices"]
+                elif name == "volume_mesh_triangle_kernel" and "triangles" in w:
+                    b = 4 * w["voxels"] + 12 * w["triangles"]
                 if b is not None:
                     bw = b / (np.median(d) * 1e-6)
                     line += f"  algorithmic {b / 1e6:8.2f} MB -> {bw / 1e12:5.2f} TB/s = {100 * bw / HBM_BYTES_PER_S:5.1f} % of 6.3 TB/s"
