@@ -621,6 +621,58 @@ int odo_volume_destroy(odo_volume* v);
  * finished before they return (the front end's ring of four slots used two frames ahead satisfies this). */
 int odo_tracker_attach_volume(odo_tracker* t, odo_volume* v);
 
+/* ---- Colour in the TSDF volume: the sensor's colour fused beside the geometry, colours for its points and its mesh ------------------
+ * Optional. A volume that never calls odo_volume_enable_colour allocates nothing more, behaves and writes exactly as above.
+ * Colour grid. A second array beside the voxel grid, one 32-bit word per voxel in the same raster order: uint8 R, G, B (bytes 0, 1,
+ * 2) and uint8 wc (byte 3: the colour weight, 0 = never coloured); cleared to 0. +4 B per voxel: 8 B per voxel in all, 49 MB for a
+ * 240 x 128 x 200 grid.
+ * Colour frame. rows x cols pixels in the grid of the depth frames (the grey camera's), interleaved uint8, dense rows, 3 or 4
+ * channels in the order RGB(A) or BGR(A) (the front end's formats); a fourth channel is ignored. Stored as R, G, B whatever the order.
+ * Coloured integration of one frame. Steps 1 to 5 of the integration above unchanged: q, w and the counters are bit for bit those
+ * of odo_volume_integrate_dev on the same frame. Exactly the voxels that update touches AND that lie in the band, fabsf(sdf) <= mu
+ * (the predicate of the in-band counter, so the colour updates of a frame equal that counter), also read the colour pixel (xi, yi)
+ * of step 2 — the pixel the depth reading came from, nearest, no interpolation — and update their colour word; no other voxel reads a
+ * colour pixel or touches the colour grid. Per channel, with the sample s, in unsigned integer arithmetic with floor division:
+ *   c' = (c * wc + s + ((wc + 1) >> 1)) / (wc + 1);   then wc' = min(wc + 1, max_weight).
+ * The numerator stays below 2^17, the result is in 0 .. 255, and wc = 0 gives c' = s (odometry_amd/csrc/volume_colour_math.h holds the
+ * device's formulation, a multiplication by a reciprocal that gives this value for every (c, wc, s)). A running 8-bit average stalls at
+ * weight 255: a sample that differs from c by less than half a level times 256 = 128 levels leaves c where it is. That is known and
+ * accepted; a caller who wants an average that tracks sets max_weight small (with 3, a sample moves c by a quarter of the difference).
+ * Colour of a point or vertex on the edge (a, b) with the extraction's alpha (in [0, 1] by construction, so no clamp is needed): both
+ * voxels have wc > 0: per channel rintf((float)Ca + alpha * ((float)Cb - (float)Ca)), the product rounded, then the sum, and
+ * A = 255; exactly one has: that voxel's R, G, B and A = 255; neither: (0, 0, 0, 0). uint8[4] per point, index for index beside
+ * xyz0 / nrmw. */
+typedef struct {
+  int channels;            /* 3 | 4 */
+  int bgr;                 /* 0: RGB(A), 1: BGR(A) */
+  int max_weight;          /* 1 .. 255 */
+} odo_volume_colour_params;
+/* Validates first, then allocates the colour grid and clears it on the volume's stream. Refused (-1, nothing changed) on a second
+ * call and while the volume is attached to a tracker. */
+int odo_volume_enable_colour(odo_volume* v, const odo_volume_colour_params* p);
+/* odo_volume_integrate_dev with the colour update: the same stream, ordering, refusal of a non-finite pose and buffer lifetimes (the
+ * colour buffer as the depth buffer), one fused launch and the sum. colour_dev: the device colour frame, 4-byte aligned when
+ * channels == 4. Refused on a volume without colour. odo_volume_integrate_dev on a volume with colour stays legal and leaves the
+ * colour grid alone. */
+int odo_volume_integrate_colour_dev(odo_volume* v, const uint16_t* depth_dev, const uint8_t* colour_dev, const float abs_pose_colmajor[16]);
+/* The whole colour grid to / from the host, 4 bytes {R, G, B, wc} per voxel in raster order, with the ordering and refusal rules of
+ * odo_volume_download / odo_volume_upload (the upload is refused while attached). odo_volume_upload does not touch the colour grid;
+ * odo_volume_clear clears it. Refused on a volume without colour. */
+int odo_volume_download_colour(odo_volume* v, uint8_t* rgbw);
+int odo_volume_upload_colour(odo_volume* v, const uint8_t* rgbw);
+/* odo_volume_extract / odo_volume_mesh plus one uint8[4] row per point / vertex (one launch more on the volume's stream, skipped
+ * when nothing is written; no atomics). xyz0, nrmw, tri, the counts and the capacity rules are bit for bit those of the uncoloured
+ * calls on the same volume. Refused on a volume without colour. Neither grid and no counter is modified. */
+int odo_volume_extract_colour(odo_volume* v, long capacity, float* xyz0, float* nrmw, uint8_t* rgba, long* n_points, long* n_dropped);
+int odo_volume_mesh_colour(odo_volume* v, long vertex_capacity, long triangle_capacity, float* xyz0, float* nrmw, uint8_t* rgba,
+                           int32_t* tri, long counts[4]);
+/* Names the colour frame (device) of the frame that the next odo_tracker_init_rgbd / odo_tracker_track_rgbd gets. That call consumes
+ * it whether or not it integrates (a failed Solve integrates nothing, as without colour). With a frame named, the attached volume's
+ * integration of that frame is the coloured one; without, the plain one. The buffer follows the depth buffer's rule: unchanged until
+ * the next track / init / quiesce / destroy has returned. Refused unless this is an RGB-D tracker with a colour-enabled volume
+ * attached. Poses, masks, keyframe flags and motion scores are bit-identical with and without it. */
+int odo_tracker_frame_colour(odo_tracker* t, const uint8_t* colour_dev);
+
 /* ---- RGB-D front end: raw sensor frames -> the RGB-D tracker's inputs ----------------------------------------------------------
  * A sensor delivers interleaved 8-bit colour and a uint16 depth frame in the DEPTH imager's pixel grid (its own intrinsics, often
  * its own resolution, centimetres beside the colour imager); odo_tracker_*_rgbd take an fp32 grey image and a uint16 depth frame in
@@ -677,6 +729,11 @@ int odo_rgbd_frontend_submit_host(odo_rgbd_frontend* f, const uint8_t* colour, s
 /* Host wait until the slot with that grey buffer is complete; its two buffers may then be handed to odo_tracker_init_rgbd /
  * _track_rgbd / _hint_next_rgbd. -1 if no frame was ever submitted to that slot. */
 int odo_rgbd_frontend_wait(odo_rgbd_frontend* f, const float* gray_out);
+/* The device colour frame the slot with that grey buffer was made from: after odo_rgbd_frontend_submit_dev the caller's pointer,
+ * after odo_rgbd_frontend_submit_host the slot's own raw copy. Valid (complete and unchanged) from the slot's completion until the
+ * slot comes round again; with it a tracker fed by the front end colours its volume (odo_tracker_frame_colour) without a second
+ * upload. Does not wait. -1 for a slot that never received a submit. */
+int odo_rgbd_frontend_colour(odo_rgbd_frontend* f, const float* gray_out, const uint8_t** colour_dev);
 /* out: n_depth (depth pixels with r != 0), n_filled (target pixels with a value), dropped_behind, dropped_range, dropped_splat,
  * frame number (0-based count of submits). Waits for the slot. */
 int odo_rgbd_frontend_stats(odo_rgbd_frontend* f, const float* gray_out, long out[6]);

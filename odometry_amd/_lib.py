@@ -49,6 +49,10 @@ class VolumeParams(C.Structure):
                 ("K", Intrinsics), ("depth_scale", C.c_float)]
 
 
+class VolumeColourParams(C.Structure):
+    _fields_ = [("channels", C.c_int), ("bgr", C.c_int), ("max_weight", C.c_int)]
+
+
 _fp = C.POINTER(C.c_float)
 _dp = C.POINTER(C.c_double)
 _u8p = C.POINTER(C.c_uint8)
@@ -221,6 +225,14 @@ SIGNATURES = {
     "odo_volume_clear": (C.c_int, [_vp]),
     "odo_volume_destroy": (C.c_int, [_vp]),
     "odo_tracker_attach_volume": (C.c_int, [_vp, _vp]),
+    "odo_volume_enable_colour": (C.c_int, [_vp, C.POINTER(VolumeColourParams)]),
+    "odo_volume_integrate_colour_dev": (C.c_int, [_vp, _vp, _vp, _fp]),
+    "odo_volume_download_colour": (C.c_int, [_vp, _u8p]),
+    "odo_volume_upload_colour": (C.c_int, [_vp, _u8p]),
+    "odo_volume_extract_colour": (C.c_int, [_vp, C.c_long, _fp, _fp, _u8p, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "odo_volume_mesh_colour": (C.c_int, [_vp, C.c_long, C.c_long, _fp, _fp, _u8p, C.POINTER(C.c_int32), C.POINTER(C.c_long)]),
+    "odo_tracker_frame_colour": (C.c_int, [_vp, _vp]),
+    "odo_rgbd_frontend_colour": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
 }
 
 _lib = None

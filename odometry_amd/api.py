@@ -730,6 +730,16 @@ class RgbdTracker(Tracker):
         self._bufs.append(p)
         return p
 
+    def upload_colour(self, colour):
+        """An interleaved uint8 colour frame (rows x cols x 3 | 4) into a device buffer owned by the tracker: a handle for
+        frame_colour."""
+        colour = np.ascontiguousarray(colour, np.uint8)
+        p = C.c_void_p()
+        L.check(self.lib.odo_dev_alloc(self._ctx, colour.nbytes, C.byref(p)), "odo_dev_alloc")
+        L.check(self.lib.odo_dev_upload(self._ctx, p, colour.ctypes.data_as(C.c_void_p), colour.nbytes), "odo_dev_upload")
+        self._bufs.append(p)
+        return p
+
     def init(self, gray_dev, depth_dev, abs_pose0=None):
         pose = _colmajor(np.eye(4) if abs_pose0 is None else abs_pose0)
         L.check(self.lib.odo_tracker_init_rgbd(self.h, gray_dev, depth_dev, _fp(pose)), "odo_tracker_init_rgbd")
@@ -772,6 +782,12 @@ class RgbdTracker(Tracker):
         self._vol = v
         if v is not None:
             v._tracker = self
+
+    def frame_colour(self, colour_dev):
+        """Names the device colour frame of the frame the next init / track gets: with a colour-enabled TsdfVolume attached, that
+        frame's integration is the coloured one. The buffer follows the depth buffer's rule (unchanged until the next track / init /
+        close has returned)."""
+        L.check(self.lib.odo_tracker_frame_colour(self.h, colour_dev), "odo_tracker_frame_colour")
 
     def depth_report(self):
         """The last frame's depth statistics (odo_depth_report): iters, cost, n_selected, n_matched, n_valid."""
@@ -904,9 +920,49 @@ class TsdfVolume:
         L.check(self.lib.odo_volume_create(ctx, C.byref(p), C.byref(h)), "odo_volume_create")
         self.h = h
 
-    def integrate(self, depth, abs_pose):
-        """One depth frame: a uint16 numpy array (uploaded into a temporary buffer) or a device handle; abs_pose = 4x4 camera-to-world."""
+    def enable_colour(self, channels=3, bgr=False, max_weight=255):
+        """Adds the colour grid (4 B per voxel more): colour frames are rows x cols x channels uint8, RGB(A) or BGR(A); max_weight
+        (1 .. 255) caps the colour's running average. Once, and not while attached to a tracker."""
+        cp = L.VolumeColourParams(int(channels), int(bool(bgr)), int(max_weight))
+        L.check(self.lib.odo_volume_enable_colour(self.h, C.byref(cp)), "odo_volume_enable_colour")
+        self.colour_params = cp
+
+    @property
+    def has_colour(self):
+        return getattr(self, "colour_params", None) is not None
+
+    def _integrate_colour(self, depth, pose, colour):
+        if not self.has_colour:
+            raise L.OdoError("TsdfVolume.integrate: the volume has no colour grid (enable_colour first)")
+        if isinstance(depth, np.ndarray) != isinstance(colour, np.ndarray):
+            raise TypeError("depth and colour must both be numpy arrays or both be device handles")
+        if not isinstance(depth, np.ndarray):
+            L.check(self.lib.odo_volume_integrate_colour_dev(self.h, depth, colour, _fp(pose)), "odo_volume_integrate_colour_dev")
+            return
+        depth = np.ascontiguousarray(depth, np.uint16)
+        assert depth.shape == (self.rows, self.cols), depth.shape
+        if colour.dtype != np.uint8 or colour.shape != (self.rows, self.cols, self.colour_params.channels):
+            raise ValueError(f"colour frame {colour.dtype} {colour.shape}")
+        colour = np.ascontiguousarray(colour)
+        bufs = []
+        try:
+            for a in (depth, colour):
+                p = C.c_void_p()
+                L.check(self.lib.odo_dev_alloc(self._ctx, a.nbytes, C.byref(p)), "odo_dev_alloc")
+                bufs.append(p)
+                L.check(self.lib.odo_dev_upload(self._ctx, p, a.ctypes.data_as(C.c_void_p), a.nbytes), "odo_dev_upload")
+            L.check(self.lib.odo_volume_integrate_colour_dev(self.h, bufs[0], bufs[1], _fp(pose)), "odo_volume_integrate_colour_dev")
+        finally:   # odo_dev_free waits for the context's stream: the integration has read the frames
+            for p in bufs:
+                self.lib.odo_dev_free(self._ctx, p)
+
+    def integrate(self, depth, abs_pose, colour=None):
+        """One depth frame: a uint16 numpy array (uploaded into a temporary buffer) or a device handle; abs_pose = 4x4 camera-to-world.
+        colour (a volume with enable_colour): the frame's colour pixels, a numpy array or a device handle like depth; the voxels of
+        the band then take their colour from it."""
         pose = _colmajor(abs_pose)
+        if colour is not None:
+            return self._integrate_colour(depth, pose, colour)
         if isinstance(depth, np.ndarray):
             depth = np.ascontiguousarray(depth, np.uint16)
             assert depth.shape == (self.rows, self.cols), depth.shape
@@ -923,15 +979,35 @@ class TsdfVolume:
     def sync(self):
         L.check(self.lib.odo_volume_sync(self.h), "odo_volume_sync")
 
-    def extract(self, capacity=1 << 20, with_dropped=False):
-        """The surface: (n, 4) float32 x, y, z, 0 and (n, 4) float32 nx, ny, nz, weight, at most `capacity` points (with_dropped:
-        also the number of points beyond it)."""
+    def extract(self, capacity=1 << 20, with_dropped=False, colour=False):
+        """The surface: (n, 4) float32 x, y, z, 0 and (n, 4) float32 nx, ny, nz, weight, at most `capacity` points (colour: also
+        (n, 4) uint8 R, G, B, A; with_dropped: also the number of points beyond the capacity)."""
         xyz0 = np.zeros((max(capacity, 1), 4), np.float32)
         nrmw = np.zeros((max(capacity, 1), 4), np.float32)
         n, d = C.c_long(0), C.c_long(0)
-        L.check(self.lib.odo_volume_extract(self.h, capacity, _fp(xyz0), _fp(nrmw), C.byref(n), C.byref(d)), "odo_volume_extract")
-        out = xyz0[:n.value].copy(), nrmw[:n.value].copy()
+        if colour:
+            rgba = np.zeros((max(capacity, 1), 4), np.uint8)
+            L.check(self.lib.odo_volume_extract_colour(self.h, capacity, _fp(xyz0), _fp(nrmw), rgba.ctypes.data_as(L._u8p), C.byref(n),
+                                                       C.byref(d)), "odo_volume_extract_colour")
+            out = xyz0[:n.value].copy(), nrmw[:n.value].copy(), rgba[:n.value].copy()
+        else:
+            L.check(self.lib.odo_volume_extract(self.h, capacity, _fp(xyz0), _fp(nrmw), C.byref(n), C.byref(d)), "odo_volume_extract")
+            out = xyz0[:n.value].copy(), nrmw[:n.value].copy()
         return out + (d.value,) if with_dropped else out
+
+    def colour_grid(self):
+        """(nz, ny, nx, 4) uint8: R, G, B and the colour weight of every voxel."""
+        nx, ny, nz = self.dims
+        c = np.zeros((nz, ny, nx, 4), np.uint8)
+        L.check(self.lib.odo_volume_download_colour(self.h, c.ctypes.data_as(L._u8p)), "odo_volume_download_colour")
+        return c
+
+    def upload_colour(self, rgbw):
+        """The whole colour grid from the host: (nz, ny, nx, 4) uint8 (what colour_grid() returns). Refused while attached."""
+        nx, ny, nz = self.dims
+        rgbw = np.ascontiguousarray(rgbw, np.uint8)
+        assert rgbw.shape == (nz, ny, nx, 4), rgbw.shape
+        L.check(self.lib.odo_volume_upload_colour(self.h, rgbw.ctypes.data_as(L._u8p)), "odo_volume_upload_colour")
 
     def grid(self):
         """(q int16, w uint16), each of shape (nz, ny, nx)."""
@@ -957,10 +1033,11 @@ class TsdfVolume:
         L.check(self.lib.odo_volume_mesh(self.h, 0, 0, None, None, None, o), "odo_volume_mesh")
         return o[1], o[3]
 
-    def mesh(self, vertex_capacity=None, triangle_capacity=None, with_counts=False):
+    def mesh(self, vertex_capacity=None, triangle_capacity=None, with_counts=False, colour=False):
         """The surface as triangles (marching tetrahedra): (n, 4) float32 x, y, z, e; (n, 4) float32 nx, ny, nz, weight; (m, 3) int32
         vertex indices, counter-clockwise seen from free space. Without capacities it asks for the totals first and then calls with
-        exact ones; with them the first `capacity` items are returned, indices unchanged (with_counts: also the four counts)."""
+        exact ones; with them the first `capacity` items are returned, indices unchanged (with_counts: also the four counts).
+        colour: (n, 4) uint8 R, G, B, A per vertex as one more array behind the indices."""
         if vertex_capacity is None or triangle_capacity is None:
             nv, nt = self.mesh_counts()
             vertex_capacity = nv if vertex_capacity is None else vertex_capacity
@@ -969,9 +1046,16 @@ class TsdfVolume:
         nrmw = np.zeros((max(vertex_capacity, 1), 4), np.float32)
         tri = np.zeros((max(triangle_capacity, 1), 3), np.int32)
         o = (C.c_long * 4)()
-        L.check(self.lib.odo_volume_mesh(self.h, vertex_capacity, triangle_capacity, _fp(xyz0), _fp(nrmw),
-                                         tri.ctypes.data_as(C.POINTER(C.c_int32)), o), "odo_volume_mesh")
-        out = xyz0[:o[0]].copy(), nrmw[:o[0]].copy(), tri[:o[2]].copy()
+        if colour:
+            rgba = np.zeros((max(vertex_capacity, 1), 4), np.uint8)
+            L.check(self.lib.odo_volume_mesh_colour(self.h, vertex_capacity, triangle_capacity, _fp(xyz0), _fp(nrmw),
+                                                    rgba.ctypes.data_as(L._u8p), tri.ctypes.data_as(C.POINTER(C.c_int32)), o),
+                    "odo_volume_mesh_colour")
+            out = xyz0[:o[0]].copy(), nrmw[:o[0]].copy(), tri[:o[2]].copy(), rgba[:o[0]].copy()
+        else:
+            L.check(self.lib.odo_volume_mesh(self.h, vertex_capacity, triangle_capacity, _fp(xyz0), _fp(nrmw),
+                                             tri.ctypes.data_as(C.POINTER(C.c_int32)), o), "odo_volume_mesh")
+            out = xyz0[:o[0]].copy(), nrmw[:o[0]].copy(), tri[:o[2]].copy()
         return out + (tuple(o),) if with_counts else out
 
     def stats(self):
@@ -983,14 +1067,24 @@ class TsdfVolume:
         L.check(self.lib.odo_volume_clear(self.h), "odo_volume_clear")
 
     def save_ply(self, path, capacity=1 << 22):
-        """Binary little-endian PLY of the extracted surface: float x y z nx ny nz."""
-        xyz0, nrmw = self.extract(capacity)
-        write_ply_normals(path, xyz0, nrmw)
+        """Binary little-endian PLY of the extracted surface: float x y z nx ny nz, and uchar red green blue when the volume has
+        colour."""
+        if self.has_colour:
+            xyz0, nrmw, rgba = self.extract(capacity, colour=True)
+            write_ply_normals(path, xyz0, nrmw, rgb=rgba)
+        else:
+            xyz0, nrmw = self.extract(capacity)
+            write_ply_normals(path, xyz0, nrmw)
 
     def save_mesh_ply(self, path):
-        """Binary little-endian PLY of the mesh: float x y z nx ny nz per vertex, three int indices per face."""
-        xyz0, nrmw, tri = self.mesh()
-        write_ply_mesh(path, xyz0, nrmw, tri)
+        """Binary little-endian PLY of the mesh: float x y z nx ny nz per vertex (and uchar red green blue when the volume has
+        colour), three int indices per face."""
+        if self.has_colour:
+            xyz0, nrmw, tri, rgba = self.mesh(colour=True)
+            write_ply_mesh(path, xyz0, nrmw, tri, rgb=rgba)
+        else:
+            xyz0, nrmw, tri = self.mesh()
+            write_ply_mesh(path, xyz0, nrmw, tri)
 
     def close(self):
         if getattr(self, "h", None):
@@ -1075,6 +1169,13 @@ class RgbdFrontend:
     def wait(self, gray_dev):
         L.check(self.lib.odo_rgbd_frontend_wait(self.h, gray_dev), "odo_rgbd_frontend_wait")
 
+    def colour(self, gray_dev):
+        """The device colour frame the slot with that grey buffer was made from (the caller's handle, or the slot's own raw copy of a
+        host frame): what RgbdTracker.frame_colour takes. Valid from the slot's completion until the slot comes round again."""
+        c = C.c_void_p()
+        L.check(self.lib.odo_rgbd_frontend_colour(self.h, gray_dev, C.byref(c)), "odo_rgbd_frontend_colour")
+        return c
+
     def stats(self, gray_dev):
         o = (C.c_long * 6)()
         L.check(self.lib.odo_rgbd_frontend_stats(self.h, gray_dev, o), "odo_rgbd_frontend_stats")
@@ -1118,37 +1219,47 @@ def write_ply(path, xyzi):
         f.write(rec.tobytes())
 
 
-def write_ply_normals(path, xyz, normals):
-    """(N, >= 3) positions and (N, >= 3) normals -> binary little-endian PLY with float x y z nx ny nz."""
+def _ply_vertices(xyz, normals, rgb):
+    """The vertex records and their property lines: float x y z nx ny nz, then uchar red green blue when rgb (N, >= 3) is given."""
     xyz = np.asarray(xyz, np.float32)
     normals = np.asarray(normals, np.float32)
     assert xyz.ndim == 2 and normals.shape[0] == xyz.shape[0] and xyz.shape[1] >= 3 and normals.shape[1] >= 3
-    rec = np.zeros(len(xyz), np.dtype([(k, "<f4") for k in ("x", "y", "z", "nx", "ny", "nz")]))
+    fields = [(k, "<f4") for k in ("x", "y", "z", "nx", "ny", "nz")]
+    props = "".join("property float %s\n" % k for k in ("x", "y", "z", "nx", "ny", "nz"))
+    if rgb is not None:
+        rgb = np.asarray(rgb, np.uint8)
+        assert rgb.ndim == 2 and rgb.shape[0] == xyz.shape[0] and rgb.shape[1] >= 3
+        fields += [(k, "u1") for k in ("red", "green", "blue")]
+        props += "".join("property uchar %s\n" % k for k in ("red", "green", "blue"))
+    rec = np.zeros(len(xyz), np.dtype(fields))
     for c, k in enumerate(("x", "y", "z")):
         rec[k] = xyz[:, c]
         rec["n" + k] = normals[:, c]
-    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % len(xyz)) + "".join(
-        "property float %s\n" % k for k in ("x", "y", "z", "nx", "ny", "nz")) + "end_header\n"
+    if rgb is not None:
+        for c, k in enumerate(("red", "green", "blue")):
+            rec[k] = rgb[:, c]
+    return rec, props
+
+
+def write_ply_normals(path, xyz, normals, rgb=None):
+    """(N, >= 3) positions and (N, >= 3) normals -> binary little-endian PLY with float x y z nx ny nz; rgb (N, >= 3) uint8: also
+    uchar red green blue."""
+    rec, props = _ply_vertices(xyz, normals, rgb)
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % len(rec)) + props + "end_header\n"
     with open(path, "wb") as f:
         f.write(header.encode("ascii"))
         f.write(rec.tobytes())
 
-def write_ply_mesh(path, xyz, normals, tri):
-    """(N, >= 3) positions, (N, >= 3) normals and (M, 3) vertex indices -> binary little-endian PLY: vertex float x y z nx ny nz, face
-    list uchar int vertex_indices."""
-    xyz = np.asarray(xyz, np.float32)
-    normals = np.asarray(normals, np.float32)
+
+def write_ply_mesh(path, xyz, normals, tri, rgb=None):
+    """(N, >= 3) positions, (N, >= 3) normals and (M, 3) vertex indices -> binary little-endian PLY: vertex float x y z nx ny nz (rgb
+    (N, >= 3) uint8: also uchar red green blue), face list uchar int vertex_indices."""
     tri = np.asarray(tri, np.int32).reshape(-1, 3)
-    assert xyz.ndim == 2 and normals.shape[0] == xyz.shape[0] and xyz.shape[1] >= 3 and normals.shape[1] >= 3
-    rec = np.zeros(len(xyz), np.dtype([(k, "<f4") for k in ("x", "y", "z", "nx", "ny", "nz")]))
-    for c, k in enumerate(("x", "y", "z")):
-        rec[k] = xyz[:, c]
-        rec["n" + k] = normals[:, c]
+    rec, props = _ply_vertices(xyz, normals, rgb)
     faces = np.zeros(len(tri), np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
     faces["n"] = 3
     faces["v"] = tri
-    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % len(xyz)) + "".join(
-        "property float %s\n" % k for k in ("x", "y", "z", "nx", "ny", "nz")) + (
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % len(rec)) + props + (
         "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % len(tri))
     with open(path, "wb") as f:
         f.write(header.encode("ascii"))

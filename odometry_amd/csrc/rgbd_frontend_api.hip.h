@@ -21,6 +21,7 @@ struct odo_rgbd_frontend {
   uint8_t* d_colour_in[kFeMaxSlots];   // submit_host: the slot's raw frame on the device (allocated on first use)
   uint16_t* d_depth_in[kFeMaxSlots];
   long slot_frame[kFeMaxSlots]; // the frame the slot holds (or will hold), -1: none yet
+  const uint8_t* slot_colour[kFeMaxSlots];   // the device colour frame the slot was made from (the caller's, or d_colour_in[slot])
   uint32_t* d_zbuf;
   FeCounters* d_ctr;
   long long* h_stats;           // host-mapped [slots][6]
@@ -119,6 +120,7 @@ static int fe_enqueue(odo_rgbd_frontend* f, int s, const uint8_t* colour_dev, co
   launch_rgbd_frontend(a, f->own);
   HIP_OK(hipGetLastError());
   f->slot_frame[s] = f->submitted;
+  f->slot_colour[s] = colour_dev;
   f->submitted++;
   *gray_out = f->d_gray[s];
   *depth_out = f->d_depth[s];
@@ -187,6 +189,15 @@ extern "C" int odo_rgbd_frontend_wait(odo_rgbd_frontend* f, const float* gray_ou
   }
   std::atomic_thread_fence(std::memory_order_acquire);
   f->done_upto = frame + 1;   // the stream runs the frames in order: every earlier one is complete as well
+  return 0;
+}
+
+extern "C" int odo_rgbd_frontend_colour(odo_rgbd_frontend* f, const float* gray_out, const uint8_t** colour_dev) {
+  if (!f || !gray_out || !colour_dev) return fail("odo_rgbd_frontend_colour: NULL arg");
+  *colour_dev = nullptr;
+  const int s = fe_slot_of(f, gray_out);
+  if (s < 0) return fail("odo_rgbd_frontend_colour: not the grey buffer of a submitted frame");
+  *colour_dev = f->slot_colour[s];
   return 0;
 }
 

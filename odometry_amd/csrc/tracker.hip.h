@@ -87,6 +87,9 @@ struct odo_tracker {
   odo_volume* vol;             // nullptr: no volume, and nothing below is used
   hipEvent_t ev_vol[2];        // the volume's stream: behind integration n, slot n & 1
   long vol_n;                  // integrations enqueued since the last drain
+  // Colour of the attached volume (odo_tracker_frame_colour): the colour frame named for the next init_rgbd / track_rgbd, and the one
+  // of the call that is running. nullptr: that frame's integration is the plain one.
+  const uint8_t *col_next, *col_cur;
   // Depth source (odo_tracker_create_rgbd): 1 = a uint16 sensor depth frame per frame instead of the right image. Only the stream-B
   // job's front differs (rgbd_job_begin / rgbd_job_stats); everything behind it is the stereo tracker's.
   int rgbd;
@@ -184,7 +187,7 @@ static int tracker_create(int device, const odo_tracker_params* p, int rgbd, flo
   t->dbg_pre_us = t->dbg_spin_us = t->dbg_chain_us = t->dbg_verdict_us = t->dbg_post_us = t->dbg_relaunch_us = 0.0; t->dbg_n = t->dbg_relaunch_n = 0;
   t->depth_ahead = getenv("ODO_NO_DEPTH_AHEAD") ? 0 : 1;
   t->map = nullptr; t->ev_map[0] = t->ev_map[1] = nullptr; t->map_wait[0].store(0); t->map_wait[1].store(0); t->map_kf_slot = -1;
-  t->vol = nullptr; t->ev_vol[0] = t->ev_vol[1] = nullptr; t->vol_n = 0;
+  t->vol = nullptr; t->ev_vol[0] = t->ev_vol[1] = nullptr; t->vol_n = 0; t->col_next = t->col_cur = nullptr;
   t->rgbd = rgbd; t->depth_scale = depth_scale; t->max_depth_step = max_depth_step;
   t->p = *p;
   float eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
@@ -515,7 +518,7 @@ static int tracker_vol_integrate(odo_tracker* t, const uint16_t* depth, const fl
   odo_volume* v = t->vol;
   long before = t->vol_n - 1;   // the last integration of an earlier call
   if (abs_pose && pose_finite(abs_pose)) {
-    if (volume_integrate(v, depth, abs_pose, v->own)) return -1;
+    if (volume_integrate(v, depth, abs_pose, v->own, v->colour ? t->col_cur : nullptr)) return -1;
     HIP_OK(hipEventRecord(t->ev_vol[t->vol_n & 1], v->own));
     t->vol_n++;
   }
@@ -538,6 +541,7 @@ extern "C" int odo_tracker_attach_volume(odo_tracker* t, odo_volume* v) {
     return fail("odo_tracker_attach_volume: the volume (device %d, %dx%d) does not match the tracker (device %d, %dx%d)", v->device,
                 v->p.rows, v->p.cols, t->ctx_a->device, t->p.rows, t->p.cols);
   HIP_OK(hipSetDevice(t->ctx_a->device));
+  t->col_next = nullptr;   // (a colour frame named for the volume that leaves)
   if (t->vol) {   // detach: the integrations already enqueued complete first
     if (volume_sync(t->vol)) return -1;
     t->vol_n = 0;
@@ -593,7 +597,21 @@ extern "C" int odo_tracker_init(odo_tracker* t, const float* left, const float* 
 extern "C" int odo_tracker_init_rgbd(odo_tracker* t, const float* gray_dev, const uint16_t* depth_dev, const float abs_pose0[16]) {
   if (!t || !gray_dev || !depth_dev || !abs_pose0) return fail("odo_tracker_init_rgbd: NULL arg");
   if (!t->rgbd) return fail("odo_tracker_init_rgbd: a stereo tracker (odo_tracker_create) takes odo_tracker_init");
-  return tracker_init(t, gray_dev, (const float*)depth_dev, abs_pose0);
+  t->col_cur = t->col_next;   // consumed by this call, whether or not it integrates
+  t->col_next = nullptr;
+  const int rc = tracker_init(t, gray_dev, (const float*)depth_dev, abs_pose0);
+  t->col_cur = nullptr;
+  return rc;
+}
+
+extern "C" int odo_tracker_frame_colour(odo_tracker* t, const uint8_t* colour_dev) {
+  if (!t || !colour_dev) return fail("odo_tracker_frame_colour: NULL arg");
+  if (!t->rgbd) return fail("odo_tracker_frame_colour: a stereo tracker has no volume to colour (RGB-D trackers only)");
+  if (!t->vol || !t->vol->colour)
+    return fail("odo_tracker_frame_colour: no volume with a colour grid is attached (odo_volume_enable_colour, then odo_tracker_attach_volume)");
+  if (t->vol->cp.channels == 4 && ((uintptr_t)colour_dev & 3)) return fail("odo_tracker_frame_colour: misaligned colour frame (4 channels: 4-byte aligned)");
+  t->col_next = colour_dev;
+  return 0;
 }
 
 // Inverse of a 4x4 (Eigen Matrix4f::inverse(), ref: run_odometry_kitti_offline.cpp:218): Gauss-Jordan in fp64,
@@ -898,7 +916,11 @@ extern "C" int odo_tracker_track_rgbd(odo_tracker* t, const float* gray_dev, con
                                       float abs_pose[16], int* is_new_keyframe, float* motion_mag, int* solve_status) {
   if (!t || !gray_dev || !depth_dev) return fail("odo_tracker_track_rgbd: NULL arg");
   if (!t->rgbd) return fail("odo_tracker_track_rgbd: a stereo tracker (odo_tracker_create) takes odo_tracker_track");
-  return tracker_track(t, gray_dev, (const float*)depth_dev, pose_to_keyframe, abs_pose, is_new_keyframe, motion_mag, solve_status);
+  t->col_cur = t->col_next;   // consumed by this call, whether or not it integrates
+  t->col_next = nullptr;
+  const int rc = tracker_track(t, gray_dev, (const float*)depth_dev, pose_to_keyframe, abs_pose, is_new_keyframe, motion_mag, solve_status);
+  t->col_cur = nullptr;
+  return rc;
 }
 
 // Host-clock averages per tracked frame since the last call (microseconds): whole track() call, Solve (stream A, calling

@@ -70,6 +70,7 @@ struct VolExtractArgs {
 };
 
 void launch_volume_integrate(const VolIntegrateArgs& a, hipStream_t s);
+void launch_volume_sum(const VolIntegrateArgs& a, hipStream_t s);   // the sum alone: behind the coloured integration (volume_colour.hip.h)
 void launch_volume_extract(const VolExtractArgs& a, hipStream_t s);
 
 }  // namespace odo

@@ -5,6 +5,7 @@
 #pragma once
 #include "volume.hip.h"
 #include "volume_mesh.hip.h"
+#include "volume_colour.hip.h"
 
 struct odo_volume {
   odo_ctx* ctx;                 // standalone integrations (odo_volume_integrate_dev) run on its stream
@@ -33,11 +34,18 @@ struct odo_volume {
   long mesh_vertex_capacity, mesh_triangle_capacity;
   long n_frames;                // integrations since create / clear
   odo_tracker* attached;
+  // colour (odo_volume_enable_colour; nothing below is allocated without it)
+  int colour;                   // 1: the colour grid exists
+  odo_volume_colour_params cp;
+  uint32_t* d_col;              // [n_vox]: {R, G, B, wc}
+  uint32_t *d_rgba, *d_mesh_rgba;   // the colours of the extraction's points / the mesh's vertices, grown on demand
+  long rgba_capacity, mesh_rgba_capacity;
 };
 
 static int volume_release(odo_volume* v) {
   void* ps[] = {v->d_vox, v->d_blk, v->d_ctr, v->d_wave, v->d_off, v->d_cnt, v->d_xyz0, v->d_nrmw,
-                v->d_mesh_mask, v->d_mesh_base, v->d_mesh_cnt, v->d_mesh_off, v->d_mesh_ctr, v->d_mesh_xyz0, v->d_mesh_nrmw, v->d_mesh_tri};
+                v->d_mesh_mask, v->d_mesh_base, v->d_mesh_cnt, v->d_mesh_off, v->d_mesh_ctr, v->d_mesh_xyz0, v->d_mesh_nrmw, v->d_mesh_tri,
+                v->d_col, v->d_rgba, v->d_mesh_rgba};
   for (void* p : ps) if (p) (void)hipFree(p);
   if (v->ev_last) (void)hipEventDestroy(v->ev_last);
   if (v->own) (void)hipStreamDestroy(v->own);
@@ -65,6 +73,7 @@ static int volume_sync(odo_volume* v) {
 static int volume_reset(odo_volume* v) {
   if (volume_order_on(v, v->own)) return -1;
   HIP_OK(hipMemsetAsync(v->d_vox, 0, sizeof(uint32_t) * (size_t)v->n_vox, v->own));
+  if (v->colour) HIP_OK(hipMemsetAsync(v->d_col, 0, sizeof(uint32_t) * (size_t)v->n_vox, v->own));
   HIP_OK(hipMemsetAsync(v->d_ctr, 0, sizeof(VolCounters), v->own));
   v->n_frames = 0;
   return volume_mark(v, v->own);
@@ -94,6 +103,8 @@ extern "C" int odo_volume_create(odo_ctx* ctx, const odo_volume_params* p, odo_v
   v->d_mesh_mask = nullptr; v->d_mesh_base = nullptr; v->d_mesh_cnt = nullptr; v->d_mesh_off = nullptr; v->d_mesh_ctr = nullptr;
   v->d_mesh_xyz0 = v->d_mesh_nrmw = nullptr; v->d_mesh_tri = nullptr; v->mesh_vertex_capacity = v->mesh_triangle_capacity = 0;
   v->n_frames = 0; v->attached = nullptr;
+  v->colour = 0; memset(&v->cp, 0, sizeof(v->cp)); v->d_col = nullptr; v->d_rgba = v->d_mesh_rgba = nullptr;
+  v->rgba_capacity = v->mesh_rgba_capacity = 0;
   bool ok = hipStreamCreateWithFlags(&v->own, hipStreamNonBlocking) == hipSuccess &&
             hipEventCreateWithFlags(&v->ev_last, hipEventDisableTiming) == hipSuccess &&
             hipMalloc((void**)&v->d_vox, sizeof(uint32_t) * (size_t)v->n_vox) == hipSuccess &&
@@ -122,8 +133,9 @@ static bool pose_finite(const float* A) {
   return true;
 }
 
-// One integration on stream s (async). depth: rows x cols uint16 on the device; A: camera-to-world, finite.
-static int volume_integrate(odo_volume* v, const uint16_t* depth, const float* A, hipStream_t s) {
+// One integration on stream s (async). depth: rows x cols uint16 on the device; A: camera-to-world, finite. colour: nullptr = the
+// plain integration, else the frame's colour pixels on the device (the volume has a colour grid): the fused coloured launch.
+static int volume_integrate(odo_volume* v, const uint16_t* depth, const float* A, hipStream_t s, const uint8_t* colour = nullptr) {
   HIP_OK(hipSetDevice(v->device));
   if (volume_order_on(v, s)) return -1;
   float M[16];
@@ -143,7 +155,15 @@ static int volume_integrate(odo_volume* v, const uint16_t* depth, const float* A
   a.nblk = (int)std::min<long long>(a.tiles, kVolMaxBlocks);
   a.step_x = a.nblk % a.tiles_x; a.step_y = (a.nblk / a.tiles_x) % a.tiles_y; a.step_k = (a.nblk / a.tiles_x) / a.tiles_y;
   a.blk = v->d_blk; a.ctr = v->d_ctr;
-  launch_volume_integrate(a, s);
+  if (colour) {
+    VolIntegrateColourArgs ac;
+    ac.a = a;
+    ac.c.col = v->d_col; ac.c.pix = colour; ac.c.channels = v->cp.channels; ac.c.bgr = v->cp.bgr; ac.c.max_weight = v->cp.max_weight;
+    launch_volume_integrate_colour(ac, s);
+    launch_volume_sum(a, s);
+  } else {
+    launch_volume_integrate(a, s);
+  }
   HIP_OK(hipGetLastError());
   v->n_frames++;
   return volume_mark(v, s);
@@ -153,6 +173,60 @@ extern "C" int odo_volume_integrate_dev(odo_volume* v, const uint16_t* depth_dev
   if (!v || !depth_dev || !abs_pose_colmajor) return fail("odo_volume_integrate_dev: NULL arg");
   if (!pose_finite(abs_pose_colmajor)) return fail("odo_volume_integrate_dev: the pose has a non-finite entry (a frame whose Solve failed?)");
   return volume_integrate(v, depth_dev, abs_pose_colmajor, v->ctx->stream);
+}
+
+extern "C" int odo_volume_enable_colour(odo_volume* v, const odo_volume_colour_params* p) {
+  if (!v || !p) return fail("odo_volume_enable_colour: NULL arg");
+  if (p->channels != 3 && p->channels != 4) return fail("odo_volume_enable_colour: channels %d (3 or 4)", p->channels);
+  if (p->bgr != 0 && p->bgr != 1) return fail("odo_volume_enable_colour: bgr %d (0 or 1)", p->bgr);
+  if (p->max_weight < 1 || p->max_weight > 255) return fail("odo_volume_enable_colour: max_weight %d out of range (1 .. 255)", p->max_weight);
+  if (v->colour) return fail("odo_volume_enable_colour: the volume has a colour grid already");
+  if (v->attached) return fail("odo_volume_enable_colour: the volume is attached to a tracker (odo_tracker_attach_volume(t, NULL) first)");
+  HIP_OK(hipSetDevice(v->device));
+  uint32_t* col = nullptr;
+  if (hipMalloc((void**)&col, sizeof(uint32_t) * (size_t)v->n_vox) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail("odo_volume_enable_colour: device allocation failed (%ld voxels)", v->n_vox);
+  }
+  if (volume_order_on(v, v->own) || hipMemsetAsync(col, 0, sizeof(uint32_t) * (size_t)v->n_vox, v->own) != hipSuccess || volume_mark(v, v->own)) {
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(v->own);
+    (void)hipFree(col);
+    return fail("odo_volume_enable_colour: clearing the colour grid failed");
+  }
+  v->d_col = col; v->cp = *p; v->colour = 1;
+  return 0;
+}
+
+extern "C" int odo_volume_integrate_colour_dev(odo_volume* v, const uint16_t* depth_dev, const uint8_t* colour_dev,
+                                               const float abs_pose_colmajor[16]) {
+  if (!v || !depth_dev || !colour_dev || !abs_pose_colmajor) return fail("odo_volume_integrate_colour_dev: NULL arg");
+  if (!v->colour) return fail("odo_volume_integrate_colour_dev: the volume has no colour grid (odo_volume_enable_colour first)");
+  if (v->cp.channels == 4 && ((uintptr_t)colour_dev & 3)) return fail("odo_volume_integrate_colour_dev: misaligned colour frame (4 channels: 4-byte aligned)");
+  if (!pose_finite(abs_pose_colmajor))
+    return fail("odo_volume_integrate_colour_dev: the pose has a non-finite entry (a frame whose Solve failed?)");
+  return volume_integrate(v, depth_dev, abs_pose_colmajor, v->ctx->stream, colour_dev);
+}
+
+extern "C" int odo_volume_download_colour(odo_volume* v, uint8_t* rgbw) {
+  if (!v || !rgbw) return fail("odo_volume_download_colour: NULL arg");
+  if (!v->colour) return fail("odo_volume_download_colour: the volume has no colour grid (odo_volume_enable_colour first)");
+  if (volume_sync(v)) return -1;
+  HIP_OK(hipMemcpyAsync(rgbw, v->d_col, sizeof(uint32_t) * (size_t)v->n_vox, hipMemcpyDeviceToHost, v->own));
+  HIP_OK(hipStreamSynchronize(v->own));
+  return 0;
+}
+
+extern "C" int odo_volume_upload_colour(odo_volume* v, const uint8_t* rgbw) {
+  if (!v || !rgbw) return fail("odo_volume_upload_colour: NULL arg");
+  if (!v->colour) return fail("odo_volume_upload_colour: the volume has no colour grid (odo_volume_enable_colour first)");
+  if (v->attached) return fail("odo_volume_upload_colour: the volume is attached to a tracker (odo_tracker_attach_volume(t, NULL) first)");
+  HIP_OK(hipSetDevice(v->device));
+  if (volume_order_on(v, v->own)) return -1;
+  HIP_OK(hipMemcpyAsync(v->d_col, rgbw, sizeof(uint32_t) * (size_t)v->n_vox, hipMemcpyHostToDevice, v->own));
+  if (volume_mark(v, v->own)) return -1;
+  HIP_OK(hipStreamSynchronize(v->own));   // (the caller's buffer is the caller's again)
+  return 0;
 }
 
 extern "C" int odo_volume_sync(odo_volume* v) {
@@ -175,8 +249,23 @@ extern "C" int odo_volume_stats(odo_volume* v, long out[4]) {
   return 0;
 }
 
+// Grows one of the mesh's output buffers to `count` items of `item` bytes; *have = its capacity in items.
+static int volume_mesh_grow(void** p, long* have, long count, size_t item, const char* what) {
+  if (count <= *have) return 0;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr; *have = 0;
+  if (hipMalloc(p, item * (size_t)count) != hipSuccess) {
+    (void)hipGetLastError();
+    *p = nullptr;
+    return fail("odo_volume_mesh: device allocation failed (%ld %s)", count, what);
+  }
+  *have = count;
+  return 0;
+}
+
 // The three launches into the volume's own buffers; *n_points = points written, *n_dropped = points beyond capacity.
-static int volume_extract_dev(odo_volume* v, long capacity, long* n_points, long* n_dropped) {
+// with_colour: one launch more, the points' colours into d_rgba (skipped when no point is written).
+static int volume_extract_dev(odo_volume* v, long capacity, long* n_points, long* n_dropped, bool with_colour = false) {
   if (volume_sync(v)) return -1;
   const int nblk = (int)((v->n_vox + kVolExtBlock - 1) / kVolExtBlock);
   if (!v->d_cnt) {
@@ -205,6 +294,7 @@ static int volume_extract_dev(odo_volume* v, long capacity, long* n_points, long
     }
     v->ext_capacity = capacity;
   }
+  if (with_colour && volume_mesh_grow((void**)&v->d_rgba, &v->rgba_capacity, capacity, sizeof(uint32_t), "point colours")) return -1;
   VolExtractArgs a;
   memset(&a, 0, sizeof(a));
   a.g = volume_grid(v);
@@ -218,6 +308,12 @@ static int volume_extract_dev(odo_volume* v, long capacity, long* n_points, long
   HIP_OK(hipStreamSynchronize(v->own));
   *n_points = (long)c.ext_written;
   *n_dropped = (long)(c.ext_total - c.ext_written);
+  if (with_colour && c.ext_written > 0) {
+    VolExtractColourArgs ac;
+    ac.a = a; ac.col = v->d_col; ac.rgba = v->d_rgba;
+    launch_volume_extract_colour(ac, v->own);
+    HIP_OK(hipGetLastError());
+  }
   return 0;
 }
 
@@ -229,6 +325,24 @@ extern "C" int odo_volume_extract(odo_volume* v, long capacity, float* xyz0, flo
   if (n > 0) {
     HIP_OK(hipMemcpyAsync(xyz0, v->d_xyz0, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, v->own));
     HIP_OK(hipMemcpyAsync(nrmw, v->d_nrmw, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, v->own));
+    HIP_OK(hipStreamSynchronize(v->own));
+  }
+  *n_points = n;
+  if (n_dropped) *n_dropped = d;
+  return 0;
+}
+
+extern "C" int odo_volume_extract_colour(odo_volume* v, long capacity, float* xyz0, float* nrmw, uint8_t* rgba, long* n_points,
+                                         long* n_dropped) {
+  if (!v || !n_points || capacity < 0 || capacity > (1L << 28) || (capacity > 0 && (!xyz0 || !nrmw || !rgba)))
+    return fail("odo_volume_extract_colour: bad arg (capacity 0 .. 2^28, buffers for `capacity` points)");
+  if (!v->colour) return fail("odo_volume_extract_colour: the volume has no colour grid (odo_volume_enable_colour first)");
+  long n = 0, d = 0;
+  if (volume_extract_dev(v, capacity, &n, &d, true)) return -1;
+  if (n > 0) {
+    HIP_OK(hipMemcpyAsync(xyz0, v->d_xyz0, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, v->own));
+    HIP_OK(hipMemcpyAsync(nrmw, v->d_nrmw, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, v->own));
+    HIP_OK(hipMemcpyAsync(rgba, v->d_rgba, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, v->own));
     HIP_OK(hipStreamSynchronize(v->own));
   }
   *n_points = n;
@@ -264,25 +378,9 @@ extern "C" int odo_volume_upload(odo_volume* v, const int16_t* q, const uint16_t
   return 0;
 }
 
-// Grows one of the mesh's output buffers to `count` items of `item` bytes; *have = its capacity in items.
-static int volume_mesh_grow(void** p, long* have, long count, size_t item, const char* what) {
-  if (count <= *have) return 0;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr; *have = 0;
-  if (hipMalloc(p, item * (size_t)count) != hipSuccess) {
-    (void)hipGetLastError();
-    *p = nullptr;
-    return fail("odo_volume_mesh: device allocation failed (%ld %s)", count, what);
-  }
-  *have = count;
-  return 0;
-}
-
-extern "C" int odo_volume_mesh(odo_volume* v, long vertex_capacity, long triangle_capacity, float* xyz0, float* nrmw, int32_t* tri,
-                               long counts[4]) {
-  if (!v || !counts || vertex_capacity < 0 || vertex_capacity > (1L << 28) || triangle_capacity < 0 || triangle_capacity > (1L << 28) ||
-      (vertex_capacity > 0 && (!xyz0 || !nrmw)) || (triangle_capacity > 0 && !tri))
-    return fail("odo_volume_mesh: bad arg (capacities 0 .. 2^28, buffers for `vertex_capacity` vertices and `triangle_capacity` triangles)");
+// odo_volume_mesh and, with_colour, odo_volume_mesh_colour (one launch more: the vertices' colours, skipped when no vertex is written).
+static int volume_mesh(odo_volume* v, long vertex_capacity, long triangle_capacity, float* xyz0, float* nrmw, uint8_t* rgba, int32_t* tri,
+                       long counts[4], bool with_colour) {
   if (volume_sync(v)) return -1;
   const int nblk = (int)((v->n_vox + kMeshBlock - 1) / kMeshBlock);
   if (!v->d_mesh_ctr) {
@@ -305,6 +403,7 @@ extern "C" int odo_volume_mesh(odo_volume* v, long vertex_capacity, long triangl
   if (volume_mesh_grow((void**)&v->d_mesh_nrmw, &have, vertex_capacity, sizeof(float4), "vertices")) { v->mesh_vertex_capacity = 0; return -1; }
   v->mesh_vertex_capacity = have;
   if (volume_mesh_grow((void**)&v->d_mesh_tri, &v->mesh_triangle_capacity, triangle_capacity, 3 * sizeof(int32_t), "triangles")) return -1;
+  if (with_colour && volume_mesh_grow((void**)&v->d_mesh_rgba, &v->mesh_rgba_capacity, vertex_capacity, sizeof(uint32_t), "vertex colours")) return -1;
   VolMeshArgs a;
   memset(&a, 0, sizeof(a));
   a.g = volume_grid(v);
@@ -321,6 +420,13 @@ extern "C" int odo_volume_mesh(odo_volume* v, long vertex_capacity, long triangl
       return fail("odo_volume_mesh: %llu vertices: an index does not fit an int32 (totals are returned with both capacities 0)", c.v_total);
     launch_volume_mesh_emit(a, c.t_written > 0, v->own);
     HIP_OK(hipGetLastError());
+    if (with_colour && c.v_written > 0) {
+      VolMeshColourArgs ac;
+      ac.a = a; ac.col = v->d_col; ac.rgba = v->d_mesh_rgba;
+      launch_volume_mesh_colour(ac, v->own);
+      HIP_OK(hipGetLastError());
+      HIP_OK(hipMemcpyAsync(rgba, v->d_mesh_rgba, sizeof(uint32_t) * (size_t)c.v_written, hipMemcpyDeviceToHost, v->own));
+    }
     if (c.v_written > 0) {
       HIP_OK(hipMemcpyAsync(xyz0, v->d_mesh_xyz0, sizeof(float4) * (size_t)c.v_written, hipMemcpyDeviceToHost, v->own));
       HIP_OK(hipMemcpyAsync(nrmw, v->d_mesh_nrmw, sizeof(float4) * (size_t)c.v_written, hipMemcpyDeviceToHost, v->own));
@@ -331,6 +437,23 @@ extern "C" int odo_volume_mesh(odo_volume* v, long vertex_capacity, long triangl
   counts[0] = (long)c.v_written; counts[1] = (long)(c.v_total - c.v_written);
   counts[2] = (long)c.t_written; counts[3] = (long)(c.t_total - c.t_written);
   return 0;
+}
+
+extern "C" int odo_volume_mesh(odo_volume* v, long vertex_capacity, long triangle_capacity, float* xyz0, float* nrmw, int32_t* tri,
+                               long counts[4]) {
+  if (!v || !counts || vertex_capacity < 0 || vertex_capacity > (1L << 28) || triangle_capacity < 0 || triangle_capacity > (1L << 28) ||
+      (vertex_capacity > 0 && (!xyz0 || !nrmw)) || (triangle_capacity > 0 && !tri))
+    return fail("odo_volume_mesh: bad arg (capacities 0 .. 2^28, buffers for `vertex_capacity` vertices and `triangle_capacity` triangles)");
+  return volume_mesh(v, vertex_capacity, triangle_capacity, xyz0, nrmw, nullptr, tri, counts, false);
+}
+
+extern "C" int odo_volume_mesh_colour(odo_volume* v, long vertex_capacity, long triangle_capacity, float* xyz0, float* nrmw, uint8_t* rgba,
+                                      int32_t* tri, long counts[4]) {
+  if (!v || !counts || vertex_capacity < 0 || vertex_capacity > (1L << 28) || triangle_capacity < 0 || triangle_capacity > (1L << 28) ||
+      (vertex_capacity > 0 && (!xyz0 || !nrmw || !rgba)) || (triangle_capacity > 0 && !tri))
+    return fail("odo_volume_mesh_colour: bad arg (capacities 0 .. 2^28, buffers for `vertex_capacity` vertices and `triangle_capacity` triangles)");
+  if (!v->colour) return fail("odo_volume_mesh_colour: the volume has no colour grid (odo_volume_enable_colour first)");
+  return volume_mesh(v, vertex_capacity, triangle_capacity, xyz0, nrmw, rgba, tri, counts, true);
 }
 
 extern "C" int odo_volume_clear(odo_volume* v) {

@@ -96,6 +96,10 @@ void launch_volume_integrate(const VolIntegrateArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(volume_sum_kernel, dim3(1), dim3(kVolBlock), 0, s, a);
 }
 
+void launch_volume_sum(const VolIntegrateArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(volume_sum_kernel, dim3(1), dim3(kVolBlock), 0, s, a);
+}
+
 // ---- extraction ----------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void vol_ijk(const VolGrid& g, int v, int* i, int* j, int* k) {
   const int row = v / g.nx;

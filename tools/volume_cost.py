@@ -3,25 +3,32 @@
   kernels   the workload for a kernel trace: the first frames of the TUM-shaped RGB-D drive integrated with their true poses into the
             pinned grid (240 x 128 x 200 voxels of 4 cm, 24.6 MB: resident in the Infinity Cache) and into a 512 x 256 x 512 grid of
             the same voxel size (268 MB: it is not), each followed by extractions and meshes (api.TsdfVolume.mesh(): count + scan
-            for the totals, then count + scan + vertices + triangles with exact capacities). Run it under the profiler, in a run of its own
-            (no counters in that run), then summarise:
+            for the totals, then count + scan + vertices + triangles with exact capacities). Each grid is then done once more as a
+            COLOURED volume (odo_volume_enable_colour): the same frames through integrate(colour=...) — volume_integrate_colour_kernel
+            beside volume_integrate_kernel in one trace — followed by coloured extractions and meshes (one colour launch behind each).
+            Run it under the profiler, in a run of its own (no counters in that run), then summarise:
               rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/volume_cost.py kernels
               python tools/volume_cost.py summary <dir>
             It prints one JSON line per grid with the counters the algorithmic bytes are made of; --json FILE keeps them for
             `summary` (without it `summary` prints the times alone).
   summary   medians of the volume's kernels per grid out of the trace, with the algorithmic bytes
               integrate = 8 B per updated voxel (load + store) + 2 B per depth pixel
+              coloured  = the same + 8 B per in-band voxel (colour word load + store) + 3 B per in-band voxel (its pixel)
+              colours   = extraction: 4 B per voxel (the ballots aside) + 20 B per point (two voxel words, two colour words, one
+                          store); mesh: 5 B per voxel + 20 B per vertex
               extract   = 4 B per voxel + 32 B per point
               mesh      = count 4 + 1 B per voxel; vertices 1 + 4 B per voxel + 32 B per vertex; triangles 4 B per voxel + 12 B
                           per triangle
             and their share of the achievable HBM bandwidth (6.3 TB/s).
   track     tools/rgbd_cost.py's tracked loop over the TUM-shaped drive (next frame announced with its depth frame, back and forth
             over the drive) with no volume, the pinned grid and the large grid attached, runs interleaved mode by mode: frames/s
-            (median, spread), the tracker's host timing, Solves redone on the step launches and depth jobs redone.
+            (median, spread), the tracker's host timing, Solves redone on the step launches and depth jobs redone. Mode `coloured` is
+            the pinned grid with a colour grid, every frame's colour named with odo_tracker_frame_colour (the price of colour:
+            --modes coloured,pinned,none alternating in one call).
 
   python tools/volume_cost.py kernels [--frames 10] [--extractions 3] [--json FILE]
   python tools/volume_cost.py summary DIR [--json FILE]
-  python tools/volume_cost.py track [--runs 3] [--steps 200] [--warmup 20] [--frames 100] [--modes none,pinned,large]
+  python tools/volume_cost.py track [--runs 3] [--steps 200] [--warmup 20] [--frames 100] [--modes none,pinned,large[,coloured]]
 
 A build without the volume is measured with tools/rgbd_cost.py --modes tum (the same drive and loop as `track`'s mode `none`).
 """
@@ -45,10 +52,13 @@ GRIDS = dict(pinned=dict(dims=(240, 128, 200), origin=(-4.8, -3.3, 0.4)),
              large=dict(dims=(512, 256, 512), origin=(-10.24, -5.86, 0.4)))   # the same corridor, the same voxel size
 
 
-def make_volume(owner, grid, size, K):
+def make_volume(owner, grid, size, K, colour=False):
     from odometry_amd import api
-    g = GRIDS[grid]
-    return api.TsdfVolume(owner, g["dims"], VS, g["origin"], MU, MAX_DEPTH, 65535, size, K, 1000.0)
+    g = GRIDS["pinned" if grid == "coloured" else grid]
+    vol = api.TsdfVolume(owner, g["dims"], VS, g["origin"], MU, MAX_DEPTH, 65535, size, K, 1000.0)
+    if colour or grid == "coloured":
+        vol.enable_colour(3, False, 255)
+    return vol
 
 
 def kernels(args):
@@ -57,32 +67,39 @@ def kernels(args):
     K = (seq["K"]["f0"], seq["K"]["cx0"], seq["K"]["cy0"])
     ctx = api.Context(0)
     dev = [ctx.upload(d) for d in seq["depth"]]
+    cdev = [ctx.upload(synth.colour_from_gray(g, 3, False, tint_seed=1)) for g in seq["gray"]]
     out = {}
     for grid in ("pinned", "large"):
-        vol = make_volume(ctx, grid, (synth.TUM_ROWS, synth.TUM_COLS), K)
-        upd = []
-        for d, A in zip(dev, seq["poses"]):
-            vol.integrate(d, A)
-            upd.append(vol.stats()["updated"])
-        t0 = time.perf_counter()
-        for d, A in zip(dev, seq["poses"]):    # once more without a host wait between the frames (weights differ, the work does not)
-            vol.integrate(d, A)
-        vol.sync()
-        host_us = 1e6 * (time.perf_counter() - t0) / len(dev)
-        n = 0
-        for _ in range(args.extractions):
-            n = len(vol.extract(1 << 21)[0])
-        nv = nt = 0
-        for _ in range(args.extractions):
-            xyz0, _, tri = vol.mesh()
-            nv, nt = len(xyz0), len(tri)
-        nx, ny, nz = GRIDS[grid]["dims"]
-        out[grid] = dict(voxels=nx * ny * nz, updated_per_frame=int(np.median(upd)), points=n, vertices=nv, triangles=nt,
-                         pixels=synth.TUM_ROWS * synth.TUM_COLS,
-                         integrate_host_us_back_to_back=round(host_us, 1))
-        print(json.dumps(dict(grid=grid, **out[grid])), flush=True)
-        vol.close()
-    for d in dev:
+        for coloured in (False, True):    # the plain leg, then the same grid and frames as a coloured volume
+            vol = make_volume(ctx, grid, (synth.TUM_ROWS, synth.TUM_COLS), K, colour=coloured)
+            upd, band = [], []
+            for d, c, A in zip(dev, cdev, seq["poses"]):
+                vol.integrate(d, A, colour=c if coloured else None)
+                st = vol.stats()
+                upd.append(st["updated"])
+                band.append(st["in_band"])
+            t0 = time.perf_counter()
+            for d, c, A in zip(dev, cdev, seq["poses"]):    # once more without a host wait between the frames (weights differ, the work does not)
+                vol.integrate(d, A, colour=c if coloured else None)
+            vol.sync()
+            host_us = 1e6 * (time.perf_counter() - t0) / len(dev)
+            n = 0
+            for _ in range(args.extractions):
+                n = len(vol.extract(1 << 21, colour=coloured)[0])
+            nv = nt = 0
+            for _ in range(args.extractions):
+                got = vol.mesh(colour=coloured)
+                nv, nt = len(got[0]), len(got[2])
+            nx, ny, nz = GRIDS[grid]["dims"]
+            row = dict(voxels=nx * ny * nz, updated_per_frame=int(np.median(upd)), in_band_per_frame=int(np.median(band)), points=n,
+                       vertices=nv, triangles=nt, pixels=synth.TUM_ROWS * synth.TUM_COLS, integrate_host_us_back_to_back=round(host_us, 1))
+            if coloured:
+                out[grid]["coloured_integrate_host_us_back_to_back"] = row["integrate_host_us_back_to_back"]
+            else:
+                out[grid] = row
+            print(json.dumps(dict(grid=grid, coloured=coloured, **row)), flush=True)
+            vol.close()
+    for d in dev + cdev:
         ctx.free(d)
     ctx.close()
     if args.json:
@@ -112,6 +129,12 @@ def summary(args):
                 b = None
                 if name == "volume_integrate_kernel":
                     b = 8 * w["updated_per_frame"] + 2 * w["pixels"]
+                elif name == "volume_integrate_colour_kernel":
+                    b = 8 * w["updated_per_frame"] + 2 * w["pixels"] + 11 * w.get("in_band_per_frame", 0)
+                elif name == "volume_extract_colour_kernel":
+                    b = 4 * w["voxels"] + 20 * w["points"]
+                elif name == "volume_mesh_colour_kernel" and "vertices" in w:
+                    b = 5 * w["voxels"] + 20 * w["vertices"]
                 elif name == "volume_count_kernel":
                     b = 4 * w["voxels"]
                 elif name == "volume_scatter_kernel":
@@ -130,12 +153,13 @@ def summary(args):
 
 def track(args):
     import rgbd_cost
-    from odometry_amd import api
+    from odometry_amd import api, synth
     modes = args.modes.split(",")
     d = rgbd_cost.render(args.frames, "tum")
     trk = api.RgbdTracker(0, depth_scale=1000.0, max_depth_step=0.05, rows=d["rows"], cols=d["cols"], K=d["K"])
     dev = [(trk.upload_frame(g), trk.upload_depth(r)) for g, r in zip(d["gray"], d["depth"])]
     vols = {m: make_volume(trk, m, (d["rows"], d["cols"]), d["K"]) for m in modes if m != "none"}
+    cdev = [trk.upload_colour(synth.colour_from_gray(g, 3, False, tint_seed=1)) for g in d["gray"]] if "coloured" in modes else None
     T = np.zeros(16, np.float32)
     A = np.zeros(16, np.float32)
     res = {m: [] for m in modes}
@@ -151,6 +175,9 @@ def track(args):
             trk.attach_volume(vol)
             _, djob0 = trk.depth_persistent_stats()
             _, redo0 = trk.persistent_stats()
+            coloured = mode == "coloured"
+            if coloured:
+                trk.frame_colour(cdev[order[0]])
             trk.init(*dev[order[0]])
             kf = 0
             t0 = None
@@ -161,6 +188,8 @@ def track(args):
                     t0 = time.perf_counter()
                 if k + 1 <= last and k + 1 != args.warmup + 1:
                     trk.hint_next(*dev[order[k + 1]])
+                if coloured:
+                    trk.frame_colour(cdev[order[k]])
                 kf += trk.track_into(*dev[order[k]], T, A)
             trk._sync()            # (waits for the pending integrations as well)
             fps = args.steps / (time.perf_counter() - t0)
@@ -171,7 +200,7 @@ def track(args):
             st = vol.stats() if vol is not None else {}
             print(json.dumps(dict(run=run, mode=mode, fps=round(fps, 1), keyframes=kf + 1, lm_persistent_groups=groups,
                                   solves_redone=redo1 - redo0, depth_jobs_redone=djob1 - djob0, frames_integrated=st.get("frames"),
-                                  updated_last=st.get("updated"), **{k_: round(v, 1) for k_, v in tm.items()})), flush=True)
+                                  updated_last=st.get("updated"), in_band_last=st.get("in_band"), **{k_: round(v, 1) for k_, v in tm.items()})), flush=True)
     trk.attach_volume(None)
     print(json.dumps(dict(summary=True, **{m: dict(median_fps=round(float(np.median(res[m])), 1),
                                                    spread=[round(min(res[m]), 1), round(max(res[m]), 1)]) for m in modes})))
