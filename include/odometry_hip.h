@@ -673,6 +673,53 @@ int odo_volume_mesh_colour(odo_volume* v, long vertex_capacity, long triangle_ca
  * attached. Poses, masks, keyframe flags and motion scores are bit-identical with and without it. */
 int odo_tracker_frame_colour(odo_tracker* t, const uint8_t* colour_dev);
 
+/* ---- Ray-cast of the TSDF volume: the model seen from a camera, as depth, normal and colour frames -----------------------------------
+ * A pure function of the grid, a camera-to-world pose and the parameters below; the output frame is independent of the volume's own
+ * rows / cols / K. All floating point is fp32, one rounding per operation (DESIGN.md section 9.7 holds the same table).
+ * Host part (fp64 from the fp32 entries, each result rounded to fp32 once): e_c = (t_c - origin_c) / vs - 0.5 per axis, the camera
+ * centre in voxel-index coordinates, in which voxel centres sit at integers; G_rc = R_rc / vs for the nine rotation entries.
+ * Per pixel (x, y): dx = ((float)x - cx) / f, dy = ((float)y - cy) / f; g_r = (G_r0 dx + G_r1 dy) + G_r2 for r = x, y, z. The
+ * camera-frame direction is (dx, dy, 1), so the ray parameter t is depth along the optical axis: the quantity of the depth frames
+ * and of the projective signed distance.
+ * Sample n = 0 .. n_steps - 1: t_n = t_min + (float)n * step (not accumulated); p_c = e_c + t_n * g_c; b_c = floorf(p_c). The sample
+ * is valid only if b_c >= 0.0f && b_c <= (float)(dim_c - 2) on every axis — compared as floats before any conversion, NaN and inf
+ * fail — and all eight corners b + d, d in {0, 1}^3, have w > 0 (the mesh's live cell). fr_c = p_c - b_c.
+ * Interpolation, with Q = (float)q of the corners c_xyz:  l_yz = c_0yz + fr_x * (c_1yz - c_0yz);  m_z = l_0z + fr_y * (l_1z - l_0z);
+ * F = m_0 + fr_z * (m_1 - m_0).
+ * End of a ray. The ray ends at its first valid sample with F <= 0.0f. It is a hit iff sample n - 1 exists, is valid and has
+ * F_prev > 0.0f; then z = t_prev + (F_prev / (F_prev - F)) * (t_n - t_prev). Every other ending, and a ray that runs out of samples,
+ * gives no hit; an invalid sample between a positive and a non-positive one also gives no hit.
+ * Outputs per pixel, row-major:
+ *   depth  float32: z, or 0 for no hit.
+ *   raw    uint16: (uint16)fminf(65535.0f, rintf(z * depth_scale)) with the volume's depth_scale, or 0 for no hit: a frame that
+ *          odo_volume_integrate_dev and the RGB-D tracker accept as it is.
+ *   nrmw   float[4]. On a hit the sample arithmetic is evaluated once more at t = z. If that cell is valid, the normal is the gradient
+ *          of the interpolant in it: d_yz = c_1yz - c_0yz; gx_z = d_0z + fr_y * (d_1z - d_0z); gx = gx_0 + fr_z * (gx_1 - gx_0);
+ *          gy_z = l_1z - l_0z; gy = gy_0 + fr_z * (gy_1 - gy_0); gz = m_1 - m_0; len = sqrtf((gx gx + gy gy) + gz gz); the output is
+ *          g / len if len > 0. Otherwise, and without a hit, (0, 0, 0). World axes, as the extraction's normals, pointing into observed
+ *          free space. The fourth component is (float) the smallest w of the eight corners where a normal is written, else 0.
+ *   rgba   uint8[4], volumes with colour only: the colour word of voxel floorf(p_c + 0.5f) of that same cell evaluation (one of the
+ *          cell's corners): (R, G, B, 255) if the cell is valid and that voxel's wc > 0, else four zeros.
+ * Validation, all of it before any device work (-1, nothing enqueued, every counter unchanged): rows and cols 1 .. 4096; f finite
+ * > 0; cx, cy finite; t_min finite >= 0; step finite > 0; n_steps 1 .. 4096; every pose entry finite; device outputs aligned to
+ * their element (4, 2, 16, 4 bytes). */
+typedef struct {
+  int rows, cols;          /* the output frame, 1 .. 4096 each */
+  float f, cx, cy;         /* its pinhole: focal length in pixels (finite > 0) and principal point (finite) */
+  float t_min, step;       /* first sample depth (finite >= 0) and sample distance (finite > 0), metres along the optical axis */
+  int n_steps;             /* samples per ray, 1 .. 4096 */
+} odo_raycast_params;
+/* One launch, a thread per pixel, no atomics, asynchronous on the volume's own stream behind everything that changed the volume so
+ * far; odo_volume_sync covers it, and a later integration on any stream is ordered behind it. Any output may be NULL (all four: nothing
+ * is enqueued); rgba_dev is refused on a volume without colour. Neither grid and no counter is modified. Legal while the volume is
+ * attached to a tracker: ordered behind the integrations enqueued so far, as odo_volume_mesh is. */
+int odo_volume_raycast_dev(odo_volume* v, const odo_raycast_params* p, const float abs_pose_colmajor[16], float* depth_dev,
+                           uint16_t* raw_dev, float* nrmw_dev, uint8_t* rgba_dev);
+/* The same with host outputs, through frames on the device that the volume owns (sized on first use, grown on demand, released with
+ * the volume); the call waits and copies. */
+int odo_volume_raycast(odo_volume* v, const odo_raycast_params* p, const float abs_pose_colmajor[16], float* depth, uint16_t* raw,
+                       float* nrmw, uint8_t* rgba);
+
 /* ---- RGB-D front end: raw sensor frames -> the RGB-D tracker's inputs ----------------------------------------------------------
  * A sensor delivers interleaved 8-bit colour and a uint16 depth frame in the DEPTH imager's pixel grid (its own intrinsics, often
  * its own resolution, centimetres beside the colour imager); odo_tracker_*_rgbd take an fp32 grey image and a uint16 depth frame in

@@ -53,6 +53,11 @@ class VolumeColourParams(C.Structure):
     _fields_ = [("channels", C.c_int), ("bgr", C.c_int), ("max_weight", C.c_int)]
 
 
+class RaycastParams(C.Structure):
+    _fields_ = [("rows", C.c_int), ("cols", C.c_int), ("f", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("t_min", C.c_float), ("step", C.c_float), ("n_steps", C.c_int)]
+
+
 _fp = C.POINTER(C.c_float)
 _dp = C.POINTER(C.c_double)
 _u8p = C.POINTER(C.c_uint8)
@@ -233,6 +238,8 @@ SIGNATURES = {
     "odo_volume_mesh_colour": (C.c_int, [_vp, C.c_long, C.c_long, _fp, _fp, _u8p, C.POINTER(C.c_int32), C.POINTER(C.c_long)]),
     "odo_tracker_frame_colour": (C.c_int, [_vp, _vp]),
     "odo_rgbd_frontend_colour": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
+    "odo_volume_raycast_dev": (C.c_int, [_vp, C.POINTER(RaycastParams), _fp, _vp, _vp, _vp, _vp]),
+    "odo_volume_raycast": (C.c_int, [_vp, C.POINTER(RaycastParams), _fp, _fp, C.POINTER(C.c_uint16), _fp, _u8p]),
 }
 
 _lib = None

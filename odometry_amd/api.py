@@ -1058,6 +1058,38 @@ class TsdfVolume:
             out = xyz0[:o[0]].copy(), nrmw[:o[0]].copy(), tri[:o[2]].copy()
         return out + (tuple(o),) if with_counts else out
 
+    def raycast_params(self, size=None, K=None, t_min=0.0, step=None, n_steps=None):
+        """The odo_raycast_params of raycast(): the volume's own size and K, step = mu / 2 and enough samples to reach
+        max_depth + mu unless given."""
+        p = self.params
+        rows, cols = (p.rows, p.cols) if size is None else size
+        f, cx, cy = (p.K.f0, p.K.cx0, p.K.cy0) if K is None else K
+        step = p.mu / 2 if step is None else step
+        if n_steps is None:
+            n_steps = min(4096, max(1, int(np.ceil((p.max_depth + p.mu - t_min) / step)) + 1))
+        return L.RaycastParams(int(rows), int(cols), f, cx, cy, t_min, step, int(n_steps))
+
+    def raycast(self, abs_pose, size=None, K=None, t_min=0.0, step=None, n_steps=None, raw=False, colour=False):
+        """The volume seen from the camera-to-world pose abs_pose (4x4): depth (rows, cols) float32, metres along the optical axis, 0 =
+        no surface; normals (rows, cols, 4) float32 nx, ny, nz in world axes and the smallest weight of the cell; with raw=True also
+        the depth as a uint16 frame in the volume's depth_scale (what integrate and RgbdTracker take); with colour=True also
+        (rows, cols, 4) uint8 R, G, B, A. size = (rows, cols) and K = (f, cx, cy) of the view: the volume's own unless given; rays
+        are sampled at t_min + n * step, n < n_steps."""
+        rp = self.raycast_params(size, K, t_min, step, n_steps)
+        depth = np.zeros((rp.rows, rp.cols), np.float32)
+        nrmw = np.zeros((rp.rows, rp.cols, 4), np.float32)
+        raw_out = np.zeros((rp.rows, rp.cols), np.uint16) if raw else None
+        rgba = np.zeros((rp.rows, rp.cols, 4), np.uint8) if colour else None
+        L.check(self.lib.odo_volume_raycast(self.h, C.byref(rp), _fp(_colmajor(abs_pose)), _fp(depth),
+                                            raw_out.ctypes.data_as(C.POINTER(C.c_uint16)) if raw else None, _fp(nrmw),
+                                            rgba.ctypes.data_as(L._u8p) if colour else None), "odo_volume_raycast")
+        out = (depth, nrmw)
+        if raw:
+            out += (raw_out,)
+        if colour:
+            out += (rgba,)
+        return out
+
     def stats(self):
         o = (C.c_long * 4)()
         L.check(self.lib.odo_volume_stats(self.h, o), "odo_volume_stats")

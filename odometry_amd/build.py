@@ -25,7 +25,9 @@ SRC_FRONTEND = os.path.join(_HERE, "csrc", "rgbd_frontend_kernels.hip")   # the 
 SRC_VOLUME = os.path.join(_HERE, "csrc", "volume_kernels.hip")   # the TSDF volume's kernels (volume.hip.h): the main unit's scheduler
 SRC_VOLUME_MESH = os.path.join(_HERE, "csrc", "volume_mesh_kernels.hip")   # the volume's mesh kernels (volume_mesh.hip.h): the main unit's scheduler
 SRC_VOLUME_COLOUR = os.path.join(_HERE, "csrc", "volume_colour_kernels.hip")   # the volume's colour kernels (volume_colour.hip.h): the main unit's scheduler
-DEPS = [SRC, SRC_DENSE, SRC_CHAIN, SRC_MAP, SRC_RGBD, SRC_FRONTEND, SRC_VOLUME, SRC_VOLUME_MESH, SRC_VOLUME_COLOUR, os.path.join(_HERE, "csrc", "volume.hip.h"),
+SRC_VOLUME_RAYCAST = os.path.join(_HERE, "csrc", "volume_raycast_kernels.hip")   # the volume's ray-cast kernel (volume_raycast.hip.h): the main unit's scheduler
+DEPS = [SRC, SRC_DENSE, SRC_CHAIN, SRC_MAP, SRC_RGBD, SRC_FRONTEND, SRC_VOLUME, SRC_VOLUME_MESH, SRC_VOLUME_COLOUR, SRC_VOLUME_RAYCAST, os.path.join(_HERE, "csrc", "volume.hip.h"),
+        os.path.join(_HERE, "csrc", "volume_raycast.hip.h"), os.path.join(_HERE, "csrc", "volume_raycast_math.h"),
         os.path.join(_HERE, "csrc", "volume_colour.hip.h"), os.path.join(_HERE, "csrc", "volume_colour_math.h"),
         os.path.join(_HERE, "csrc", "volume_mesh.hip.h"), os.path.join(_HERE, "csrc", "volume_mesh_table.h"),
         os.path.join(_HERE, "csrc", "volume_api.hip.h"), os.path.join(_HERE, "csrc", "rgbd_frontend.hip.h"),
@@ -85,9 +87,9 @@ def build(force=False, verbose=False, stamps=False):
     os.makedirs(os.path.dirname(lib), exist_ok=True)
     objdir = os.path.join(os.path.dirname(lib), "obj_stamps" if stamps else "obj")
     os.makedirs(objdir, exist_ok=True)
-    o_main, o_dense, o_batch, o_map, o_rgbd, o_fe, o_vol, o_mesh, o_col = (os.path.join(objdir, n) for n in (
+    o_main, o_dense, o_batch, o_map, o_rgbd, o_fe, o_vol, o_mesh, o_col, o_ray = (os.path.join(objdir, n) for n in (
         "odometry_hip.o", "dense_kernels.o", "lm_chain_kernels.o", "map_kernels.o", "rgbd_kernels.o", "rgbd_frontend_kernels.o",
-        "volume_kernels.o", "volume_mesh_kernels.o", "volume_colour_kernels.o"))
+        "volume_kernels.o", "volume_mesh_kernels.o", "volume_colour_kernels.o", "volume_raycast_kernels.o"))
     cmds = [[HIPCC] + _flags_for(SRC, flags) + ["-c", "-o", o_main, SRC],
             [HIPCC] + _flags_for(SRC_DENSE, flags) + ["-c", "-o", o_dense, SRC_DENSE],
             [HIPCC] + _flags_for(SRC_CHAIN, flags) + ["-c", "-o", o_batch, SRC_CHAIN],
@@ -97,18 +99,19 @@ def build(force=False, verbose=False, stamps=False):
             [HIPCC] + _flags_for(SRC_VOLUME, flags) + ["-c", "-o", o_vol, SRC_VOLUME],
             [HIPCC] + _flags_for(SRC_VOLUME_MESH, flags) + ["-c", "-o", o_mesh, SRC_VOLUME_MESH],
             [HIPCC] + _flags_for(SRC_VOLUME_COLOUR, flags) + ["-c", "-o", o_col, SRC_VOLUME_COLOUR],
-            [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, o_main, o_dense, o_batch, o_map, o_rgbd, o_fe, o_vol, o_mesh, o_col]]
+            [HIPCC] + _flags_for(SRC_VOLUME_RAYCAST, flags) + ["-c", "-o", o_ray, SRC_VOLUME_RAYCAST],
+            [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, o_main, o_dense, o_batch, o_map, o_rgbd, o_fe, o_vol, o_mesh, o_col, o_ray]]
     procs = []
-    for cmd in cmds[:9]:   # the nine translation units compile side by side
+    for cmd in cmds[:-1]:   # the ten translation units compile side by side
         if verbose:
             print(" ".join(cmd))
         procs.append(subprocess.Popen(cmd))
-    for pr, cmd in zip(procs, cmds[:9]):
+    for pr, cmd in zip(procs, cmds[:-1]):
         if pr.wait() != 0:
             raise subprocess.CalledProcessError(pr.returncode, cmd)
     if verbose:
-        print(" ".join(cmds[9]))
-    subprocess.check_call(cmds[9])
+        print(" ".join(cmds[-1]))
+    subprocess.check_call(cmds[-1])
     return lib
 
 

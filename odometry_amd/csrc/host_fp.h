@@ -147,4 +147,15 @@ inline void invert_rigid(const float* A, float* M) {
   M[15] = 1.0f;
 }
 
+// The ray-cast's frame (volume_api.hip.h; include/odometry_hip.h, odo_volume_raycast_dev) of a camera-to-world pose A = [R | t]
+// (column-major fp32), the grid's origin and voxel size vs: e_c = (t_c - origin_c) / vs - 0.5, the camera centre in voxel-index
+// coordinates (voxel centres at integers), and G_rc = R_rc / vs, row r column c at G[3 r + c]. fp64 from the fp32 entries, each result
+// rounded to fp32 once.
+inline void raycast_frame(const float* A, const float* origin, float vs, float* e, float* G) {
+  for (int r = 0; r < 3; r++) {
+    e[r] = (float)(((double)A[12 + r] - (double)origin[r]) / (double)vs - 0.5);
+    for (int c = 0; c < 3; c++) G[3 * r + c] = (float)((double)A[c * 4 + r] / (double)vs);
+  }
+}
+
 }  // namespace hostfp

@@ -6,6 +6,7 @@
 #include "volume.hip.h"
 #include "volume_mesh.hip.h"
 #include "volume_colour.hip.h"
+#include "volume_raycast.hip.h"
 
 struct odo_volume {
   odo_ctx* ctx;                 // standalone integrations (odo_volume_integrate_dev) run on its stream
@@ -40,12 +41,18 @@ struct odo_volume {
   uint32_t* d_col;              // [n_vox]: {R, G, B, wc}
   uint32_t *d_rgba, *d_mesh_rgba;   // the colours of the extraction's points / the mesh's vertices, grown on demand
   long rgba_capacity, mesh_rgba_capacity;
+  // ray-cast (odo_volume_raycast's frames on the device: sized on first use, grown on demand)
+  float* d_ray_depth;
+  uint16_t* d_ray_raw;
+  float4* d_ray_nrmw;
+  uint32_t* d_ray_rgba;
+  long ray_capacity, ray_rgba_capacity;   // pixels
 };
 
 static int volume_release(odo_volume* v) {
   void* ps[] = {v->d_vox, v->d_blk, v->d_ctr, v->d_wave, v->d_off, v->d_cnt, v->d_xyz0, v->d_nrmw,
                 v->d_mesh_mask, v->d_mesh_base, v->d_mesh_cnt, v->d_mesh_off, v->d_mesh_ctr, v->d_mesh_xyz0, v->d_mesh_nrmw, v->d_mesh_tri,
-                v->d_col, v->d_rgba, v->d_mesh_rgba};
+                v->d_col, v->d_rgba, v->d_mesh_rgba, v->d_ray_depth, v->d_ray_raw, v->d_ray_nrmw, v->d_ray_rgba};
   for (void* p : ps) if (p) (void)hipFree(p);
   if (v->ev_last) (void)hipEventDestroy(v->ev_last);
   if (v->own) (void)hipStreamDestroy(v->own);
@@ -105,6 +112,8 @@ extern "C" int odo_volume_create(odo_ctx* ctx, const odo_volume_params* p, odo_v
   v->n_frames = 0; v->attached = nullptr;
   v->colour = 0; memset(&v->cp, 0, sizeof(v->cp)); v->d_col = nullptr; v->d_rgba = v->d_mesh_rgba = nullptr;
   v->rgba_capacity = v->mesh_rgba_capacity = 0;
+  v->d_ray_depth = nullptr; v->d_ray_raw = nullptr; v->d_ray_nrmw = nullptr; v->d_ray_rgba = nullptr;
+  v->ray_capacity = v->ray_rgba_capacity = 0;
   bool ok = hipStreamCreateWithFlags(&v->own, hipStreamNonBlocking) == hipSuccess &&
             hipEventCreateWithFlags(&v->ev_last, hipEventDisableTiming) == hipSuccess &&
             hipMalloc((void**)&v->d_vox, sizeof(uint32_t) * (size_t)v->n_vox) == hipSuccess &&
@@ -454,6 +463,90 @@ extern "C" int odo_volume_mesh_colour(odo_volume* v, long vertex_capacity, long 
     return fail("odo_volume_mesh_colour: bad arg (capacities 0 .. 2^28, buffers for `vertex_capacity` vertices and `triangle_capacity` triangles)");
   if (!v->colour) return fail("odo_volume_mesh_colour: the volume has no colour grid (odo_volume_enable_colour first)");
   return volume_mesh(v, vertex_capacity, triangle_capacity, xyz0, nrmw, rgba, tri, counts, true);
+}
+
+// ---- ray-cast ----------------------------------------------------------------------------------------------------------------------
+// Everything odo_volume_raycast_dev / odo_volume_raycast check before they look at the volume.
+static int raycast_check(const char* who, const odo_raycast_params* rp, const float* A) {
+  if (rp->rows < 1 || rp->rows > 4096 || rp->cols < 1 || rp->cols > 4096) return fail("%s: bad size %dx%d (1 .. 4096 each)", who, rp->rows, rp->cols);
+  if (!(std::isfinite(rp->f) && rp->f > 0.0f)) return fail("%s: f must be finite and > 0", who);
+  if (!(std::isfinite(rp->cx) && std::isfinite(rp->cy))) return fail("%s: cx and cy must be finite", who);
+  if (!(std::isfinite(rp->t_min) && rp->t_min >= 0.0f)) return fail("%s: t_min must be finite and >= 0", who);
+  if (!(std::isfinite(rp->step) && rp->step > 0.0f)) return fail("%s: step must be finite and > 0", who);
+  if (rp->n_steps < 1 || rp->n_steps > 4096) return fail("%s: n_steps %d out of range (1 .. 4096)", who, rp->n_steps);
+  if (!pose_finite(A)) return fail("%s: the pose has a non-finite entry (a frame whose Solve failed?)", who);
+  return 0;
+}
+
+// The launch, on the volume's own stream behind the last change. The ray-cast is marked like a change: it reads the grid, and the
+// next integration on another stream must not overtake it.
+static int volume_raycast_launch(odo_volume* v, const odo_raycast_params* rp, const float* A, float* depth, uint16_t* raw, float4* nrmw,
+                                 uint32_t* rgba) {
+  HIP_OK(hipSetDevice(v->device));
+  if (volume_order_on(v, v->own)) return -1;
+  VolRaycastArgs a;
+  memset(&a, 0, sizeof(a));
+  a.vox = v->d_vox; a.col = v->d_col;
+  a.nx = v->p.nx; a.ny = v->p.ny; a.nz = v->p.nz;
+  a.rows = rp->rows; a.cols = rp->cols;
+  a.f = rp->f; a.cx = rp->cx; a.cy = rp->cy; a.t_min = rp->t_min; a.step = rp->step; a.n_steps = rp->n_steps;
+  a.depth_scale = v->p.depth_scale;
+  float e[3], G[9];
+  hostfp::raycast_frame(A, v->p.origin, v->p.voxel_size, e, G);
+  a.ex = e[0]; a.ey = e[1]; a.ez = e[2];
+  a.g00 = G[0]; a.g01 = G[1]; a.g02 = G[2]; a.g10 = G[3]; a.g11 = G[4]; a.g12 = G[5]; a.g20 = G[6]; a.g21 = G[7]; a.g22 = G[8];
+  a.depth = depth; a.raw = raw; a.nrmw = nrmw; a.rgba = rgba;
+  launch_volume_raycast(a, v->own);
+  HIP_OK(hipGetLastError());
+  return volume_mark(v, v->own);
+}
+
+extern "C" int odo_volume_raycast_dev(odo_volume* v, const odo_raycast_params* rp, const float abs_pose_colmajor[16], float* depth_dev,
+                                      uint16_t* raw_dev, float* nrmw_dev, uint8_t* rgba_dev) {
+  if (!v || !rp || !abs_pose_colmajor) return fail("odo_volume_raycast_dev: NULL arg");
+  if (((uintptr_t)depth_dev & 3) || ((uintptr_t)raw_dev & 1) || ((uintptr_t)nrmw_dev & 15) || ((uintptr_t)rgba_dev & 3))
+    return fail("odo_volume_raycast_dev: misaligned output (depth 4, raw 2, nrmw 16, rgba 4 bytes)");
+  if (raycast_check("odo_volume_raycast_dev", rp, abs_pose_colmajor)) return -1;
+  if (rgba_dev && !v->colour) return fail("odo_volume_raycast_dev: the volume has no colour grid (odo_volume_enable_colour first)");
+  if (!depth_dev && !raw_dev && !nrmw_dev && !rgba_dev) return 0;   // nothing asked for
+  return volume_raycast_launch(v, rp, abs_pose_colmajor, depth_dev, raw_dev, (float4*)nrmw_dev, (uint32_t*)rgba_dev);
+}
+
+extern "C" int odo_volume_raycast(odo_volume* v, const odo_raycast_params* rp, const float abs_pose_colmajor[16], float* depth,
+                                  uint16_t* raw, float* nrmw, uint8_t* rgba) {
+  if (!v || !rp || !abs_pose_colmajor) return fail("odo_volume_raycast: NULL arg");
+  if (raycast_check("odo_volume_raycast", rp, abs_pose_colmajor)) return -1;
+  if (rgba && !v->colour) return fail("odo_volume_raycast: the volume has no colour grid (odo_volume_enable_colour first)");
+  if (!depth && !raw && !nrmw && !rgba) return 0;
+  HIP_OK(hipSetDevice(v->device));
+  const long n = (long)rp->rows * rp->cols;
+  if (n > v->ray_capacity || (rgba && n > v->ray_rgba_capacity)) {
+    HIP_OK(hipStreamSynchronize(v->own));   // (an earlier ray-cast into these buffers through odo_volume_raycast has been waited for; be sure)
+    if (n > v->ray_capacity) {
+      void* ps[] = {v->d_ray_depth, v->d_ray_raw, v->d_ray_nrmw};
+      for (void* p : ps) if (p) (void)hipFree(p);
+      v->d_ray_depth = nullptr; v->d_ray_raw = nullptr; v->d_ray_nrmw = nullptr; v->ray_capacity = 0;
+      if (hipMalloc((void**)&v->d_ray_depth, sizeof(float) * (size_t)n) != hipSuccess ||
+          hipMalloc((void**)&v->d_ray_raw, sizeof(uint16_t) * (size_t)n) != hipSuccess ||
+          hipMalloc((void**)&v->d_ray_nrmw, sizeof(float4) * (size_t)n) != hipSuccess) {
+        (void)hipGetLastError();
+        void* qs[] = {v->d_ray_depth, v->d_ray_raw, v->d_ray_nrmw};
+        for (void* p : qs) if (p) (void)hipFree(p);
+        v->d_ray_depth = nullptr; v->d_ray_raw = nullptr; v->d_ray_nrmw = nullptr;
+        return fail("odo_volume_raycast: device allocation failed (%ld pixels)", n);
+      }
+      v->ray_capacity = n;
+    }
+    if (rgba && volume_mesh_grow((void**)&v->d_ray_rgba, &v->ray_rgba_capacity, n, sizeof(uint32_t), "pixel colours")) return -1;
+  }
+  if (volume_raycast_launch(v, rp, abs_pose_colmajor, depth ? v->d_ray_depth : nullptr, raw ? v->d_ray_raw : nullptr,
+                            nrmw ? v->d_ray_nrmw : nullptr, rgba ? v->d_ray_rgba : nullptr)) return -1;
+  if (depth) HIP_OK(hipMemcpyAsync(depth, v->d_ray_depth, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, v->own));
+  if (raw) HIP_OK(hipMemcpyAsync(raw, v->d_ray_raw, sizeof(uint16_t) * (size_t)n, hipMemcpyDeviceToHost, v->own));
+  if (nrmw) HIP_OK(hipMemcpyAsync(nrmw, v->d_ray_nrmw, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, v->own));
+  if (rgba) HIP_OK(hipMemcpyAsync(rgba, v->d_ray_rgba, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, v->own));
+  HIP_OK(hipStreamSynchronize(v->own));
+  return 0;
 }
 
 extern "C" int odo_volume_clear(odo_volume* v) {

@@ -6,6 +6,9 @@
             for the totals, then count + scan + vertices + triangles with exact capacities). Each grid is then done once more as a
             COLOURED volume (odo_volume_enable_colour): the same frames through integrate(colour=...) — volume_integrate_colour_kernel
             beside volume_integrate_kernel in one trace — followed by coloured extractions and meshes (one colour launch behind each).
+            Every leg ends with ray-casts (api.TsdfVolume.raycast: one volume_raycast_kernel launch each) at 480 x 640 with the
+            volume's K from the first and the last pose of the drive, t_min = 0, step = mu / 2, samples up to max_depth + mu; the
+            coloured legs ask for the colour frame as well.
             Run it under the profiler, in a run of its own (no counters in that run), then summarise:
               rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/volume_cost.py kernels
               python tools/volume_cost.py summary <dir>
@@ -90,8 +93,12 @@ def kernels(args):
             for _ in range(args.extractions):
                 got = vol.mesh(colour=coloured)
                 nv, nt = len(got[0]), len(got[2])
+            hits = []
+            for _ in range(args.extractions):
+                for k in (0, len(seq["poses"]) - 1):
+                    hits.append(int((vol.raycast(seq["poses"][k], step=MU / 2, raw=True, colour=coloured)[0] > 0).sum()))
             nx, ny, nz = GRIDS[grid]["dims"]
-            row = dict(voxels=nx * ny * nz, updated_per_frame=int(np.median(upd)), in_band_per_frame=int(np.median(band)), points=n,
+            row = dict(raycast_hits=hits[:2], voxels=nx * ny * nz, updated_per_frame=int(np.median(upd)), in_band_per_frame=int(np.median(band)), points=n,
                        vertices=nv, triangles=nt, pixels=synth.TUM_ROWS * synth.TUM_COLS, integrate_host_us_back_to_back=round(host_us, 1))
             if coloured:
                 out[grid]["coloured_integrate_host_us_back_to_back"] = row["integrate_host_us_back_to_back"]
