@@ -31,7 +31,7 @@ DEPS = [SRC, SRC_DENSE, SRC_CHAIN, SRC_MAP, SRC_RGBD, SRC_FRONTEND, SRC_VOLUME, 
         os.path.join(_HERE, "csrc", "volume_colour.hip.h"), os.path.join(_HERE, "csrc", "volume_colour_math.h"),
         os.path.join(_HERE, "csrc", "volume_mesh.hip.h"), os.path.join(_HERE, "csrc", "volume_mesh_table.h"),
         os.path.join(_HERE, "csrc", "volume_api.hip.h"), os.path.join(_HERE, "csrc", "rgbd_frontend.hip.h"),
-        os.path.join(_HERE, "csrc", "rgbd_frontend_api.hip.h"), os.path.join(_HERE, "csrc", "rgbd.hip.h"), os.path.join(_HERE, "csrc", "map.hip.h"), os.path.join(_HERE, "csrc", "map_api.hip.h"), os.path.join(_HERE, "csrc", "kernels.hip.h"), os.path.join(_HERE, "csrc", "odo_math.h"), os.path.join(_HERE, "csrc", "tracker.hip.h"), os.path.join(_HERE, "csrc", "batch.hip.h"), os.path.join(_HERE, "csrc", "gather.hip.h"), os.path.join(_HERE, "csrc", "camera.hip.h"),
+        os.path.join(_HERE, "csrc", "rgbd_frontend_api.hip.h"), os.path.join(_HERE, "csrc", "rgbd.hip.h"), os.path.join(_HERE, "csrc", "map.hip.h"), os.path.join(_HERE, "csrc", "map_api.hip.h"), os.path.join(_HERE, "csrc", "kernels.hip.h"), os.path.join(_HERE, "csrc", "odo_math.h"), os.path.join(_HERE, "csrc", "tracker.hip.h"), os.path.join(_HERE, "csrc", "batch.hip.h"), os.path.join(_HERE, "csrc", "gather.hip.h"), os.path.join(_HERE, "csrc", "camera.hip.h"), os.path.join(_HERE, "csrc", "camera_math.h"),
         os.path.join(_HERE, "csrc", "dense.hip.h"), os.path.join(_HERE, "csrc", "host_fp.h"),
         os.path.join(os.path.dirname(_HERE), "include", "odometry_hip.h"), os.path.abspath(__file__)]   # (this file: the flags)
 LIB = os.path.join(_HERE, "lib", "libodometry_hip.so")

@@ -3,39 +3,19 @@
 // Replaces odometry::CameraPyramid (ref: include/camera.h:16-119; src/camera.cpp:12-38 ctor, :40-69 ConfigureCamera,
 // :71-82 UndistortRectify). The two OpenCV calls behind it — cv::initUndistortRectifyMap and cv::remap — are restated
 // from their documented definitions (the library is not vendored; parity unpinned):
-//   map:   [x y w]^T = (P[:, :3] * R)^-1 * [u v 1]^T; x' = x/w, y' = y/w; r2 = x'^2 + y'^2;
-//          kr = 1 + (k2*r2 + k1)*r2; xd = x'*kr + p1*2x'y' + p2*(r2 + 2x'^2); yd = y'*kr + p1*(r2 + 2y'^2) + p2*2x'y';
-//          map_x = fx*xd + cx, map_y = fy*yd + cy   — fp64, stored as fp32 (CV_32FC1 maps).
-//   remap: INTER_LINEAR with OpenCV's 5-bit fixed-point coordinates (INTER_BITS = 5): sx = rint(map_x * 32),
-//          ix = sx >> 5, ax = sx & 31, weights (1 - ay/32)(1 - ax/32) ... as fp32 products, value =
-//          ((S00*w00 + S01*w01) + S10*w10) + S11*w11; BORDER_CONSTANT: a tap outside the source reads border_value.
+// The per-pixel arithmetic (the map entry, the remapped pixel, the rule for coordinates that do not fit an int) and the host-side
+// coefficients are camera_math.h, which tests/camera_math_harness.cpp compiles with g++ as well.
 // Included at the end of odometry_hip.hip (shares its context, error and allocation helpers).
 #pragma once
 
+#include "camera_math.h"
+
 namespace odo {
 
-struct CamCoef {     // everything the map kernel needs, fp64
-  double iR[9];      // (P[:, :3] * R)^-1, row-major
-  double fx, fy, cx, cy;  // raw camera matrix (skew is ignored, as cv::initUndistortRectifyMap does)
-  double k1, k2, p1, p2;  // radial k1, k2 and tangential p1, p2 (the reference's "r1", "r2")
+struct CamLoad {     // the source in global memory
+  const float* __restrict__ p;
+  __device__ __forceinline__ float operator()(size_t i) const { return p[i]; }
 };
-
-// One map entry.
-ODO_HD void undistort_map_entry(const CamCoef& c, int u, int v, float* mx, float* my) {
-  const double du = (double)u, dv = (double)v;
-  const double _x = (c.iR[0] * du + c.iR[1] * dv) + c.iR[2];
-  const double _y = (c.iR[3] * du + c.iR[4] * dv) + c.iR[5];
-  const double _w = (c.iR[6] * du + c.iR[7] * dv) + c.iR[8];
-  const double w = 1.0 / _w;
-  const double x = _x * w, y = _y * w;
-  const double x2 = x * x, y2 = y * y;
-  const double r2 = x2 + y2, _2xy = (2.0 * x) * y;
-  const double kr = 1.0 + (c.k2 * r2 + c.k1) * r2;
-  const double xd = (x * kr + c.p1 * _2xy) + c.p2 * (r2 + 2.0 * x2);
-  const double yd = (y * kr + c.p1 * (r2 + 2.0 * y2)) + c.p2 * _2xy;
-  *mx = (float)(c.fx * xd + c.cx);
-  *my = (float)(c.fy * yd + c.cy);
-}
 
 __global__ void __launch_bounds__(256) undistort_map_kernel(CamCoef c, int rows, int cols, float* __restrict__ mapx,
                                                             float* __restrict__ mapy) {
@@ -58,17 +38,8 @@ __global__ void __launch_bounds__(256) remap_bilinear_kernel(const float* __rest
   const int v = blockIdx.y * 4 + (threadIdx.x >> 6);
   if (u >= dcols || v >= drows) return;
   const size_t o = (size_t)v * dcols + u;
-  const int sx = (int)rintf(mapx[o] * 32.0f), sy = (int)rintf(mapy[o] * 32.0f);
-  const int ix = sx >> 5, iy = sy >> 5;
-  const float ax = (float)(sx & 31) * (1.0f / 32.0f), ay = (float)(sy & 31) * (1.0f / 32.0f);
-  const float w00 = (1.0f - ay) * (1.0f - ax), w01 = (1.0f - ay) * ax, w10 = ay * (1.0f - ax), w11 = ay * ax;
-  const bool x0 = (unsigned)ix < (unsigned)scols, x1 = (unsigned)(ix + 1) < (unsigned)scols;
-  const bool y0 = (unsigned)iy < (unsigned)srows, y1 = (unsigned)(iy + 1) < (unsigned)srows;
-  const float s00 = (x0 && y0) ? src[(size_t)iy * scols + ix] : border_value;
-  const float s01 = (x1 && y0) ? src[(size_t)iy * scols + ix + 1] : border_value;
-  const float s10 = (x0 && y1) ? src[(size_t)(iy + 1) * scols + ix] : border_value;
-  const float s11 = (x1 && y1) ? src[(size_t)(iy + 1) * scols + ix + 1] : border_value;
-  dst[o] = ((s00 * w00 + s01 * w01) + s10 * w10) + s11 * w11;
+  const CamLoad load = {src};
+  dst[o] = remap_bilinear_pixel(load, srows, scols, mapx[o], mapy[o], border_value);
 }
 
 }  // namespace odo
@@ -90,20 +61,6 @@ struct odo_camera {
   float* d_dst;
   size_t src_cap, dst_cap;
 };
-
-// 3x3 inverse by cofactors in fp64, fixed operation order (part of the arithmetic contract: the CPU checker repeats it).
-static bool cam_inv3(const double m[9], double out[9]) {
-  const double c00 = m[4] * m[8] - m[5] * m[7];
-  const double c01 = m[5] * m[6] - m[3] * m[8];
-  const double c02 = m[3] * m[7] - m[4] * m[6];
-  const double det = (m[0] * c00 + m[1] * c01) + m[2] * c02;
-  if (!(fabs(det) > 0.0)) return false;
-  const double id = 1.0 / det;
-  out[0] = c00 * id; out[1] = (m[2] * m[7] - m[1] * m[8]) * id; out[2] = (m[1] * m[5] - m[2] * m[4]) * id;
-  out[3] = c01 * id; out[4] = (m[0] * m[8] - m[2] * m[6]) * id; out[5] = (m[2] * m[3] - m[0] * m[5]) * id;
-  out[6] = c02 * id; out[7] = (m[1] * m[6] - m[0] * m[7]) * id; out[8] = (m[0] * m[4] - m[1] * m[3]) * id;
-  return true;
-}
 
 extern "C" int odo_camera_create(odo_ctx* ctx, int levels, double fx, double fy, double f_theta, double cx, double cy,
                                  double k1, double k2, double r1, double r2, double sensor_width, double sensor_height,
@@ -138,14 +95,8 @@ extern "C" int odo_camera_configure(odo_camera* c, const double R_rowmajor[9], c
     cy = (cy + 0.5) / 2.0 + 0.5;
   }
   // lookup maps (ref: :68 cv::initUndistortRectifyMap(intrinsic_raw_, distortion_param_, R, P, size, CV_32FC1, ...))
-  double PR[9];
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++)
-      PR[i * 3 + j] = (P[i * 4 + 0] * R_rowmajor[0 * 3 + j] + P[i * 4 + 1] * R_rowmajor[1 * 3 + j]) + P[i * 4 + 2] * R_rowmajor[2 * 3 + j];
   odo::CamCoef k;
-  if (!cam_inv3(PR, k.iR)) return fail("odo_camera_configure: P[:, :3] * R is singular");
-  k.fx = c->raw[0]; k.fy = c->raw[1]; k.cx = c->raw[3]; k.cy = c->raw[4];
-  k.k1 = c->dist[0]; k.k2 = c->dist[1]; k.p1 = c->dist[2]; k.p2 = c->dist[3];
+  if (!odo::cam_coef(c->raw, c->dist, R_rowmajor, P, &k)) return fail("odo_camera_configure: P[:, :3] * R is singular");
   HIP_OK(hipSetDevice(c->ctx->device));
   const size_t n = (size_t)new_width * new_height;
   if (c->d_mapx) { (void)hipFree(c->d_mapx); c->d_mapx = nullptr; }
@@ -215,6 +166,7 @@ extern "C" int odo_camera_undistort_rectify(odo_camera* c, const float* src, int
                                             float border_value) {
   if (!c || !src || !dst) return fail("odo_camera_undistort_rectify: NULL arg");
   if (!c->configured) return fail("odo_camera_undistort_rectify: ConfigureCamera has not run");
+  if (src_rows < 1 || src_cols < 1) return fail("odo_camera_undistort_rectify: bad source size");
   HIP_OK(hipSetDevice(c->ctx->device));
   const size_t sb = (size_t)src_rows * src_cols * sizeof(float), db = (size_t)c->map_rows * c->map_cols * sizeof(float);
   if (c->src_cap < sb) {

@@ -1214,13 +1214,20 @@ int orc_camera_init_maps(const double raw[5], const double dist[4], const double
 }
 
 /* cv::remap(src, dst, mapx, mapy, INTER_LINEAR, BORDER_CONSTANT, border_value) on CV_32F (ref: src/camera.cpp:80):
- * 5-bit fixed-point source coordinates, fp32 bilinear weights, taps outside the source read border_value. */
+ * 5-bit fixed-point source coordinates, fp32 bilinear weights, taps outside the source read border_value. A pixel with a
+ * coordinate c for which !(fabsf(c * 32) < 2^31) is border_value as it is: tested on floats, so nothing
+ * that an int cannot represent is ever converted. */
 void orc_camera_remap(const float* src, int srows, int scols, const float* mapx, const float* mapy, int drows, int dcols,
                       float border_value, float* dst) {
   for (int v = 0; v < drows; v++)
     for (int u = 0; u < dcols; u++) {
       const size_t o = (size_t)v * dcols + u;
-      const int sx = (int)rintf(mapx[o] * 32.0f), sy = (int)rintf(mapy[o] * 32.0f);
+      const float fx = mapx[o] * 32.0f, fy = mapy[o] * 32.0f;
+      if (!(fabsf(fx) < 2147483648.0f && fabsf(fy) < 2147483648.0f)) {  /* NaN, +-inf, no int holds it: the border value itself */
+        dst[o] = border_value;
+        continue;
+      }
+      const int sx = (int)rintf(fx), sy = (int)rintf(fy);
       const int ix = sx >> 5, iy = sy >> 5;
       const float ax = (float)(sx & 31) * (1.0f / 32.0f), ay = (float)(sy & 31) * (1.0f / 32.0f);
       const float w00 = (1.0f - ay) * (1.0f - ax), w01 = (1.0f - ay) * ax, w10 = ay * (1.0f - ax), w11 = ay * ax;
