@@ -720,6 +720,96 @@ int odo_volume_raycast_dev(odo_volume* v, const odo_raycast_params* p, const flo
 int odo_volume_raycast(odo_volume* v, const odo_raycast_params* p, const float abs_pose_colmajor[16], float* depth, uint16_t* raw,
                        float* nrmw, uint8_t* rgba);
 
+/* ---- Frame-to-model tracking: a depth frame aligned to the volume's ray-cast by point-to-plane ICP --------------------------------
+ * The model frame is a ray-cast of the volume at the volume's own rows, cols and K (f = K.f0, cx = K.cx0, cy = K.cy0): depth
+ * (float32) and nrmw, taken from the camera-to-world pose P_m. The sensor frame is a uint16 raw depth frame as odo_volume_integrate_dev
+ * takes it. The unknown is C, the transform from the sensor camera to the model camera (column-major, C_rc at C[4 c + r]); projective
+ * association, point-to-plane Gauss-Newton over up to three strides of the sensor frame. All floating point is fp32, one rounding
+ * per operation, unless fp64 is named (DESIGN.md section 9.8 holds the same table).
+ * Host part (fp64 from the fp32 entries, each result rounded to fp32 once): M = [R^T | -R^T t] of P_m as in the integration;
+ * C_0 = M P_init with every entry ((m_r0 p_0c + m_r1 p_1c) + m_r2 p_2c) + m_r3 p_3c; at the end abs_pose = P_m C the same way.
+ * Per sensor pixel (x, y) with x % s == 0 && y % s == 0, s the level's stride:
+ *   1. r = raw[y cols + x]; skipped if 0. D = (float)r / depth_scale; skipped if D > max_depth (the integration's step 3).
+ *   2. dx = ((float)x - cx) / f, dy = ((float)y - cy) / f (the ray-cast's); p = (dx D, dy D, D).
+ *   3. pm_r = ((C_r0 p_x + C_r1 p_y) + C_r2 p_z) + C_r3; skipped unless pm_z > 0.
+ *   4. u = f (pm_x / pm_z) + cx, v = f (pm_y / pm_z) + cy; xi = floorf(u + 0.5f), yi = floorf(v + 0.5f); skipped unless 0 <= xi < cols
+ *      and 0 <= yi < rows, compared as floats before any conversion, so NaN fails (the integration's step 2).
+ *   5. zm = depth_m[yi cols + xi]; skipped unless zm > 0. n_w = nrmw_m[yi cols + xi].xyz; skipped if all three are 0.
+ *      n_r = (M_r0 n_w.x + M_r1 n_w.y) + M_r2 n_w.z: the normal in the model camera.
+ *   6. vm = ((((float)xi - cx) / f) zm, (((float)yi - cy) / f) zm, zm); d = pm - vm; dd = (d_x d_x + d_y d_y) + d_z d_z; skipped
+ *      unless dd <= dist_max * dist_max (the product in fp32; equality keeps the pair).
+ *   7. res = (n_x d_x + n_y d_y) + n_z d_z;
+ *      J = (n_x, n_y, n_z, pm_y n_z - pm_z n_y, pm_z n_x - pm_x n_z, pm_x n_y - pm_y n_x), translation first as in the LM's steps;
+ *      w = (|res| <= huber_delta ? 1 : huber_delta / |res|) if huber_delta > 0, else 1.
+ *   8. The 29 sums of the pose LM, fp64 over exact products of fp32 values: the upper triangle of sum (J_a w) J_b in row-major order
+ *      (21), sum (J_a w) res (6), sum (res w) res, and the number of pairs; J_a w and res w are rounded to fp32 first.
+ * The order of the sums is fixed (per block of 16 x 16 lattice points, then over the blocks in raster order: volume_icp.hip.h), no
+ * atomics: two calls on the same inputs give the same bits.
+ * Step. It fails (status 1) if the number of pairs is below min_pairs or any sum is not finite. Otherwise delta solves the undamped
+ * normal equations in fp64 by the pose LM's elimination (a zero pivot leaves its component at 0), rounded to fp32, and
+ * C <- matrix(SE3(exp(delta) C)) with the pose LM's exponential, fp32 4 x 4 product and quaternion round trip. The level has
+ * converged when sqrtf((d_0 d_0 + d_1 d_1) + d_2 d_2) < eps_t and the same over d_3 .. d_5 is < eps_r; otherwise it ends after
+ * iters[level] steps. Levels run in the order given, each from the C the one before left.
+ * Conditioning (host, fp64). eig_min and eig_max are the extreme eigenvalues of the 6 x 6 of the last evaluation (cyclic Jacobi).
+ * Translation (metres) and rotation (radians) share the matrix unscaled, so the ratio depends on the scene's distance from the
+ * camera: it is a test for a direction that the geometry does not constrain at all (a corridor's axis: 1e-6), not a measure of
+ * accuracy. If eig_min < min_eig_ratio * eig_max the alignment is refused (status 2). A C with a non-finite entry is status 1.
+ * status: 0 aligned; 1 too few pairs or non-finite sums; 2 rank-deficient. On 1 and 2 abs_pose is sixteen NaNs — the trackers'
+ * convention for a failed Solve, which odo_volume_integrate_dev refuses. */
+typedef struct {
+  int levels;                  /* 1 .. 3 */
+  int stride[3];               /* per level, 1 .. 16 */
+  int iters[3];                /* per level, >= 0; their sum over the levels 1 .. 64 */
+  float dist_max;              /* the pair gate in metres, finite > 0 */
+  float huber_delta;           /* metres, finite >= 0; 0: no robust weight */
+  float eps_t, eps_r;          /* convergence thresholds on the step, metres / radians, finite >= 0 (0: every iteration runs) */
+  int min_pairs;               /* >= 6 */
+  float min_eig_ratio;         /* 0 .. 1; 0: never refused as rank-deficient */
+} odo_icp_params;
+typedef struct {
+  int status;                  /* 0, 1, 2: above */
+  int iterations;              /* steps taken over all levels (a failed one included) */
+  double pairs, cost;          /* of the last evaluation: the number of pairs and sum w res^2 */
+  double eig_min, eig_max;     /* of its 6 x 6; 0 if nothing was evaluated */
+  float C[16];                 /* the last estimate, whatever the status */
+} odo_icp_result;
+typedef struct {               /* one step of an alignment */
+  int level, iteration;        /* iteration counts over all levels from 0 */
+  double acc[29];              /* the sums of the evaluation at the C before the step */
+  float delta[6];              /* the step (zeros when it failed) */
+  float C[16];                 /* the estimate after it */
+} odo_icp_trace_row;
+/* One evaluation of steps 1 .. 8 at C for one stride: acc receives the 29 sums; rows_dev (device, 16-byte aligned, may be NULL)
+ * receives float[8] = {J_0 .. J_5, res, w} for every pixel of the frame, eight zeros for a pixel that is skipped or off the stride.
+ * depth_m_dev / nrmw_m_dev: the model frame on the device (4 / 16-byte aligned), model_pose = P_m; raw_dev: the sensor frame.
+ * Validation before any device work (-1, nothing enqueued): stride 1 .. 16, dist_max finite > 0, huber_delta finite >= 0, every
+ * entry of C and model_pose finite, alignment. The call runs on the volume's own stream behind everything that changed the volume
+ * so far and waits. Neither grid and no counter is modified; legal while attached, ordered as odo_volume_raycast_dev is. */
+int odo_volume_icp_eval_dev(odo_volume* v, const float* depth_m_dev, const float* nrmw_m_dev, const float model_pose_colmajor[16],
+                            const uint16_t* raw_dev, const float C_colmajor[16], int stride, float dist_max, float huber_delta,
+                            double acc[29], float* rows_dev);
+/* Event timing of the two kernels (diagnostic): reps (1 .. 10000) launches of the rows kernel at C for one stride, then reps launches
+ * of the step kernel's fold, each batch between two events on the volume's own stream; us[0], us[1] receive the mean time of one
+ * launch of either in microseconds. Validated, ordered and legal as odo_volume_icp_eval_dev; nothing of the volume changes. */
+int odo_volume_icp_time_dev(odo_volume* v, const float* depth_m_dev, const float* nrmw_m_dev, const float model_pose_colmajor[16],
+                            const uint16_t* raw_dev, const float C_colmajor[16], int stride, float dist_max, float huber_delta, int reps,
+                            float us[2]);
+/* The alignment: the sum of iters pairs of ordinary launches (rows, step) on the volume's own stream, each of which returns at once
+ * when its level has converged or the alignment has failed; the host waits once, at the end. init_pose = P_init, the first guess of
+ * the sensor camera's camera-to-world pose; abs_pose receives P_m C or sixteen NaNs. trace (host, may be NULL) receives the first
+ * trace_capacity steps, *trace_n (may be NULL) how many were written. Validation of params, the poses and the alignment before any
+ * device work (-1, nothing enqueued). Ordered and legal as odo_volume_icp_eval_dev. */
+int odo_volume_icp_align_dev(odo_volume* v, const odo_icp_params* p, const float* depth_m_dev, const float* nrmw_m_dev,
+                             const float model_pose_colmajor[16], const uint16_t* raw_dev, const float init_pose_colmajor[16],
+                             float abs_pose_colmajor[16], odo_icp_result* result, odo_icp_trace_row* trace, int trace_capacity,
+                             int* trace_n);
+/* Frame-to-model tracking of one depth frame: a ray-cast of the volume from prev_pose at the volume's own rows, cols and K with
+ * t_min = 0, step = mu / 2 and n_steps = min(4096, ceil((max_depth + mu) / step) + 1) (api.TsdfVolume.raycast's defaults) into frames
+ * that the volume owns, then odo_volume_icp_align_dev against them with model_pose = init_pose = prev_pose. It does not integrate.
+ * Refused when rows or cols exceed the ray-cast's 4096. */
+int odo_volume_track_dev(odo_volume* v, const odo_icp_params* p, const uint16_t* raw_dev, const float prev_pose_colmajor[16],
+                         float abs_pose_colmajor[16], odo_icp_result* result);
+
 /* ---- RGB-D front end: raw sensor frames -> the RGB-D tracker's inputs ----------------------------------------------------------
  * A sensor delivers interleaved 8-bit colour and a uint16 depth frame in the DEPTH imager's pixel grid (its own intrinsics, often
  * its own resolution, centimetres beside the colour imager); odo_tracker_*_rgbd take an fp32 grey image and a uint16 depth frame in

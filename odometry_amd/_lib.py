@@ -58,6 +58,22 @@ class RaycastParams(C.Structure):
                 ("t_min", C.c_float), ("step", C.c_float), ("n_steps", C.c_int)]
 
 
+class IcpParams(C.Structure):
+    _fields_ = [("levels", C.c_int), ("stride", C.c_int * 3), ("iters", C.c_int * 3), ("dist_max", C.c_float),
+                ("huber_delta", C.c_float), ("eps_t", C.c_float), ("eps_r", C.c_float), ("min_pairs", C.c_int),
+                ("min_eig_ratio", C.c_float)]
+
+
+class IcpResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("iterations", C.c_int), ("pairs", C.c_double), ("cost", C.c_double),
+                ("eig_min", C.c_double), ("eig_max", C.c_double), ("C", C.c_float * 16)]
+
+
+class IcpTraceRow(C.Structure):
+    _fields_ = [("level", C.c_int), ("iteration", C.c_int), ("acc", C.c_double * NACC), ("delta", C.c_float * 6),
+                ("C", C.c_float * 16)]
+
+
 _fp = C.POINTER(C.c_float)
 _dp = C.POINTER(C.c_double)
 _u8p = C.POINTER(C.c_uint8)
@@ -240,6 +256,11 @@ SIGNATURES = {
     "odo_rgbd_frontend_colour": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "odo_volume_raycast_dev": (C.c_int, [_vp, C.POINTER(RaycastParams), _fp, _vp, _vp, _vp, _vp]),
     "odo_volume_raycast": (C.c_int, [_vp, C.POINTER(RaycastParams), _fp, _fp, C.POINTER(C.c_uint16), _fp, _u8p]),
+    "odo_volume_icp_eval_dev": (C.c_int, [_vp, _vp, _vp, _fp, _vp, _fp, C.c_int, C.c_float, C.c_float, _dp, _vp]),
+    "odo_volume_icp_time_dev": (C.c_int, [_vp, _vp, _vp, _fp, _vp, _fp, C.c_int, C.c_float, C.c_float, C.c_int, _fp]),
+    "odo_volume_icp_align_dev": (C.c_int, [_vp, C.POINTER(IcpParams), _vp, _vp, _fp, _vp, _fp, _fp, C.POINTER(IcpResult),
+                                           C.POINTER(IcpTraceRow), C.c_int, _ip]),
+    "odo_volume_track_dev": (C.c_int, [_vp, C.POINTER(IcpParams), _vp, _fp, _fp, C.POINTER(IcpResult)]),
 }
 
 _lib = None

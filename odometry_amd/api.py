@@ -1090,6 +1090,142 @@ class TsdfVolume:
             out += (rgba,)
         return out
 
+    # ---- frame-to-model tracking (odo_volume_icp_*, odo_volume_track_dev) ----
+    ICP_STATUS = ("aligned", "too few pairs", "rank-deficient")
+    # Default of min_eig_ratio: 0, nothing is refused as rank-deficient unless the caller sets a ratio. Measured with the fp32 model
+    # at 120 x 160: eig_min / eig_max is at most 6.5e-4 on the plain corridor, which cannot be tracked, and at
+    # least 4.95e-3 on a narrow ribbed one, which can; their geometric mean 1.8e-3 separates the two by a factor 2.8 only.
+    ICP_MIN_EIG_RATIO = 0.0
+
+    def icp_params(self, strides=(4, 2, 1), iters=(4, 5, 10), dist_max=None, huber_delta=0.0, eps_t=1e-5, eps_r=1e-5, min_pairs=None,
+                   min_eig_ratio=None):
+        """The odo_icp_params of align() and track(): coarse to fine over the strides, dist_max = 2 mu, min_pairs = 1 / 64 of the
+        first level's pixels and the measured default of min_eig_ratio unless given."""
+        if not 1 <= len(strides) == len(iters) <= 3:
+            raise ValueError("one to three levels, a stride and an iteration count for each")
+        p = L.IcpParams()
+        p.levels = len(strides)
+        for i, (s, n) in enumerate(zip(strides, iters)):
+            p.stride[i], p.iters[i] = int(s), int(n)
+        p.dist_max = 2 * self.params.mu if dist_max is None else dist_max
+        p.huber_delta, p.eps_t, p.eps_r = huber_delta, eps_t, eps_r
+        s0 = int(strides[0])
+        lattice = (-(-self.rows // s0)) * (-(-self.cols // s0)) if s0 >= 1 else 0
+        p.min_pairs = max(6, lattice // 64) if min_pairs is None else int(min_pairs)
+        p.min_eig_ratio = self.ICP_MIN_EIG_RATIO if min_eig_ratio is None else min_eig_ratio
+        return p
+
+    def _frames_dev(self, frames):
+        """Device handles of frames given as numpy arrays (uploaded; the second list names the temporaries) or as handles."""
+        handles, temps = [], []
+        try:
+            for a, dtype, shape in frames:
+                if isinstance(a, np.ndarray):
+                    a = np.ascontiguousarray(a, dtype)
+                    if a.shape != shape:
+                        raise ValueError(f"frame {a.shape}, expected {shape}")
+                    p = C.c_void_p()
+                    L.check(self.lib.odo_dev_alloc(self._ctx, a.nbytes, C.byref(p)), "odo_dev_alloc")
+                    temps.append(p)
+                    L.check(self.lib.odo_dev_upload(self._ctx, p, a.ctypes.data_as(C.c_void_p), a.nbytes), "odo_dev_upload")
+                    a = p
+                handles.append(a)
+        except Exception:
+            self._free_dev(temps)
+            raise
+        return handles, temps
+
+    def _free_dev(self, temps):
+        for p in temps:
+            self.lib.odo_dev_free(self._ctx, p)
+
+    def _model_frames(self, depth, model_depth, model_nrmw):
+        size = (self.rows, self.cols)
+        return self._frames_dev([(depth, np.uint16, size), (model_depth, np.float32, size), (model_nrmw, np.float32, size + (4,))])
+
+    @staticmethod
+    def _icp_result(r):
+        return dict(status=r.status, iterations=r.iterations, pairs=r.pairs, cost=r.cost, eig_min=r.eig_min, eig_max=r.eig_max,
+                    C=_from_colmajor(list(r.C)))
+
+    def icp_eval(self, depth, model_depth, model_nrmw, model_pose, C_sensor_to_model, stride=1, dist_max=None, huber_delta=0.0,
+                 rows=False):
+        """One evaluation of the alignment's rows at the 4x4 transform C_sensor_to_model: the 29 sums (float64), with rows=True also
+        (rows, cols, 8) float32 {J0 .. J5, res, w} per pixel. depth: the sensor's uint16 frame; model_depth / model_nrmw: a ray-cast
+        from model_pose at the volume's size and K; each a numpy array or a device handle."""
+        (raw_d, dep_d, nrm_d), temps = self._model_frames(depth, model_depth, model_nrmw)
+        acc = np.zeros(L.NACC, np.float64)
+        out = None
+        try:
+            if rows:
+                out = C.c_void_p()
+                L.check(self.lib.odo_dev_alloc(self._ctx, self.rows * self.cols * 32, C.byref(out)), "odo_dev_alloc")
+                temps.append(out)
+                L.check(self.lib.odo_dev_upload(self._ctx, out, np.full(self.rows * self.cols * 32, 0xAB, np.uint8).ctypes.data_as(C.c_void_p),
+                                                self.rows * self.cols * 32), "odo_dev_upload")
+            L.check(self.lib.odo_volume_icp_eval_dev(self.h, dep_d, nrm_d, _fp(_colmajor(model_pose)), raw_d, _fp(_colmajor(C_sensor_to_model)),
+                                                     int(stride), 2 * self.params.mu if dist_max is None else dist_max, huber_delta,
+                                                     acc.ctypes.data_as(L._dp), out), "odo_volume_icp_eval_dev")
+            if rows:
+                got = np.empty((self.rows, self.cols, 8), np.float32)
+                L.check(self.lib.odo_dev_download(self._ctx, got.ctypes.data_as(C.c_void_p), out, got.nbytes), "odo_dev_download")
+                return acc, got
+            return acc
+        finally:
+            self._free_dev(temps)
+
+    def icp_time(self, depth, model_depth, model_nrmw, model_pose, C_sensor_to_model, stride=1, dist_max=None, huber_delta=0.0, reps=50):
+        """Event timing of the alignment's two kernels: (rows, step) microseconds per launch, means over reps launches each."""
+        (raw_d, dep_d, nrm_d), temps = self._model_frames(depth, model_depth, model_nrmw)
+        us = np.zeros(2, np.float32)
+        try:
+            L.check(self.lib.odo_volume_icp_time_dev(self.h, dep_d, nrm_d, _fp(_colmajor(model_pose)), raw_d, _fp(_colmajor(C_sensor_to_model)),
+                                                     int(stride), 2 * self.params.mu if dist_max is None else dist_max, huber_delta, int(reps),
+                                                     _fp(us)), "odo_volume_icp_time_dev")
+        finally:
+            self._free_dev(temps)
+        return float(us[0]), float(us[1])
+
+    def align(self, depth, model_depth, model_nrmw, model_pose, init_pose, trace=False, params=None):
+        """Aligns the sensor's depth frame to a model frame (a ray-cast from model_pose at the volume's size and K) from the first
+        guess init_pose: (abs_pose 4x4 float32 — NaNs unless status is 0 —, result dict: status, iterations, pairs, cost, eig_min,
+        eig_max, C), with trace=True also the steps as a list of dicts (level, iteration, acc, delta, C)."""
+        p = self.icp_params() if params is None else params
+        (raw_d, dep_d, nrm_d), temps = self._model_frames(depth, model_depth, model_nrmw)
+        cap = sum(p.iters[:p.levels]) if trace else 0
+        rows = (L.IcpTraceRow * max(cap, 1))()
+        n = C.c_int(0)
+        res = L.IcpResult()
+        pose = np.zeros(16, np.float32)
+        try:
+            L.check(self.lib.odo_volume_icp_align_dev(self.h, C.byref(p), dep_d, nrm_d, _fp(_colmajor(model_pose)), raw_d,
+                                                      _fp(_colmajor(init_pose)), _fp(pose), C.byref(res), rows if trace else None, cap,
+                                                      C.byref(n)), "odo_volume_icp_align_dev")
+        finally:
+            self._free_dev(temps)
+        out = (_from_colmajor(pose), self._icp_result(res))
+        if trace:
+            out += ([dict(level=r.level, iteration=r.iteration, acc=np.array(r.acc, np.float64), delta=np.array(r.delta, np.float32),
+                          C=_from_colmajor(list(r.C))) for r in rows[:n.value]],)
+        return out
+
+    def track(self, depth, prev_pose, integrate=False, params=None):
+        """Frame-to-model tracking of one depth frame (a uint16 numpy array or a device handle): the volume is ray-cast from prev_pose
+        and the frame aligned to that from prev_pose. Returns (abs_pose, result dict) as align(). integrate=True fuses the frame at
+        the returned pose when status is 0."""
+        p = self.icp_params() if params is None else params
+        (raw_d,), temps = self._frames_dev([(depth, np.uint16, (self.rows, self.cols))])
+        res = L.IcpResult()
+        pose = np.zeros(16, np.float32)
+        try:
+            L.check(self.lib.odo_volume_track_dev(self.h, C.byref(p), raw_d, _fp(_colmajor(prev_pose)), _fp(pose), C.byref(res)),
+                    "odo_volume_track_dev")
+            if integrate and res.status == 0:
+                L.check(self.lib.odo_volume_integrate_dev(self.h, raw_d, _fp(pose)), "odo_volume_integrate_dev")
+        finally:   # odo_dev_free waits for the context's stream: the integration has read the frame
+            self._free_dev(temps)
+        return _from_colmajor(pose), self._icp_result(res)
+
     def stats(self):
         o = (C.c_long * 4)()
         L.check(self.lib.odo_volume_stats(self.h, o), "odo_volume_stats")

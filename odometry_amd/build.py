@@ -26,7 +26,9 @@ SRC_VOLUME = os.path.join(_HERE, "csrc", "volume_kernels.hip")   # the TSDF volu
 SRC_VOLUME_MESH = os.path.join(_HERE, "csrc", "volume_mesh_kernels.hip")   # the volume's mesh kernels (volume_mesh.hip.h): the main unit's scheduler
 SRC_VOLUME_COLOUR = os.path.join(_HERE, "csrc", "volume_colour_kernels.hip")   # the volume's colour kernels (volume_colour.hip.h): the main unit's scheduler
 SRC_VOLUME_RAYCAST = os.path.join(_HERE, "csrc", "volume_raycast_kernels.hip")   # the volume's ray-cast kernel (volume_raycast.hip.h): the main unit's scheduler
-DEPS = [SRC, SRC_DENSE, SRC_CHAIN, SRC_MAP, SRC_RGBD, SRC_FRONTEND, SRC_VOLUME, SRC_VOLUME_MESH, SRC_VOLUME_COLOUR, SRC_VOLUME_RAYCAST, os.path.join(_HERE, "csrc", "volume.hip.h"),
+SRC_VOLUME_ICP = os.path.join(_HERE, "csrc", "volume_icp_kernels.hip")   # the volume's frame-to-model alignment kernels (volume_icp.hip.h): the main unit's scheduler
+DEPS = [SRC, SRC_DENSE, SRC_CHAIN, SRC_MAP, SRC_RGBD, SRC_FRONTEND, SRC_VOLUME, SRC_VOLUME_MESH, SRC_VOLUME_COLOUR, SRC_VOLUME_RAYCAST, SRC_VOLUME_ICP, os.path.join(_HERE, "csrc", "volume.hip.h"),
+        os.path.join(_HERE, "csrc", "volume_icp.hip.h"), os.path.join(_HERE, "csrc", "volume_icp_math.h"), os.path.join(_HERE, "csrc", "volume_icp_api.hip.h"),
         os.path.join(_HERE, "csrc", "volume_raycast.hip.h"), os.path.join(_HERE, "csrc", "volume_raycast_math.h"),
         os.path.join(_HERE, "csrc", "volume_colour.hip.h"), os.path.join(_HERE, "csrc", "volume_colour_math.h"),
         os.path.join(_HERE, "csrc", "volume_mesh.hip.h"), os.path.join(_HERE, "csrc", "volume_mesh_table.h"),
@@ -87,9 +89,9 @@ def build(force=False, verbose=False, stamps=False):
     os.makedirs(os.path.dirname(lib), exist_ok=True)
     objdir = os.path.join(os.path.dirname(lib), "obj_stamps" if stamps else "obj")
     os.makedirs(objdir, exist_ok=True)
-    o_main, o_dense, o_batch, o_map, o_rgbd, o_fe, o_vol, o_mesh, o_col, o_ray = (os.path.join(objdir, n) for n in (
+    o_main, o_dense, o_batch, o_map, o_rgbd, o_fe, o_vol, o_mesh, o_col, o_ray, o_icp = (os.path.join(objdir, n) for n in (
         "odometry_hip.o", "dense_kernels.o", "lm_chain_kernels.o", "map_kernels.o", "rgbd_kernels.o", "rgbd_frontend_kernels.o",
-        "volume_kernels.o", "volume_mesh_kernels.o", "volume_colour_kernels.o", "volume_raycast_kernels.o"))
+        "volume_kernels.o", "volume_mesh_kernels.o", "volume_colour_kernels.o", "volume_raycast_kernels.o", "volume_icp_kernels.o"))
     cmds = [[HIPCC] + _flags_for(SRC, flags) + ["-c", "-o", o_main, SRC],
             [HIPCC] + _flags_for(SRC_DENSE, flags) + ["-c", "-o", o_dense, SRC_DENSE],
             [HIPCC] + _flags_for(SRC_CHAIN, flags) + ["-c", "-o", o_batch, SRC_CHAIN],
@@ -100,9 +102,10 @@ def build(force=False, verbose=False, stamps=False):
             [HIPCC] + _flags_for(SRC_VOLUME_MESH, flags) + ["-c", "-o", o_mesh, SRC_VOLUME_MESH],
             [HIPCC] + _flags_for(SRC_VOLUME_COLOUR, flags) + ["-c", "-o", o_col, SRC_VOLUME_COLOUR],
             [HIPCC] + _flags_for(SRC_VOLUME_RAYCAST, flags) + ["-c", "-o", o_ray, SRC_VOLUME_RAYCAST],
-            [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, o_main, o_dense, o_batch, o_map, o_rgbd, o_fe, o_vol, o_mesh, o_col, o_ray]]
+            [HIPCC] + _flags_for(SRC_VOLUME_ICP, flags) + ["-c", "-o", o_icp, SRC_VOLUME_ICP],
+            [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, o_main, o_dense, o_batch, o_map, o_rgbd, o_fe, o_vol, o_mesh, o_col, o_ray, o_icp]]
     procs = []
-    for cmd in cmds[:-1]:   # the ten translation units compile side by side
+    for cmd in cmds[:-1]:   # the eleven translation units compile side by side
         if verbose:
             print(" ".join(cmd))
         procs.append(subprocess.Popen(cmd))

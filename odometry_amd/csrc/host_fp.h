@@ -158,4 +158,23 @@ inline void raycast_frame(const float* A, const float* origin, float vs, float* 
   }
 }
 
+// out = A B for two column-major fp32 4x4 matrices: fp64 from the fp32 entries, ((a_r0 b_0c + a_r1 b_1c) + a_r2 b_2c) + a_r3 b_3c in
+// that order, each entry rounded to fp32 once. out may not alias A or B.
+inline void mul4(const float* A, const float* B, float* out) {
+  for (int c = 0; c < 4; c++)
+    for (int r = 0; r < 4; r++) {
+      const double d = (((double)A[0 * 4 + r] * (double)B[c * 4 + 0] + (double)A[1 * 4 + r] * (double)B[c * 4 + 1]) +
+                        (double)A[2 * 4 + r] * (double)B[c * 4 + 2]) + (double)A[3 * 4 + r] * (double)B[c * 4 + 3];
+      out[c * 4 + r] = (float)d;
+    }
+}
+
+// The frame-to-model alignment's frame (volume_icp_api.hip.h; include/odometry_hip.h, odo_volume_icp_align_dev) of the model
+// camera's camera-to-world pose P_m and the first guess P_init of the sensor camera's: M = invert_rigid(P_m), world to model camera,
+// and C0 = M P_init, sensor camera to model camera. All column-major fp32. The alignment's result goes back as mul4(P_m, C).
+inline void icp_frame(const float* P_m, const float* P_init, float* M, float* C0) {
+  invert_rigid(P_m, M);
+  mul4(M, P_init, C0);
+}
+
 }  // namespace hostfp

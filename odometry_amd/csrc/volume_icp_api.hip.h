@@ -1,0 +1,289 @@
+// volume_icp_api.hip.h — frame-to-model tracking on the TSDF volume (odo_volume_icp_eval_dev, odo_volume_icp_align_dev,
+// odo_volume_track_dev, odo_volume_icp_time_dev): the host side over the kernels of volume_icp_kernels.hip. Included by odometry_hip.hip behind
+// volume_api.hip.h, whose object and helpers it uses and does not change.
+//
+// The alignment's device memory (the state, one partial per block of the finest grid, the trace) lives for one call: allocated on
+// entry, released after the call's single wait. A call costs three allocations beside its launches; the volume object stays as it is.
+#pragma once
+#include <cstddef>
+#include <limits>
+#include "volume_icp.hip.h"
+#include "volume_icp_math.h"
+
+static_assert(sizeof(odo_icp_trace_row) == sizeof(IcpTraceRow) && offsetof(odo_icp_trace_row, acc) == offsetof(IcpTraceRow, acc) &&
+              offsetof(odo_icp_trace_row, delta) == offsetof(IcpTraceRow, delta) && offsetof(odo_icp_trace_row, C) == offsetof(IcpTraceRow, C),
+              "odo_icp_trace_row is the device's IcpTraceRow");
+
+struct IcpScratch {
+  IcpState* state = nullptr;
+  double* partials = nullptr;
+  IcpTraceRow* trace = nullptr;
+  ~IcpScratch() {
+    if (state) (void)hipFree(state);
+    if (partials) (void)hipFree(partials);
+    if (trace) (void)hipFree(trace);
+  }
+};
+
+static int icp_alloc(IcpScratch* sc, int max_blocks, int trace_rows) {
+  if (hipMalloc((void**)&sc->state, sizeof(IcpState)) != hipSuccess ||
+      hipMalloc((void**)&sc->partials, sizeof(double) * ODO_NACC * (size_t)max_blocks) != hipSuccess ||
+      (trace_rows > 0 && hipMalloc((void**)&sc->trace, sizeof(IcpTraceRow) * (size_t)trace_rows) != hipSuccess)) {
+    (void)hipGetLastError();
+    return fail("odo_volume_icp: device allocation failed (%d partials, %d trace rows)", max_blocks, trace_rows);
+  }
+  return 0;
+}
+
+// The volume's own stream behind everything enqueued so far on the context's stream (the upload of the sensor frame) and behind
+// everything that changed the volume.
+static int icp_order(odo_volume* v) {
+  hipEvent_t ev = nullptr;
+  HIP_OK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  const bool ok = hipEventRecord(ev, v->ctx->stream) == hipSuccess && hipStreamWaitEvent(v->own, ev, 0) == hipSuccess;
+  (void)hipEventDestroy(ev);   // (released once it has completed)
+  if (!ok) return fail("odo_volume_icp: ordering behind the context's stream failed");
+  return volume_order_on(v, v->own);
+}
+
+static int icp_blocks(const odo_volume* v, int stride) {
+  const dim3 g = volume_icp_grid(v->p.rows, v->p.cols, stride);
+  return (int)(g.x * g.y);
+}
+
+static bool icp_float_ok(float x, bool positive) { return std::isfinite(x) && (positive ? x > 0.0f : x >= 0.0f); }
+
+static int icp_check_params(const char* who, const odo_icp_params* p) {
+  if (p->levels < 1 || p->levels > kIcpMaxLevels) return fail("%s: levels %d out of range (1 .. 3)", who, p->levels);
+  long total = 0;
+  for (int l = 0; l < p->levels; l++) {
+    if (p->stride[l] < 1 || p->stride[l] > 16) return fail("%s: stride[%d] = %d out of range (1 .. 16)", who, l, p->stride[l]);
+    if (p->iters[l] < 0 || p->iters[l] > 64) return fail("%s: iters[%d] = %d out of range (0 .. 64)", who, l, p->iters[l]);
+    total += p->iters[l];
+  }
+  if (total < 1 || total > 64) return fail("%s: the iterations sum to %ld (1 .. 64)", who, total);
+  if (!icp_float_ok(p->dist_max, true)) return fail("%s: dist_max must be finite and > 0", who);
+  if (!icp_float_ok(p->huber_delta, false)) return fail("%s: huber_delta must be finite and >= 0", who);
+  if (!icp_float_ok(p->eps_t, false) || !icp_float_ok(p->eps_r, false)) return fail("%s: eps_t and eps_r must be finite and >= 0", who);
+  if (p->min_pairs < 6) return fail("%s: min_pairs %d (at least 6)", who, p->min_pairs);
+  if (!(p->min_eig_ratio >= 0.0f && p->min_eig_ratio <= 1.0f)) return fail("%s: min_eig_ratio must lie in 0 .. 1", who);
+  return 0;
+}
+
+static VolIcpRowsArgs icp_rows_args(const odo_volume* v, const float* depth_m, const float* nrmw_m, const uint16_t* raw, const float* M,
+                                    int stride, int level, float dist_max, float huber_delta, const IcpScratch& sc, float* rows_dev) {
+  VolIcpRowsArgs a;
+  memset(&a, 0, sizeof(a));
+  a.raw = raw; a.depth_m = depth_m; a.nrmw_m = nrmw_m;
+  a.rows = v->p.rows; a.cols = v->p.cols;
+  a.f = v->p.K.f0; a.cx = v->p.K.cx0; a.cy = v->p.K.cy0;
+  a.depth_scale = v->p.depth_scale; a.max_depth = v->p.max_depth;
+  a.dist_max = dist_max; a.huber_delta = huber_delta;
+  a.m0 = M[0]; a.m1 = M[4]; a.m2 = M[8]; a.m3 = M[1]; a.m4 = M[5]; a.m5 = M[9]; a.m6 = M[2]; a.m7 = M[6]; a.m8 = M[10];
+  a.stride = stride; a.level = level;
+  a.state = sc.state; a.partials = sc.partials; a.rows_dev = rows_dev;
+  return a;
+}
+
+extern "C" int odo_volume_icp_eval_dev(odo_volume* v, const float* depth_m_dev, const float* nrmw_m_dev, const float model_pose_colmajor[16],
+                                       const uint16_t* raw_dev, const float C_colmajor[16], int stride, float dist_max, float huber_delta,
+                                       double acc[29], float* rows_dev) {
+  const char* who = "odo_volume_icp_eval_dev";
+  if (!v || !depth_m_dev || !nrmw_m_dev || !model_pose_colmajor || !raw_dev || !C_colmajor || !acc) return fail("%s: NULL arg", who);
+  if (((uintptr_t)depth_m_dev & 3) || ((uintptr_t)nrmw_m_dev & 15) || ((uintptr_t)raw_dev & 1) || ((uintptr_t)rows_dev & 15))
+    return fail("%s: misaligned frame (depth 4, nrmw 16, raw 2, rows 16 bytes)", who);
+  if (stride < 1 || stride > 16) return fail("%s: stride %d out of range (1 .. 16)", who, stride);
+  if (!icp_float_ok(dist_max, true)) return fail("%s: dist_max must be finite and > 0", who);
+  if (!icp_float_ok(huber_delta, false)) return fail("%s: huber_delta must be finite and >= 0", who);
+  if (!pose_finite(model_pose_colmajor) || !pose_finite(C_colmajor)) return fail("%s: a pose has a non-finite entry", who);
+  HIP_OK(hipSetDevice(v->device));
+  IcpScratch sc;
+  const int nblk = icp_blocks(v, stride);
+  if (icp_alloc(&sc, nblk, 0)) return -1;
+  if (icp_order(v)) return -1;
+  float M[16];
+  hostfp::invert_rigid(model_pose_colmajor, M);
+  IcpInit init;
+  memcpy(init.C, C_colmajor, sizeof(init.C));
+  launch_volume_icp_init(sc.state, init, v->own);
+  launch_volume_icp_rows(icp_rows_args(v, depth_m_dev, nrmw_m_dev, raw_dev, M, stride, 0, dist_max, huber_delta, sc, rows_dev), v->own);
+  VolIcpStepArgs s;
+  memset(&s, 0, sizeof(s));
+  s.partials = sc.partials; s.nblk = nblk; s.state = sc.state;
+  launch_volume_icp_step(s, v->own);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(acc, (const char*)sc.state + offsetof(IcpState, acc), sizeof(double) * ODO_NACC, hipMemcpyDeviceToHost, v->own));
+  HIP_OK(hipStreamSynchronize(v->own));
+  return 0;
+}
+
+// Event timing of the two kernels (tools/volume_cost.py icp): `reps` launches of the rows kernel at C between two events on the
+// volume's own stream, then `reps` launches of the step kernel's fold (take_step == 0: the state keeps its C). us[0], us[1]: the
+// mean time of one launch of either, microseconds.
+extern "C" int odo_volume_icp_time_dev(odo_volume* v, const float* depth_m_dev, const float* nrmw_m_dev, const float model_pose_colmajor[16],
+                                       const uint16_t* raw_dev, const float C_colmajor[16], int stride, float dist_max, float huber_delta,
+                                       int reps, float us[2]) {
+  const char* who = "odo_volume_icp_time_dev";
+  if (!v || !depth_m_dev || !nrmw_m_dev || !model_pose_colmajor || !raw_dev || !C_colmajor || !us) return fail("%s: NULL arg", who);
+  if (((uintptr_t)depth_m_dev & 3) || ((uintptr_t)nrmw_m_dev & 15) || ((uintptr_t)raw_dev & 1))
+    return fail("%s: misaligned frame (depth 4, nrmw 16, raw 2 bytes)", who);
+  if (stride < 1 || stride > 16 || reps < 1 || reps > 10000) return fail("%s: stride 1 .. 16, reps 1 .. 10000", who);
+  if (!icp_float_ok(dist_max, true) || !icp_float_ok(huber_delta, false)) return fail("%s: dist_max finite > 0, huber_delta finite >= 0", who);
+  if (!pose_finite(model_pose_colmajor) || !pose_finite(C_colmajor)) return fail("%s: a pose has a non-finite entry", who);
+  HIP_OK(hipSetDevice(v->device));
+  IcpScratch sc;
+  const int nblk = icp_blocks(v, stride);
+  if (icp_alloc(&sc, nblk, 0)) return -1;
+  if (icp_order(v)) return -1;
+  float M[16];
+  hostfp::invert_rigid(model_pose_colmajor, M);
+  IcpInit init;
+  memcpy(init.C, C_colmajor, sizeof(init.C));
+  const VolIcpRowsArgs ra = icp_rows_args(v, depth_m_dev, nrmw_m_dev, raw_dev, M, stride, 0, dist_max, huber_delta, sc, nullptr);
+  VolIcpStepArgs sa;
+  memset(&sa, 0, sizeof(sa));
+  sa.partials = sc.partials; sa.nblk = nblk; sa.state = sc.state;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+  bool ok = true;
+  for (auto& e : ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+  if (ok) {
+    launch_volume_icp_init(sc.state, init, v->own);
+    launch_volume_icp_rows(ra, v->own);   // (warm)
+    launch_volume_icp_step(sa, v->own);
+    ok = hipEventRecord(ev[0], v->own) == hipSuccess;
+    for (int i = 0; i < reps; i++) launch_volume_icp_rows(ra, v->own);
+    ok = ok && hipEventRecord(ev[1], v->own) == hipSuccess;
+    for (int i = 0; i < reps; i++) launch_volume_icp_step(sa, v->own);
+    ok = ok && hipEventRecord(ev[2], v->own) == hipSuccess && hipGetLastError() == hipSuccess && hipStreamSynchronize(v->own) == hipSuccess;
+    float ms0 = 0.0f, ms1 = 0.0f;
+    ok = ok && hipEventElapsedTime(&ms0, ev[0], ev[1]) == hipSuccess && hipEventElapsedTime(&ms1, ev[1], ev[2]) == hipSuccess;
+    us[0] = 1e3f * ms0 / (float)reps;
+    us[1] = 1e3f * ms1 / (float)reps;
+  }
+  for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+  if (!ok) {
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(v->own);
+    return fail("%s: timing failed", who);
+  }
+  return 0;
+}
+
+static void icp_nan_pose(float* A) {
+  for (int i = 0; i < 16; i++) A[i] = std::numeric_limits<float>::quiet_NaN();
+}
+
+// The launches and the single wait of one alignment, every argument checked by the caller.
+static int icp_align(odo_volume* v, const odo_icp_params* p, const float* depth_m, const float* nrmw_m, const float* P_m, const uint16_t* raw,
+                     const float* P_init, float* abs_pose, odo_icp_result* res, odo_icp_trace_row* trace, int trace_capacity, int* trace_n) {
+  int total = 0, max_blocks = 1;
+  for (int l = 0; l < p->levels; l++) {
+    total += p->iters[l];
+    max_blocks = std::max(max_blocks, icp_blocks(v, p->stride[l]));
+  }
+  const int trace_rows = trace ? std::min(trace_capacity, total) : 0;
+  IcpScratch sc;
+  if (icp_alloc(&sc, max_blocks, trace_rows)) return -1;
+  if (icp_order(v)) return -1;
+  float M[16];
+  IcpInit init;
+  hostfp::icp_frame(P_m, P_init, M, init.C);
+  launch_volume_icp_init(sc.state, init, v->own);
+  for (int l = 0; l < p->levels; l++) {
+    const VolIcpRowsArgs ra = icp_rows_args(v, depth_m, nrmw_m, raw, M, p->stride[l], l, p->dist_max, p->huber_delta, sc, nullptr);
+    VolIcpStepArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.partials = sc.partials; sa.nblk = icp_blocks(v, p->stride[l]); sa.level = l;
+    sa.min_pairs = p->min_pairs; sa.eps_t = p->eps_t; sa.eps_r = p->eps_r; sa.take_step = 1;
+    sa.state = sc.state; sa.trace = sc.trace; sa.trace_capacity = trace_rows;
+    for (int it = 0; it < p->iters[l]; it++) {
+      launch_volume_icp_rows(ra, v->own);
+      launch_volume_icp_step(sa, v->own);
+    }
+  }
+  HIP_OK(hipGetLastError());
+  IcpState st;
+  HIP_OK(hipMemcpyAsync(&st, sc.state, sizeof(st), hipMemcpyDeviceToHost, v->own));
+  HIP_OK(hipStreamSynchronize(v->own));
+  const int n_rows = std::min(st.trace_n, trace_rows);
+  if (n_rows > 0) {
+    HIP_OK(hipMemcpyAsync(trace, sc.trace, sizeof(IcpTraceRow) * (size_t)n_rows, hipMemcpyDeviceToHost, v->own));
+    HIP_OK(hipStreamSynchronize(v->own));
+  }
+  if (trace_n) *trace_n = n_rows;
+  memset(res, 0, sizeof(*res));
+  res->status = st.status;
+  res->iterations = st.iterations;
+  memcpy(res->C, st.C, sizeof(res->C));
+  if (st.evaluated) {
+    res->pairs = st.acc[28];
+    res->cost = st.acc[27];
+    double ev[6];
+    icp_eigenvalues(st.acc, ev);
+    res->eig_min = ev[0];
+    res->eig_max = ev[5];
+  }
+  if (res->status == 0 && !pose_finite(st.C)) res->status = 1;
+  if (res->status == 0 && (!st.evaluated || res->eig_min < (double)p->min_eig_ratio * res->eig_max)) res->status = st.evaluated ? 2 : 1;
+  if (res->status == 0) hostfp::mul4(P_m, st.C, abs_pose);
+  else icp_nan_pose(abs_pose);
+  return 0;
+}
+
+extern "C" int odo_volume_icp_align_dev(odo_volume* v, const odo_icp_params* p, const float* depth_m_dev, const float* nrmw_m_dev,
+                                        const float model_pose_colmajor[16], const uint16_t* raw_dev, const float init_pose_colmajor[16],
+                                        float abs_pose_colmajor[16], odo_icp_result* result, odo_icp_trace_row* trace, int trace_capacity,
+                                        int* trace_n) {
+  const char* who = "odo_volume_icp_align_dev";
+  if (trace_n) *trace_n = 0;
+  if (!v || !p || !depth_m_dev || !nrmw_m_dev || !model_pose_colmajor || !raw_dev || !init_pose_colmajor || !abs_pose_colmajor || !result)
+    return fail("%s: NULL arg", who);
+  if (trace_capacity < 0 || (trace && trace_capacity < 1)) return fail("%s: a trace buffer needs a capacity >= 1", who);
+  if (((uintptr_t)depth_m_dev & 3) || ((uintptr_t)nrmw_m_dev & 15) || ((uintptr_t)raw_dev & 1))
+    return fail("%s: misaligned frame (depth 4, nrmw 16, raw 2 bytes)", who);
+  if (icp_check_params(who, p)) return -1;
+  if (!pose_finite(model_pose_colmajor) || !pose_finite(init_pose_colmajor)) return fail("%s: a pose has a non-finite entry", who);
+  HIP_OK(hipSetDevice(v->device));
+  return icp_align(v, p, depth_m_dev, nrmw_m_dev, model_pose_colmajor, raw_dev, init_pose_colmajor, abs_pose_colmajor, result, trace,
+                   trace_capacity, trace_n);
+}
+
+// The ray-cast frames that the volume owns (odo_volume_raycast's: depth, raw and normals grow together), for n pixels.
+static int icp_ray_frames(odo_volume* v, long n) {
+  if (n <= v->ray_capacity) return 0;
+  HIP_OK(hipStreamSynchronize(v->own));
+  void* ps[] = {v->d_ray_depth, v->d_ray_raw, v->d_ray_nrmw};
+  for (void* q : ps) if (q) (void)hipFree(q);
+  v->d_ray_depth = nullptr; v->d_ray_raw = nullptr; v->d_ray_nrmw = nullptr; v->ray_capacity = 0;
+  if (hipMalloc((void**)&v->d_ray_depth, sizeof(float) * (size_t)n) != hipSuccess ||
+      hipMalloc((void**)&v->d_ray_raw, sizeof(uint16_t) * (size_t)n) != hipSuccess ||
+      hipMalloc((void**)&v->d_ray_nrmw, sizeof(float4) * (size_t)n) != hipSuccess) {
+    (void)hipGetLastError();
+    void* qs[] = {v->d_ray_depth, v->d_ray_raw, v->d_ray_nrmw};
+    for (void* q : qs) if (q) (void)hipFree(q);
+    v->d_ray_depth = nullptr; v->d_ray_raw = nullptr; v->d_ray_nrmw = nullptr;
+    return fail("odo_volume_track_dev: device allocation failed (%ld pixels)", n);
+  }
+  v->ray_capacity = n;
+  return 0;
+}
+
+extern "C" int odo_volume_track_dev(odo_volume* v, const odo_icp_params* p, const uint16_t* raw_dev, const float prev_pose_colmajor[16],
+                                    float abs_pose_colmajor[16], odo_icp_result* result) {
+  const char* who = "odo_volume_track_dev";
+  if (!v || !p || !raw_dev || !prev_pose_colmajor || !abs_pose_colmajor || !result) return fail("%s: NULL arg", who);
+  if ((uintptr_t)raw_dev & 1) return fail("%s: misaligned frame (raw 2 bytes)", who);
+  if (icp_check_params(who, p)) return -1;
+  odo_raycast_params rp;
+  rp.rows = v->p.rows; rp.cols = v->p.cols;
+  rp.f = v->p.K.f0; rp.cx = v->p.K.cx0; rp.cy = v->p.K.cy0;
+  const double step = (double)v->p.mu / 2;
+  rp.t_min = 0.0f; rp.step = (float)step;
+  rp.n_steps = (int)std::min(4096.0, std::max(1.0, std::ceil(((double)v->p.max_depth + (double)v->p.mu) / step) + 1.0));
+  if (raycast_check(who, &rp, prev_pose_colmajor)) return -1;
+  HIP_OK(hipSetDevice(v->device));
+  if (icp_ray_frames(v, (long)rp.rows * rp.cols)) return -1;
+  if (volume_raycast_launch(v, &rp, prev_pose_colmajor, v->d_ray_depth, nullptr, v->d_ray_nrmw, nullptr)) return -1;
+  return icp_align(v, p, v->d_ray_depth, (const float*)v->d_ray_nrmw, prev_pose_colmajor, raw_dev, prev_pose_colmajor, abs_pose_colmajor,
+                   result, nullptr, 0, nullptr);
+}

@@ -29,7 +29,15 @@
             the pinned grid with a colour grid, every frame's colour named with odo_tracker_frame_colour (the price of colour:
             --modes coloured,pinned,none alternating in one call).
 
+  icp       the frame-to-model alignment's two kernels timed with events (api.TsdfVolume.icp_time: `reps` launches of
+            volume_icp_rows_kernel, then of volume_icp_step_kernel's fold, each batch between two events on the volume's stream):
+            the pinned grid after `frames` integrations at their true poses, the ray-cast from the last pose but one as the model
+            frame, the last frame as the sensor frame, at 480 x 640 and strides 4, 2 and 1. One JSON line per stride with the medians
+            over `runs` batches, the pairs and the blocks, then the wall time of whole api.TsdfVolume.track calls (ray-cast, the
+            alignment's launches, its allocations and its one wait).
+
   python tools/volume_cost.py kernels [--frames 10] [--extractions 3] [--json FILE]
+  python tools/volume_cost.py icp [--frames 10] [--runs 7] [--reps 50]
   python tools/volume_cost.py summary DIR [--json FILE]
   python tools/volume_cost.py track [--runs 3] [--steps 200] [--warmup 20] [--frames 100] [--modes none,pinned,large[,coloured]]
 
@@ -216,6 +224,37 @@ def track(args):
     trk.close()
 
 
+def icp(args):
+    from odometry_amd import api, synth
+    seq = synth.make_rgbd_sequence(args.frames, seed=0)
+    K = (seq["K"]["f0"], seq["K"]["cx0"], seq["K"]["cy0"])
+    ctx = api.Context(0)
+    vol = make_volume(ctx, "pinned", (synth.TUM_ROWS, synth.TUM_COLS), K)
+    for d, A in zip(seq["depth"][:-1], seq["poses"][:-1]):
+        vol.integrate(d, A)
+    P_m = seq["poses"][-2]
+    depth, nrmw = vol.raycast(P_m)
+    raw = seq["depth"][-1]
+    for stride in (4, 2, 1):
+        acc = vol.icp_eval(raw, depth, nrmw, P_m, np.eye(4), stride=stride)
+        us = np.array([vol.icp_time(raw, depth, nrmw, P_m, np.eye(4), stride=stride, reps=args.reps) for _ in range(args.runs)])
+        lattice = (-(-synth.TUM_ROWS // stride)) * (-(-synth.TUM_COLS // stride))
+        print(json.dumps(dict(stride=stride, lattice=lattice, pairs=int(acc[28]), blocks=(-(-(-(-synth.TUM_ROWS // stride)) // 16)) * (-(-(-(-synth.TUM_COLS // stride)) // 16)),
+                              rows_us_median=round(float(np.median(us[:, 0])), 2), rows_us_min_max=[round(float(us[:, 0].min()), 2), round(float(us[:, 0].max()), 2)],
+                              step_fold_us_median=round(float(np.median(us[:, 1])), 2),
+                              step_fold_us_min_max=[round(float(us[:, 1].min()), 2), round(float(us[:, 1].max()), 2)])), flush=True)
+    wall = []
+    for _ in range(args.runs):
+        t0 = time.perf_counter()
+        pose, res = vol.track(raw, P_m)
+        wall.append(1e3 * (time.perf_counter() - t0))
+    print(json.dumps(dict(track_call_ms_median=round(float(np.median(wall)), 3), track_call_ms_min_max=[round(min(wall), 3), round(max(wall), 3)],
+                          status=res["status"], iterations=res["iterations"], pairs=res["pairs"], eig_ratio=res["eig_min"] / res["eig_max"] if res["eig_max"] else None)),
+          flush=True)
+    vol.close()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -232,8 +271,12 @@ def main():
     t.add_argument("--warmup", type=int, default=20)
     t.add_argument("--frames", type=int, default=100)
     t.add_argument("--modes", default="none,pinned,large")
+    i = sub.add_parser("icp")
+    i.add_argument("--frames", type=int, default=10)
+    i.add_argument("--runs", type=int, default=7)
+    i.add_argument("--reps", type=int, default=50)
     args = ap.parse_args()
-    dict(kernels=kernels, summary=summary, track=track)[args.cmd](args)
+    dict(kernels=kernels, summary=summary, track=track, icp=icp)[args.cmd](args)
 
 
 if __name__ == "__main__":
