@@ -16,26 +16,21 @@ import os
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(_HERE, "csrc", "odometry_hip.hip")
-SRC_DENSE = os.path.join(_HERE, "csrc", "dense_kernels.hip")   # its own translation unit (see dense.hip.h)
-SRC_CHAIN = os.path.join(_HERE, "csrc", "lm_chain_kernels.hip")   # the single tracker's LM chain: its own unit AND its own scheduler
-SRC_MAP = os.path.join(_HERE, "csrc", "map_kernels.hip")   # the keyframe map's insertion kernels (map.hip.h): the main unit's scheduler
-SRC_RGBD = os.path.join(_HERE, "csrc", "rgbd_kernels.hip")   # the RGB-D tracker's sensor-depth kernels (rgbd.hip.h): the main unit's scheduler
-SRC_FRONTEND = os.path.join(_HERE, "csrc", "rgbd_frontend_kernels.hip")   # the RGB-D front end's kernels (rgbd_frontend.hip.h): the main unit's scheduler
-SRC_VOLUME = os.path.join(_HERE, "csrc", "volume_kernels.hip")   # the TSDF volume's kernels (volume.hip.h): the main unit's scheduler
-SRC_VOLUME_MESH = os.path.join(_HERE, "csrc", "volume_mesh_kernels.hip")   # the volume's mesh kernels (volume_mesh.hip.h): the main unit's scheduler
-SRC_VOLUME_COLOUR = os.path.join(_HERE, "csrc", "volume_colour_kernels.hip")   # the volume's colour kernels (volume_colour.hip.h): the main unit's scheduler
-SRC_VOLUME_RAYCAST = os.path.join(_HERE, "csrc", "volume_raycast_kernels.hip")   # the volume's ray-cast kernel (volume_raycast.hip.h): the main unit's scheduler
-SRC_VOLUME_ICP = os.path.join(_HERE, "csrc", "volume_icp_kernels.hip")   # the volume's frame-to-model alignment kernels (volume_icp.hip.h): the main unit's scheduler
-DEPS = [SRC, SRC_DENSE, SRC_CHAIN, SRC_MAP, SRC_RGBD, SRC_FRONTEND, SRC_VOLUME, SRC_VOLUME_MESH, SRC_VOLUME_COLOUR, SRC_VOLUME_RAYCAST, SRC_VOLUME_ICP, os.path.join(_HERE, "csrc", "volume.hip.h"),
-        os.path.join(_HERE, "csrc", "volume_icp.hip.h"), os.path.join(_HERE, "csrc", "volume_icp_math.h"), os.path.join(_HERE, "csrc", "volume_icp_api.hip.h"),
-        os.path.join(_HERE, "csrc", "volume_raycast.hip.h"), os.path.join(_HERE, "csrc", "volume_raycast_math.h"),
-        os.path.join(_HERE, "csrc", "volume_colour.hip.h"), os.path.join(_HERE, "csrc", "volume_colour_math.h"),
-        os.path.join(_HERE, "csrc", "volume_mesh.hip.h"), os.path.join(_HERE, "csrc", "volume_mesh_table.h"),
-        os.path.join(_HERE, "csrc", "volume_api.hip.h"), os.path.join(_HERE, "csrc", "rgbd_frontend.hip.h"),
-        os.path.join(_HERE, "csrc", "rgbd_frontend_api.hip.h"), os.path.join(_HERE, "csrc", "rgbd.hip.h"), os.path.join(_HERE, "csrc", "map.hip.h"), os.path.join(_HERE, "csrc", "map_api.hip.h"), os.path.join(_HERE, "csrc", "kernels.hip.h"), os.path.join(_HERE, "csrc", "odo_math.h"), os.path.join(_HERE, "csrc", "tracker.hip.h"), os.path.join(_HERE, "csrc", "batch.hip.h"), os.path.join(_HERE, "csrc", "gather.hip.h"), os.path.join(_HERE, "csrc", "camera.hip.h"), os.path.join(_HERE, "csrc", "camera_math.h"),
-        os.path.join(_HERE, "csrc", "dense.hip.h"), os.path.join(_HERE, "csrc", "host_fp.h"),
-        os.path.join(os.path.dirname(_HERE), "include", "odometry_hip.h"), os.path.abspath(__file__)]   # (this file: the flags)
+_CSRC = os.path.join(_HERE, "csrc")
+SRC = os.path.join(_CSRC, "odometry_hip.hip")
+SRC_CHAIN = os.path.join(_CSRC, "lm_chain_kernels.hip")   # the single tracker's LM chain: its own unit AND its own scheduler
+SRC_DENSE = os.path.join(_CSRC, "dense_kernels.hip")      # its own translation unit (see dense.hip.h), optionally its own scheduler
+
+
+def _deps():
+    """Every header and source under csrc/ (subfolders included), the public header and this file (the flags)."""
+    out = [os.path.join(os.path.dirname(_HERE), "include", "odometry_hip.h"), os.path.abspath(__file__)]
+    for root, _, files in os.walk(_CSRC):
+        out += [os.path.join(root, f) for f in sorted(files) if f.endswith((".h", ".hip"))]
+    return out
+
+
+DEPS = _deps()
 LIB = os.path.join(_HERE, "lib", "libodometry_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
@@ -52,10 +47,15 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", "-fn
 # Hence lm_chain_kernels.hip (ODO_SCHED_CHAIN, iterative-ilp) beside the main unit (ODO_SCHED, iterative-maxocc).
 SCHED_CHAIN = os.environ.get("ODO_SCHED_CHAIN", "iterative-ilp")
 SCHED_DENSE = os.environ.get("ODO_SCHED_DENSE", "")   # dense_kernels.hip: "" = the main unit's
+# The translation units: (source, its scheduler override; "" = the main unit's scheduler). Every kernel family has a unit of its own (see
+# the header of each file); object names and command lines are derived from this list.
+UNITS = [(SRC, ""), (SRC_DENSE, SCHED_DENSE), (SRC_CHAIN, SCHED_CHAIN)] + [(os.path.join(_CSRC, n), "") for n in (
+    "map_kernels.hip", "rgbd_kernels.hip", "rgbd_frontend_kernels.hip", "volume_kernels.hip", "volume_mesh_kernels.hip",
+    "volume_colour_kernels.hip", "volume_raycast_kernels.hip", "volume_icp_kernels.hip")]
 
 
 def _flags_for(src, flags):
-    sched = SCHED_CHAIN if src == SRC_CHAIN else SCHED_DENSE if src == SRC_DENSE else ""
+    sched = dict(UNITS).get(src, "")
     if not sched:
         return flags
     if sched == "default":   # the compiler's own choice: drop the option (and the -mllvm in front of it)
@@ -89,23 +89,11 @@ def build(force=False, verbose=False, stamps=False):
     os.makedirs(os.path.dirname(lib), exist_ok=True)
     objdir = os.path.join(os.path.dirname(lib), "obj_stamps" if stamps else "obj")
     os.makedirs(objdir, exist_ok=True)
-    o_main, o_dense, o_batch, o_map, o_rgbd, o_fe, o_vol, o_mesh, o_col, o_ray, o_icp = (os.path.join(objdir, n) for n in (
-        "odometry_hip.o", "dense_kernels.o", "lm_chain_kernels.o", "map_kernels.o", "rgbd_kernels.o", "rgbd_frontend_kernels.o",
-        "volume_kernels.o", "volume_mesh_kernels.o", "volume_colour_kernels.o", "volume_raycast_kernels.o", "volume_icp_kernels.o"))
-    cmds = [[HIPCC] + _flags_for(SRC, flags) + ["-c", "-o", o_main, SRC],
-            [HIPCC] + _flags_for(SRC_DENSE, flags) + ["-c", "-o", o_dense, SRC_DENSE],
-            [HIPCC] + _flags_for(SRC_CHAIN, flags) + ["-c", "-o", o_batch, SRC_CHAIN],
-            [HIPCC] + _flags_for(SRC_MAP, flags) + ["-c", "-o", o_map, SRC_MAP],
-            [HIPCC] + _flags_for(SRC_RGBD, flags) + ["-c", "-o", o_rgbd, SRC_RGBD],
-            [HIPCC] + _flags_for(SRC_FRONTEND, flags) + ["-c", "-o", o_fe, SRC_FRONTEND],
-            [HIPCC] + _flags_for(SRC_VOLUME, flags) + ["-c", "-o", o_vol, SRC_VOLUME],
-            [HIPCC] + _flags_for(SRC_VOLUME_MESH, flags) + ["-c", "-o", o_mesh, SRC_VOLUME_MESH],
-            [HIPCC] + _flags_for(SRC_VOLUME_COLOUR, flags) + ["-c", "-o", o_col, SRC_VOLUME_COLOUR],
-            [HIPCC] + _flags_for(SRC_VOLUME_RAYCAST, flags) + ["-c", "-o", o_ray, SRC_VOLUME_RAYCAST],
-            [HIPCC] + _flags_for(SRC_VOLUME_ICP, flags) + ["-c", "-o", o_icp, SRC_VOLUME_ICP],
-            [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, o_main, o_dense, o_batch, o_map, o_rgbd, o_fe, o_vol, o_mesh, o_col, o_ray, o_icp]]
+    objs = [os.path.join(objdir, os.path.splitext(os.path.basename(src))[0] + ".o") for src, _ in UNITS]
+    cmds = [[HIPCC] + _flags_for(src, flags) + ["-c", "-o", obj, src] for (src, _), obj in zip(UNITS, objs)]
+    cmds.append([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs)
     procs = []
-    for cmd in cmds[:-1]:   # the eleven translation units compile side by side
+    for cmd in cmds[:-1]:   # the translation units compile side by side
         if verbose:
             print(" ".join(cmd))
         procs.append(subprocess.Popen(cmd))

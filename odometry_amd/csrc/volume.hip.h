@@ -1,8 +1,8 @@
 // volume.hip.h — what the TSDF volume's kernels (volume_kernels.hip, a translation unit of their own) and its host object
 // (volume_api.hip.h, in the main unit) share: the launch arguments, the device-resident counters and the launchers.
 //
-// A voxel is 4 bytes, {int16 q, uint16 w} = one 32-bit word (q in the low half): q = truncated signed distance * 32767, w = weight,
-// 0 = never observed. Voxel (i, j, k) is word (k * ny + j) * nx + i.
+// The voxel word, the grid and every piece of voxel arithmetic are volume_math.h's (host + device); the kernels add the walk, the
+// loads and the stores.
 //
 // One integration (odo_volume_integrate_dev) = two launches, no host synchronisation, no atomics:
 //   integrate  a grid-stride launch of at most kVolMaxBlocks blocks over tiles of 64 (x) by 4 (y) voxels: a wave's voxels are 64
@@ -10,12 +10,17 @@
 //              block leaves its two counts (updated, in band) in a row of its own. The stride is added to the tile's three digits
 //              (x tile, y tile, k): no division in the loop.
 //   sum        one block adds the rows into the counters.
+// A coloured integration (odo_volume_integrate_colour_dev) is the same two launches: volume_integrate_colour_kernel is the same body
+// with the colour update compiled in. A lane in the band (|sdf| <= mu) also loads the colour pixel its depth reading came from (a
+// 16-bit and a byte load, or one dword with 4 channels) and its colour word (the neighbour of its voxel word: as coalesced as the
+// grid) in front of the voxel's load, and behind the voxel's store applies volume_colour_math.h and stores one dword.
 // One extraction (odo_volume_extract) = three launches, the map's shape: count (three ballot words per wave: the +x, +y, +z edges
 // that carry a point), scan (one block: exclusive offsets of the blocks, totals, the clamp at capacity), scatter (points and
 // normals at block offset + rank in the block). Output order = (voxel in raster order, axis); nothing depends on timing.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "volume_math.h"
 
 namespace odo {
 
@@ -33,21 +38,10 @@ struct VolCounters {
   unsigned long long ext_total, ext_written;   // the last extraction: points found, points written (<= capacity)
 };
 
-struct VolGrid {
-  uint32_t* vox;   // [nx * ny * nz]
-  int nx, ny, nz;
-  float vs, ox, oy, oz;
-};
-
 struct VolIntegrateArgs {
   VolGrid g;
   const uint16_t* raw;   // rows x cols depth frame
-  int rows, cols;
-  float f0, cx0, cy0;
-  float depth_scale, max_depth, mu;
-  int max_weight;
-  float m0, m1, m2, m4, m5, m6, m8, m9, m10, m12, m13, m14;   // world-to-camera, column-major indices
-  float zc_far;   // the kernel's early-out: 1.001 (max_depth + mu)
+  VolFrame f;
   int tiles_x, tiles_y;   // ceil(nx / 64), ceil(ny / 4)
   long long tiles;        // tiles_x * tiles_y * nz
   int nblk;               // blocks of the launch (<= kVolMaxBlocks)
@@ -69,8 +63,22 @@ struct VolExtractArgs {
   float4* nrmw;   // [capacity]
 };
 
-void launch_volume_integrate(const VolIntegrateArgs& a, hipStream_t s);
-void launch_volume_sum(const VolIntegrateArgs& a, hipStream_t s);   // the sum alone: behind the coloured integration (volume_colour.hip.h)
+// The colour grid (volume_colour.hip.h) and the colour frame of a coloured integration.
+struct VolColourFrame {
+  uint32_t* col;          // [nx * ny * nz]: {R, G, B, wc}
+  const uint8_t* pix;     // rows x cols x channels, dense
+  int channels;           // 3 | 4
+  int bgr;                // 0: R first, 1: B first
+  int max_weight;         // 1 .. 255
+};
+
+struct VolIntegrateColourArgs {
+  VolIntegrateArgs a;
+  VolColourFrame c;
+};
+
+void launch_volume_integrate(const VolIntegrateArgs& a, hipStream_t s);                      // integrate, sum
+void launch_volume_integrate_colour(const VolIntegrateColourArgs& a, hipStream_t s);         // likewise
 void launch_volume_extract(const VolExtractArgs& a, hipStream_t s);
 
 }  // namespace odo

@@ -19,11 +19,12 @@ struct odo_volume {
   uint32_t* d_vox;
   unsigned long long* d_blk;    // integrate: the blocks' rows
   VolCounters* d_ctr;
-  // extraction (sized on first use, the point buffers grown on demand)
+  // Every buffer that is grown on demand (volume_grow) has a capacity of its own, in items.
+  // extraction (the scratch sized on first use, the point buffers grown on demand)
   unsigned long long *d_wave, *d_off;
   int* d_cnt;
   float4 *d_xyz0, *d_nrmw;
-  long ext_capacity;
+  long xyz0_capacity, nrmw_capacity;
   // mesh (the scratch sized on first use: 5 B per voxel; the output buffers grown on demand)
   uint8_t* d_mesh_mask;
   uint32_t* d_mesh_base;
@@ -32,7 +33,7 @@ struct odo_volume {
   MeshCounters* d_mesh_ctr;
   float4 *d_mesh_xyz0, *d_mesh_nrmw;
   int* d_mesh_tri;
-  long mesh_vertex_capacity, mesh_triangle_capacity;
+  long mesh_xyz0_capacity, mesh_nrmw_capacity, mesh_triangle_capacity;
   long n_frames;                // integrations since create / clear
   odo_tracker* attached;
   // colour (odo_volume_enable_colour; nothing below is allocated without it)
@@ -46,7 +47,7 @@ struct odo_volume {
   uint16_t* d_ray_raw;
   float4* d_ray_nrmw;
   uint32_t* d_ray_rgba;
-  long ray_capacity, ray_rgba_capacity;   // pixels
+  long ray_depth_capacity, ray_raw_capacity, ray_nrmw_capacity, ray_rgba_capacity;   // pixels
 };
 
 static int volume_release(odo_volume* v) {
@@ -102,18 +103,9 @@ extern "C" int odo_volume_create(odo_ctx* ctx, const odo_volume_params* p, odo_v
   HIP_OK(hipSetDevice(ctx->device));
   odo_volume* v = new (std::nothrow) odo_volume();
   if (!v) return fail("out of memory");
-  v->ctx = ctx; v->device = ctx->device; v->own = nullptr; v->ev_last = nullptr; v->last = nullptr;
+  v->ctx = ctx; v->device = ctx->device;   // (everything else is zero: new odo_volume())
   v->p = *p;
   v->n_vox = (long)p->nx * p->ny * p->nz;
-  v->d_vox = nullptr; v->d_blk = nullptr; v->d_ctr = nullptr;
-  v->d_wave = v->d_off = nullptr; v->d_cnt = nullptr; v->d_xyz0 = v->d_nrmw = nullptr; v->ext_capacity = 0;
-  v->d_mesh_mask = nullptr; v->d_mesh_base = nullptr; v->d_mesh_cnt = nullptr; v->d_mesh_off = nullptr; v->d_mesh_ctr = nullptr;
-  v->d_mesh_xyz0 = v->d_mesh_nrmw = nullptr; v->d_mesh_tri = nullptr; v->mesh_vertex_capacity = v->mesh_triangle_capacity = 0;
-  v->n_frames = 0; v->attached = nullptr;
-  v->colour = 0; memset(&v->cp, 0, sizeof(v->cp)); v->d_col = nullptr; v->d_rgba = v->d_mesh_rgba = nullptr;
-  v->rgba_capacity = v->mesh_rgba_capacity = 0;
-  v->d_ray_depth = nullptr; v->d_ray_raw = nullptr; v->d_ray_nrmw = nullptr; v->d_ray_rgba = nullptr;
-  v->ray_capacity = v->ray_rgba_capacity = 0;
   bool ok = hipStreamCreateWithFlags(&v->own, hipStreamNonBlocking) == hipSuccess &&
             hipEventCreateWithFlags(&v->ev_last, hipEventDisableTiming) == hipSuccess &&
             hipMalloc((void**)&v->d_vox, sizeof(uint32_t) * (size_t)v->n_vox) == hipSuccess &&
@@ -152,12 +144,14 @@ static int volume_integrate(odo_volume* v, const uint16_t* depth, const float* A
   VolIntegrateArgs a;
   memset(&a, 0, sizeof(a));
   a.g = volume_grid(v);
-  a.raw = depth; a.rows = v->p.rows; a.cols = v->p.cols;
-  a.f0 = v->p.K.f0; a.cx0 = v->p.K.cx0; a.cy0 = v->p.K.cy0;
-  a.depth_scale = v->p.depth_scale; a.max_depth = v->p.max_depth; a.mu = v->p.mu; a.max_weight = v->p.max_weight;
-  a.m0 = M[0]; a.m1 = M[1]; a.m2 = M[2]; a.m4 = M[4]; a.m5 = M[5]; a.m6 = M[6];
-  a.m8 = M[8]; a.m9 = M[9]; a.m10 = M[10]; a.m12 = M[12]; a.m13 = M[13]; a.m14 = M[14];
-  a.zc_far = (v->p.max_depth + v->p.mu) * 1.001f;
+  a.raw = depth;
+  VolFrame& f = a.f;
+  f.rows = v->p.rows; f.cols = v->p.cols;
+  f.f0 = v->p.K.f0; f.cx0 = v->p.K.cx0; f.cy0 = v->p.K.cy0;
+  f.depth_scale = v->p.depth_scale; f.max_depth = v->p.max_depth; f.mu = v->p.mu; f.max_weight = v->p.max_weight;
+  f.m0 = M[0]; f.m1 = M[1]; f.m2 = M[2]; f.m4 = M[4]; f.m5 = M[5]; f.m6 = M[6];
+  f.m8 = M[8]; f.m9 = M[9]; f.m10 = M[10]; f.m12 = M[12]; f.m13 = M[13]; f.m14 = M[14];
+  f.zc_far = (v->p.max_depth + v->p.mu) * 1.001f;
   a.tiles_x = (v->p.nx + kVolTileX - 1) / kVolTileX;
   a.tiles_y = (v->p.ny + kVolTileY - 1) / kVolTileY;
   a.tiles = (long long)a.tiles_x * a.tiles_y * v->p.nz;
@@ -169,7 +163,6 @@ static int volume_integrate(odo_volume* v, const uint16_t* depth, const float* A
     ac.a = a;
     ac.c.col = v->d_col; ac.c.pix = colour; ac.c.channels = v->cp.channels; ac.c.bgr = v->cp.bgr; ac.c.max_weight = v->cp.max_weight;
     launch_volume_integrate_colour(ac, s);
-    launch_volume_sum(a, s);
   } else {
     launch_volume_integrate(a, s);
   }
@@ -258,23 +251,28 @@ extern "C" int odo_volume_stats(odo_volume* v, long out[4]) {
   return 0;
 }
 
-// Grows one of the mesh's output buffers to `count` items of `item` bytes; *have = its capacity in items.
-static int volume_mesh_grow(void** p, long* have, long count, size_t item, const char* what) {
+// Grows one device buffer to `count` items of `item` bytes; *have = its capacity in items. The caller has waited for whatever used the
+// buffer. After a failure the buffer is empty (nullptr, capacity 0): the volume stays usable and releases everything at destroy.
+static int volume_grow(void** p, long* have, long count, size_t item, const char* who, const char* what) {
   if (count <= *have) return 0;
   if (*p) (void)hipFree(*p);
   *p = nullptr; *have = 0;
   if (hipMalloc(p, item * (size_t)count) != hipSuccess) {
     (void)hipGetLastError();
     *p = nullptr;
-    return fail("odo_volume_mesh: device allocation failed (%ld %s)", count, what);
+    return fail("%s: device allocation failed (%ld %s)", who, count, what);
   }
   *have = count;
   return 0;
 }
 
-// The three launches into the volume's own buffers; *n_points = points written, *n_dropped = points beyond capacity.
-// with_colour: one launch more, the points' colours into d_rgba (skipped when no point is written).
-static int volume_extract_dev(odo_volume* v, long capacity, long* n_points, long* n_dropped, bool with_colour = false) {
+// odo_volume_extract and, with_colour, odo_volume_extract_colour: the three launches into the volume's own buffers and, with_colour,
+// one launch more, the points' colours into d_rgba (skipped when no point is written).
+static int volume_extract(const char* who, odo_volume* v, long capacity, float* xyz0, float* nrmw, uint8_t* rgba, long* n_points,
+                          long* n_dropped, bool with_colour) {
+  if (!v || !n_points || capacity < 0 || capacity > (1L << 28) || (capacity > 0 && (!xyz0 || !nrmw || (with_colour && !rgba))))
+    return fail("%s: bad arg (capacity 0 .. 2^28, buffers for `capacity` points)", who);
+  if (with_colour && !v->colour) return fail("%s: the volume has no colour grid (odo_volume_enable_colour first)", who);
   if (volume_sync(v)) return -1;
   const int nblk = (int)((v->n_vox + kVolExtBlock - 1) / kVolExtBlock);
   if (!v->d_cnt) {
@@ -287,23 +285,13 @@ static int volume_extract_dev(odo_volume* v, long capacity, long* n_points, long
       if (v->d_off) (void)hipFree(v->d_off);
       if (v->d_cnt) (void)hipFree(v->d_cnt);
       v->d_wave = v->d_off = nullptr; v->d_cnt = nullptr;
-      return fail("odo_volume_extract: device allocation failed (%d blocks)", nblk);
+      return fail("%s: device allocation failed (%d blocks)", who, nblk);
     }
   }
-  if (capacity > v->ext_capacity) {
-    if (v->d_xyz0) (void)hipFree(v->d_xyz0);
-    if (v->d_nrmw) (void)hipFree(v->d_nrmw);
-    v->d_xyz0 = v->d_nrmw = nullptr; v->ext_capacity = 0;
-    if (hipMalloc((void**)&v->d_xyz0, sizeof(float4) * (size_t)capacity) != hipSuccess ||
-        hipMalloc((void**)&v->d_nrmw, sizeof(float4) * (size_t)capacity) != hipSuccess) {
-      (void)hipGetLastError();
-      if (v->d_xyz0) (void)hipFree(v->d_xyz0);
-      v->d_xyz0 = v->d_nrmw = nullptr;
-      return fail("odo_volume_extract: device allocation failed (%ld points)", capacity);
-    }
-    v->ext_capacity = capacity;
-  }
-  if (with_colour && volume_mesh_grow((void**)&v->d_rgba, &v->rgba_capacity, capacity, sizeof(uint32_t), "point colours")) return -1;
+  if (volume_grow((void**)&v->d_xyz0, &v->xyz0_capacity, capacity, sizeof(float4), who, "points") ||
+      volume_grow((void**)&v->d_nrmw, &v->nrmw_capacity, capacity, sizeof(float4), who, "points") ||
+      (with_colour && volume_grow((void**)&v->d_rgba, &v->rgba_capacity, capacity, sizeof(uint32_t), who, "point colours")))
+    return -1;
   VolExtractArgs a;
   memset(&a, 0, sizeof(a));
   a.g = volume_grid(v);
@@ -315,48 +303,31 @@ static int volume_extract_dev(odo_volume* v, long capacity, long* n_points, long
   VolCounters c;
   HIP_OK(hipMemcpyAsync(&c, v->d_ctr, sizeof(VolCounters), hipMemcpyDeviceToHost, v->own));
   HIP_OK(hipStreamSynchronize(v->own));
-  *n_points = (long)c.ext_written;
-  *n_dropped = (long)(c.ext_total - c.ext_written);
-  if (with_colour && c.ext_written > 0) {
-    VolExtractColourArgs ac;
-    ac.a = a; ac.col = v->d_col; ac.rgba = v->d_rgba;
-    launch_volume_extract_colour(ac, v->own);
-    HIP_OK(hipGetLastError());
+  const size_t n = (size_t)c.ext_written;
+  if (n > 0) {
+    if (with_colour) {
+      VolExtractColourArgs ac;
+      ac.a = a; ac.col = v->d_col; ac.rgba = v->d_rgba;
+      launch_volume_extract_colour(ac, v->own);
+      HIP_OK(hipGetLastError());
+    }
+    HIP_OK(hipMemcpyAsync(xyz0, v->d_xyz0, sizeof(float4) * n, hipMemcpyDeviceToHost, v->own));
+    HIP_OK(hipMemcpyAsync(nrmw, v->d_nrmw, sizeof(float4) * n, hipMemcpyDeviceToHost, v->own));
+    if (with_colour) HIP_OK(hipMemcpyAsync(rgba, v->d_rgba, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, v->own));
+    HIP_OK(hipStreamSynchronize(v->own));
   }
+  *n_points = (long)c.ext_written;
+  if (n_dropped) *n_dropped = (long)(c.ext_total - c.ext_written);
   return 0;
 }
 
 extern "C" int odo_volume_extract(odo_volume* v, long capacity, float* xyz0, float* nrmw, long* n_points, long* n_dropped) {
-  if (!v || !n_points || capacity < 0 || capacity > (1L << 28) || (capacity > 0 && (!xyz0 || !nrmw)))
-    return fail("odo_volume_extract: bad arg (capacity 0 .. 2^28, buffers for `capacity` points)");
-  long n = 0, d = 0;
-  if (volume_extract_dev(v, capacity, &n, &d)) return -1;
-  if (n > 0) {
-    HIP_OK(hipMemcpyAsync(xyz0, v->d_xyz0, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, v->own));
-    HIP_OK(hipMemcpyAsync(nrmw, v->d_nrmw, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, v->own));
-    HIP_OK(hipStreamSynchronize(v->own));
-  }
-  *n_points = n;
-  if (n_dropped) *n_dropped = d;
-  return 0;
+  return volume_extract("odo_volume_extract", v, capacity, xyz0, nrmw, nullptr, n_points, n_dropped, false);
 }
 
 extern "C" int odo_volume_extract_colour(odo_volume* v, long capacity, float* xyz0, float* nrmw, uint8_t* rgba, long* n_points,
                                          long* n_dropped) {
-  if (!v || !n_points || capacity < 0 || capacity > (1L << 28) || (capacity > 0 && (!xyz0 || !nrmw || !rgba)))
-    return fail("odo_volume_extract_colour: bad arg (capacity 0 .. 2^28, buffers for `capacity` points)");
-  if (!v->colour) return fail("odo_volume_extract_colour: the volume has no colour grid (odo_volume_enable_colour first)");
-  long n = 0, d = 0;
-  if (volume_extract_dev(v, capacity, &n, &d, true)) return -1;
-  if (n > 0) {
-    HIP_OK(hipMemcpyAsync(xyz0, v->d_xyz0, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, v->own));
-    HIP_OK(hipMemcpyAsync(nrmw, v->d_nrmw, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, v->own));
-    HIP_OK(hipMemcpyAsync(rgba, v->d_rgba, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, v->own));
-    HIP_OK(hipStreamSynchronize(v->own));
-  }
-  *n_points = n;
-  if (n_dropped) *n_dropped = d;
-  return 0;
+  return volume_extract("odo_volume_extract_colour", v, capacity, xyz0, nrmw, rgba, n_points, n_dropped, true);
 }
 
 extern "C" int odo_volume_download(odo_volume* v, int16_t* q, uint16_t* w) {
@@ -388,8 +359,12 @@ extern "C" int odo_volume_upload(odo_volume* v, const int16_t* q, const uint16_t
 }
 
 // odo_volume_mesh and, with_colour, odo_volume_mesh_colour (one launch more: the vertices' colours, skipped when no vertex is written).
-static int volume_mesh(odo_volume* v, long vertex_capacity, long triangle_capacity, float* xyz0, float* nrmw, uint8_t* rgba, int32_t* tri,
-                       long counts[4], bool with_colour) {
+static int volume_mesh(const char* who, odo_volume* v, long vertex_capacity, long triangle_capacity, float* xyz0, float* nrmw, uint8_t* rgba,
+                       int32_t* tri, long counts[4], bool with_colour) {
+  if (!v || !counts || vertex_capacity < 0 || vertex_capacity > (1L << 28) || triangle_capacity < 0 || triangle_capacity > (1L << 28) ||
+      (vertex_capacity > 0 && (!xyz0 || !nrmw || (with_colour && !rgba))) || (triangle_capacity > 0 && !tri))
+    return fail("%s: bad arg (capacities 0 .. 2^28, buffers for `vertex_capacity` vertices and `triangle_capacity` triangles)", who);
+  if (with_colour && !v->colour) return fail("%s: the volume has no colour grid (odo_volume_enable_colour first)", who);
   if (volume_sync(v)) return -1;
   const int nblk = (int)((v->n_vox + kMeshBlock - 1) / kMeshBlock);
   if (!v->d_mesh_ctr) {
@@ -403,16 +378,14 @@ static int volume_mesh(odo_volume* v, long vertex_capacity, long triangle_capaci
       void* ps[] = {v->d_mesh_mask, v->d_mesh_base, v->d_mesh_cnt, v->d_mesh_off, v->d_mesh_ctr};
       for (void* p : ps) if (p) (void)hipFree(p);
       v->d_mesh_mask = nullptr; v->d_mesh_base = nullptr; v->d_mesh_cnt = nullptr; v->d_mesh_off = nullptr; v->d_mesh_ctr = nullptr;
-      return fail("odo_volume_mesh: device allocation failed (scratch for %ld voxels)", v->n_vox);
+      return fail("%s: device allocation failed (scratch for %ld voxels)", who, v->n_vox);
     }
   }
-  long have = v->mesh_vertex_capacity;
-  if (volume_mesh_grow((void**)&v->d_mesh_xyz0, &have, vertex_capacity, sizeof(float4), "vertices")) { v->mesh_vertex_capacity = 0; return -1; }
-  have = v->mesh_vertex_capacity;
-  if (volume_mesh_grow((void**)&v->d_mesh_nrmw, &have, vertex_capacity, sizeof(float4), "vertices")) { v->mesh_vertex_capacity = 0; return -1; }
-  v->mesh_vertex_capacity = have;
-  if (volume_mesh_grow((void**)&v->d_mesh_tri, &v->mesh_triangle_capacity, triangle_capacity, 3 * sizeof(int32_t), "triangles")) return -1;
-  if (with_colour && volume_mesh_grow((void**)&v->d_mesh_rgba, &v->mesh_rgba_capacity, vertex_capacity, sizeof(uint32_t), "vertex colours")) return -1;
+  if (volume_grow((void**)&v->d_mesh_xyz0, &v->mesh_xyz0_capacity, vertex_capacity, sizeof(float4), who, "vertices") ||
+      volume_grow((void**)&v->d_mesh_nrmw, &v->mesh_nrmw_capacity, vertex_capacity, sizeof(float4), who, "vertices") ||
+      volume_grow((void**)&v->d_mesh_tri, &v->mesh_triangle_capacity, triangle_capacity, 3 * sizeof(int32_t), who, "triangles") ||
+      (with_colour && volume_grow((void**)&v->d_mesh_rgba, &v->mesh_rgba_capacity, vertex_capacity, sizeof(uint32_t), who, "vertex colours")))
+    return -1;
   VolMeshArgs a;
   memset(&a, 0, sizeof(a));
   a.g = volume_grid(v);
@@ -426,7 +399,7 @@ static int volume_mesh(odo_volume* v, long vertex_capacity, long triangle_capaci
   HIP_OK(hipStreamSynchronize(v->own));
   if (c.v_written > 0 || c.t_written > 0) {
     if (c.v_total > 0x7fffffffull)
-      return fail("odo_volume_mesh: %llu vertices: an index does not fit an int32 (totals are returned with both capacities 0)", c.v_total);
+      return fail("%s: %llu vertices: an index does not fit an int32 (totals are returned with both capacities 0)", who, c.v_total);
     launch_volume_mesh_emit(a, c.t_written > 0, v->own);
     HIP_OK(hipGetLastError());
     if (with_colour && c.v_written > 0) {
@@ -450,19 +423,12 @@ static int volume_mesh(odo_volume* v, long vertex_capacity, long triangle_capaci
 
 extern "C" int odo_volume_mesh(odo_volume* v, long vertex_capacity, long triangle_capacity, float* xyz0, float* nrmw, int32_t* tri,
                                long counts[4]) {
-  if (!v || !counts || vertex_capacity < 0 || vertex_capacity > (1L << 28) || triangle_capacity < 0 || triangle_capacity > (1L << 28) ||
-      (vertex_capacity > 0 && (!xyz0 || !nrmw)) || (triangle_capacity > 0 && !tri))
-    return fail("odo_volume_mesh: bad arg (capacities 0 .. 2^28, buffers for `vertex_capacity` vertices and `triangle_capacity` triangles)");
-  return volume_mesh(v, vertex_capacity, triangle_capacity, xyz0, nrmw, nullptr, tri, counts, false);
+  return volume_mesh("odo_volume_mesh", v, vertex_capacity, triangle_capacity, xyz0, nrmw, nullptr, tri, counts, false);
 }
 
 extern "C" int odo_volume_mesh_colour(odo_volume* v, long vertex_capacity, long triangle_capacity, float* xyz0, float* nrmw, uint8_t* rgba,
                                       int32_t* tri, long counts[4]) {
-  if (!v || !counts || vertex_capacity < 0 || vertex_capacity > (1L << 28) || triangle_capacity < 0 || triangle_capacity > (1L << 28) ||
-      (vertex_capacity > 0 && (!xyz0 || !nrmw || !rgba)) || (triangle_capacity > 0 && !tri))
-    return fail("odo_volume_mesh_colour: bad arg (capacities 0 .. 2^28, buffers for `vertex_capacity` vertices and `triangle_capacity` triangles)");
-  if (!v->colour) return fail("odo_volume_mesh_colour: the volume has no colour grid (odo_volume_enable_colour first)");
-  return volume_mesh(v, vertex_capacity, triangle_capacity, xyz0, nrmw, rgba, tri, counts, true);
+  return volume_mesh("odo_volume_mesh_colour", v, vertex_capacity, triangle_capacity, xyz0, nrmw, rgba, tri, counts, true);
 }
 
 // ---- ray-cast ----------------------------------------------------------------------------------------------------------------------
@@ -512,6 +478,18 @@ extern "C" int odo_volume_raycast_dev(odo_volume* v, const odo_raycast_params* r
   return volume_raycast_launch(v, rp, abs_pose_colmajor, depth_dev, raw_dev, (float4*)nrmw_dev, (uint32_t*)rgba_dev);
 }
 
+// The ray-cast frames that the volume owns, for n pixels: depth, raw and normals, and the colours when asked for.
+static int volume_ray_frames(const char* who, odo_volume* v, long n, bool with_colour) {
+  if (n <= v->ray_depth_capacity && n <= v->ray_raw_capacity && n <= v->ray_nrmw_capacity && (!with_colour || n <= v->ray_rgba_capacity)) return 0;
+  HIP_OK(hipStreamSynchronize(v->own));   // (an earlier ray-cast into these buffers has been waited for; be sure)
+  if (volume_grow((void**)&v->d_ray_depth, &v->ray_depth_capacity, n, sizeof(float), who, "pixels") ||
+      volume_grow((void**)&v->d_ray_raw, &v->ray_raw_capacity, n, sizeof(uint16_t), who, "pixels") ||
+      volume_grow((void**)&v->d_ray_nrmw, &v->ray_nrmw_capacity, n, sizeof(float4), who, "pixels") ||
+      (with_colour && volume_grow((void**)&v->d_ray_rgba, &v->ray_rgba_capacity, n, sizeof(uint32_t), who, "pixel colours")))
+    return -1;
+  return 0;
+}
+
 extern "C" int odo_volume_raycast(odo_volume* v, const odo_raycast_params* rp, const float abs_pose_colmajor[16], float* depth,
                                   uint16_t* raw, float* nrmw, uint8_t* rgba) {
   if (!v || !rp || !abs_pose_colmajor) return fail("odo_volume_raycast: NULL arg");
@@ -520,25 +498,7 @@ extern "C" int odo_volume_raycast(odo_volume* v, const odo_raycast_params* rp, c
   if (!depth && !raw && !nrmw && !rgba) return 0;
   HIP_OK(hipSetDevice(v->device));
   const long n = (long)rp->rows * rp->cols;
-  if (n > v->ray_capacity || (rgba && n > v->ray_rgba_capacity)) {
-    HIP_OK(hipStreamSynchronize(v->own));   // (an earlier ray-cast into these buffers through odo_volume_raycast has been waited for; be sure)
-    if (n > v->ray_capacity) {
-      void* ps[] = {v->d_ray_depth, v->d_ray_raw, v->d_ray_nrmw};
-      for (void* p : ps) if (p) (void)hipFree(p);
-      v->d_ray_depth = nullptr; v->d_ray_raw = nullptr; v->d_ray_nrmw = nullptr; v->ray_capacity = 0;
-      if (hipMalloc((void**)&v->d_ray_depth, sizeof(float) * (size_t)n) != hipSuccess ||
-          hipMalloc((void**)&v->d_ray_raw, sizeof(uint16_t) * (size_t)n) != hipSuccess ||
-          hipMalloc((void**)&v->d_ray_nrmw, sizeof(float4) * (size_t)n) != hipSuccess) {
-        (void)hipGetLastError();
-        void* qs[] = {v->d_ray_depth, v->d_ray_raw, v->d_ray_nrmw};
-        for (void* p : qs) if (p) (void)hipFree(p);
-        v->d_ray_depth = nullptr; v->d_ray_raw = nullptr; v->d_ray_nrmw = nullptr;
-        return fail("odo_volume_raycast: device allocation failed (%ld pixels)", n);
-      }
-      v->ray_capacity = n;
-    }
-    if (rgba && volume_mesh_grow((void**)&v->d_ray_rgba, &v->ray_rgba_capacity, n, sizeof(uint32_t), "pixel colours")) return -1;
-  }
+  if (volume_ray_frames("odo_volume_raycast", v, n, rgba != nullptr)) return -1;
   if (volume_raycast_launch(v, rp, abs_pose_colmajor, depth ? v->d_ray_depth : nullptr, raw ? v->d_ray_raw : nullptr,
                             nrmw ? v->d_ray_nrmw : nullptr, rgba ? v->d_ray_rgba : nullptr)) return -1;
   if (depth) HIP_OK(hipMemcpyAsync(depth, v->d_ray_depth, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, v->own));

@@ -4,12 +4,7 @@
 // The colour grid is a second array beside the voxel grid, one 32-bit word per voxel in the same raster order: uint8 R, G, B (bytes
 // 0, 1, 2) and uint8 wc (byte 3: the colour weight, 0 = never coloured). include/odometry_hip.h / DESIGN.md section 9.6.
 //
-// One coloured integration (odo_volume_integrate_colour_dev) = two launches, as the plain one:
-//   integrate  volume_integrate_kernel's walk, tests and voxel update unchanged (volume_kernels.hip); a lane in the band (|sdf| <= mu)
-//              also loads the colour pixel its depth reading came from (a 16-bit and a byte load, or one dword with 4 channels) and
-//              its colour word (the neighbour of its voxel word: as coalesced as the grid) in front of the voxel's load, and behind
-//              the voxel's store applies volume_colour_math.h and stores one dword.
-//   sum        volume_sum_kernel, the plain integration's.
+// The coloured integration is volume_kernels.hip's (volume.hip.h: one body for the plain and the coloured kernel).
 // Colours of extracted points / mesh vertices = one launch behind the unchanged extraction / mesh launches, on the volume's stream: a
 // thread per voxel rebuilds the index of its first point (the extraction's wave ballots and block offsets; the mesh's per-voxel
 // vertex base and edge mask) and writes one dword per point. No atomics; the order does not depend on timing.
@@ -20,19 +15,6 @@
 #include "volume_mesh.hip.h"
 
 namespace odo {
-
-struct VolColourFrame {
-  uint32_t* col;          // [nx * ny * nz]: {R, G, B, wc}
-  const uint8_t* pix;     // rows x cols x channels, dense
-  int channels;           // 3 | 4
-  int bgr;                // 0: R first, 1: B first
-  int max_weight;         // 1 .. 255
-};
-
-struct VolIntegrateColourArgs {
-  VolIntegrateArgs a;
-  VolColourFrame c;
-};
 
 struct VolExtractColourArgs {
   VolExtractArgs a;       // what launch_volume_extract was given: wave_mask and blk_off are read, xyz0 / nrmw are not
@@ -46,7 +28,6 @@ struct VolMeshColourArgs {
   uint32_t* rgba;         // [vertex_capacity]
 };
 
-void launch_volume_integrate_colour(const VolIntegrateColourArgs& a, hipStream_t s);   // the fused launch only (the sum: launch_volume_sum)
 void launch_volume_extract_colour(const VolExtractColourArgs& a, hipStream_t s);
 void launch_volume_mesh_colour(const VolMeshColourArgs& a, hipStream_t s);
 

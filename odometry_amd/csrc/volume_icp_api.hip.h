@@ -248,26 +248,6 @@ extern "C" int odo_volume_icp_align_dev(odo_volume* v, const odo_icp_params* p, 
                    trace_capacity, trace_n);
 }
 
-// The ray-cast frames that the volume owns (odo_volume_raycast's: depth, raw and normals grow together), for n pixels.
-static int icp_ray_frames(odo_volume* v, long n) {
-  if (n <= v->ray_capacity) return 0;
-  HIP_OK(hipStreamSynchronize(v->own));
-  void* ps[] = {v->d_ray_depth, v->d_ray_raw, v->d_ray_nrmw};
-  for (void* q : ps) if (q) (void)hipFree(q);
-  v->d_ray_depth = nullptr; v->d_ray_raw = nullptr; v->d_ray_nrmw = nullptr; v->ray_capacity = 0;
-  if (hipMalloc((void**)&v->d_ray_depth, sizeof(float) * (size_t)n) != hipSuccess ||
-      hipMalloc((void**)&v->d_ray_raw, sizeof(uint16_t) * (size_t)n) != hipSuccess ||
-      hipMalloc((void**)&v->d_ray_nrmw, sizeof(float4) * (size_t)n) != hipSuccess) {
-    (void)hipGetLastError();
-    void* qs[] = {v->d_ray_depth, v->d_ray_raw, v->d_ray_nrmw};
-    for (void* q : qs) if (q) (void)hipFree(q);
-    v->d_ray_depth = nullptr; v->d_ray_raw = nullptr; v->d_ray_nrmw = nullptr;
-    return fail("odo_volume_track_dev: device allocation failed (%ld pixels)", n);
-  }
-  v->ray_capacity = n;
-  return 0;
-}
-
 extern "C" int odo_volume_track_dev(odo_volume* v, const odo_icp_params* p, const uint16_t* raw_dev, const float prev_pose_colmajor[16],
                                     float abs_pose_colmajor[16], odo_icp_result* result) {
   const char* who = "odo_volume_track_dev";
@@ -282,7 +262,7 @@ extern "C" int odo_volume_track_dev(odo_volume* v, const odo_icp_params* p, cons
   rp.n_steps = (int)std::min(4096.0, std::max(1.0, std::ceil(((double)v->p.max_depth + (double)v->p.mu) / step) + 1.0));
   if (raycast_check(who, &rp, prev_pose_colmajor)) return -1;
   HIP_OK(hipSetDevice(v->device));
-  if (icp_ray_frames(v, (long)rp.rows * rp.cols)) return -1;
+  if (volume_ray_frames(who, v, (long)rp.rows * rp.cols, false)) return -1;
   if (volume_raycast_launch(v, &rp, prev_pose_colmajor, v->d_ray_depth, nullptr, v->d_ray_nrmw, nullptr)) return -1;
   return icp_align(v, p, v->d_ray_depth, (const float*)v->d_ray_nrmw, prev_pose_colmajor, raw_dev, prev_pose_colmajor, abs_pose_colmajor,
                    result, nullptr, 0, nullptr);

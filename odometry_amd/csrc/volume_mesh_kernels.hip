@@ -1,31 +1,16 @@
 // volume_mesh_kernels.hip — the TSDF volume's mesh kernels (volume_mesh.hip.h) as a translation unit of their own, plus their
 // host-side launchers. The arithmetic is the table of include/odometry_hip.h (odo_volume_mesh) / DESIGN.md section 9.5: the vertices
-// are the points of the extraction (volume_kernels.hip) carried over to seven edge directions, fp32, one rounding per operation (the
-// unit is built with -ffp-contract=off and correctly rounded divide / sqrt); the triangles are integers out of the table of
-// volume_mesh_table.h. Nothing is combined across threads but counts.
+// are the points of the extraction carried over to seven edge directions: the same functions of volume_math.h, fp32, one rounding
+// per operation (the unit is built with -ffp-contract=off and correctly rounded divide / sqrt); the triangles are integers out of the
+// table of volume_mesh_table.h. Nothing is combined across threads but counts.
 #include <hip/hip_runtime.h>
 #include "volume_mesh.hip.h"
 #include "volume_mesh_table.h"
+#include "volume_scan.hip.h"
 
 namespace odo {
 
 __constant__ MtetTable c_mtet = make_mtet_table();   // 672 bytes, derived at compile time
-
-__device__ __forceinline__ int mesh_q(uint32_t v) { return (int)(int16_t)(v & 0xffffu); }
-__device__ __forceinline__ int mesh_w(uint32_t v) { return (int)(v >> 16); }
-__device__ __forceinline__ float mesh_centre(float o, int i, float vs) { return o + ((float)i + 0.5f) * vs; }
-
-__device__ __forceinline__ void mesh_ijk(const VolGrid& g, int v, int* i, int* j, int* k) {
-  const int row = v / g.nx;
-  *i = v - row * g.nx;
-  *k = row / g.ny;
-  *j = row - *k * g.ny;
-}
-
-// Word of the voxel at corner c (= dx + 2 dy + 4 dz) of the cell whose corner 0 is word v.
-__device__ __forceinline__ long long mesh_corner_word(const VolGrid& g, int v, int c) {
-  return (long long)v + (c & 1) + (long long)((c >> 1) & 1) * g.nx + (long long)((c >> 2) & 1) * g.nx * g.ny;
-}
 
 // What the count and the triangle pass both need of voxel v (< n): the 7-bit mask of its edges that carry a vertex, and of its cell
 // whether it is live (all eight corners observed) and which corners are positive. A neighbour outside the grid is never loaded.
@@ -34,20 +19,20 @@ __device__ __forceinline__ void mesh_voxel(const VolGrid& g, int v, unsigned* ed
   *live = false;
   *pos8 = 0;
   const uint32_t va = g.vox[v];
-  if (mesh_w(va) == 0) return;   // no edge of an unobserved voxel carries a vertex, and its cell is not live
+  if (vox_w(va) == 0) return;   // no edge of an unobserved voxel carries a vertex, and its cell is not live
   int i, j, k;
-  mesh_ijk(g, v, &i, &j, &k);
+  vox_ijk(g, v, &i, &j, &k);
   const bool in_x = i + 1 < g.nx, in_y = j + 1 < g.ny, in_z = k + 1 < g.nz;
-  const bool pa = mesh_q(va) > 0;
+  const bool pa = vox_q(va) > 0;
   unsigned mask = 0, pos = pa ? 1u : 0u, observed = 1u;
 #pragma unroll
   for (int e = 0; e < 7; e++) {
     const int c = mtet_dir_offset(e);
     const bool inside = (!(c & 1) || in_x) && (!(c & 2) || in_y) && (!(c & 4) || in_z);
     if (!inside) continue;
-    const uint32_t vb = g.vox[mesh_corner_word(g, v, c)];
-    if (mesh_w(vb) == 0) continue;
-    const bool pb = mesh_q(vb) > 0;
+    const uint32_t vb = g.vox[vox_corner_word(g, v, c)];
+    if (vox_w(vb) == 0) continue;
+    const bool pb = vox_q(vb) > 0;
     observed |= 1u << c;
     pos |= (pb ? 1u : 0u) << c;
     mask |= (pa != pb ? 1u : 0u) << e;
@@ -55,22 +40,6 @@ __device__ __forceinline__ void mesh_voxel(const VolGrid& g, int v, unsigned* ed
   *edge_mask = mask;
   *live = observed == 0xffu;
   *pos8 = pos;
-}
-
-// Exclusive rank of s among the block's threads in thread order. Every thread of the block calls it.
-__device__ __forceinline__ unsigned mesh_block_rank(unsigned s, unsigned* wsum) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  unsigned inc = s;
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned v = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += v;
-  }
-  if (lane == 63) wsum[w] = inc;
-  __syncthreads();
-  unsigned before = 0;
-  for (int q = 0; q < kMeshBlock / 64; q++)
-    if (q < w) before += wsum[q];
-  return before + inc - s;
 }
 
 __global__ void __launch_bounds__(kMeshBlock) volume_mesh_count_kernel(VolMeshArgs a) {
@@ -99,7 +68,7 @@ __global__ void __launch_bounds__(kMeshBlock) volume_mesh_count_kernel(VolMeshAr
 // One block: exclusive scans of both per-block counts, 1024 blocks at a time (coalesced, a running base), the totals, the clamps.
 __global__ void __launch_bounds__(kMeshScanThreads) volume_mesh_scan_kernel(VolMeshArgs a) {
   __shared__ unsigned wsum[2][kMeshScanThreads / 64];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int t = threadIdx.x;
   unsigned long long base[2] = {0, 0};
   for (int c0 = 0; c0 < a.nblk; c0 += kMeshScanThreads) {
     const int b = c0 + t;
@@ -107,23 +76,14 @@ __global__ void __launch_bounds__(kMeshScanThreads) volume_mesh_scan_kernel(VolM
 #pragma unroll
     for (int x = 0; x < 2; x++) {
       s[x] = b < a.nblk ? a.blk[2 * b + x] : 0u;   // (a chunk's sum is at most 1024 * 12 288: far below 2^32)
-      inc[x] = s[x];
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned v = __shfl_up(inc[x], o, 64);
-        if (lane >= o) inc[x] += v;
-      }
-      if (lane == 63) wsum[x][w] = inc[x];
+      inc[x] = scan_wave(s[x], wsum[x]);
     }
     __syncthreads();
 #pragma unroll
     for (int x = 0; x < 2; x++) {
-      unsigned before = 0, total = 0;
-      for (int q = 0; q < kMeshScanThreads / 64; q++) {
-        if (q < w) before += wsum[x][q];
-        total += wsum[x][q];
-      }
-      if (b < a.nblk) a.blk_off[2 * b + x] = base[x] + (unsigned long long)(before + inc[x] - s[x]);
-      base[x] += total;
+      const ScanRank r = scan_rank<kMeshScanThreads>(s[x], inc[x], wsum[x]);
+      if (b < a.nblk) a.blk_off[2 * b + x] = base[x] + (unsigned long long)r.rank;
+      base[x] += r.total;
     }
     __syncthreads();   // wsum is written again
   }
@@ -136,65 +96,32 @@ __global__ void __launch_bounds__(kMeshScanThreads) volume_mesh_scan_kernel(VolM
   }
 }
 
-// The gradient of Q = (float)q at voxel (i, j, k), whose own word is vc: the extraction's rule unchanged.
-__device__ __forceinline__ bool mesh_gradient(const VolGrid& g, long long v, int i, int j, int k, uint32_t vc, float* gx, float* gy, float* gz) {
-  const float Q = (float)mesh_q(vc);
-  const int pos[3] = {i, j, k}, dim[3] = {g.nx, g.ny, g.nz};
-  const long long stride[3] = {1, g.nx, (long long)g.nx * g.ny};
-  float out[3];
-  bool ok = true;
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    uint32_t vp = 0, vm = 0;
-    if (pos[c] + 1 < dim[c]) vp = g.vox[v + stride[c]];
-    if (pos[c] > 0) vm = g.vox[v - stride[c]];
-    const bool up = mesh_w(vp) > 0, um = mesh_w(vm) > 0;   // (a neighbour outside the grid stays 0: w = 0, not usable)
-    const float Qp = (float)mesh_q(vp), Qm = (float)mesh_q(vm);
-    float d = 0.0f;
-    if (up && um) d = Qp - Qm;
-    else if (up) d = 2.0f * (Qp - Q);
-    else if (um) d = 2.0f * (Q - Qm);
-    else ok = false;
-    out[c] = d;
-  }
-  *gx = out[0]; *gy = out[1]; *gz = out[2];
-  return ok;
-}
-
 __global__ void __launch_bounds__(kMeshBlock) volume_mesh_vertex_kernel(VolMeshArgs a) {
   __shared__ unsigned wsum[kMeshBlock / 64];
   const int v = blockIdx.x * kMeshBlock + threadIdx.x;
   const unsigned mask = v < a.n ? (unsigned)a.edge_mask[v] : 0u;
-  const unsigned rank = mesh_block_rank((unsigned)__popc(mask), wsum);
+  const unsigned rank = scan_block<kMeshBlock>((unsigned)__popc(mask), wsum).rank;
   unsigned long long idx = a.blk_off[2 * blockIdx.x] + rank;
   if (v < a.n) a.vertex_base[v] = (uint32_t)idx;   // (the host ends the call when the total does not fit 31 bits)
   const unsigned long long cap = (unsigned long long)a.vertex_capacity;
   if (!mask || idx >= cap) return;   // (so are this voxel's later vertices)
   int i, j, k;
-  mesh_ijk(a.g, v, &i, &j, &k);
+  vox_ijk(a.g, v, &i, &j, &k);
   const uint32_t va = a.g.vox[v];
-  const float qa = (float)mesh_q(va);
-  float gax, gay, gaz;
-  const bool has_a = mesh_gradient(a.g, v, i, j, k, va, &gax, &gay, &gaz);
-  const float cx = mesh_centre(a.g.ox, i, a.g.vs), cy = mesh_centre(a.g.oy, j, a.g.vs), cz = mesh_centre(a.g.oz, k, a.g.vs);
+  float ga[3], gb[3];
+  const bool has_a = vox_gradient(a.g, v, i, j, k, va, ga);
+  const float cx = vox_centre(a.g.ox, i, a.g.vs), cy = vox_centre(a.g.oy, j, a.g.vs), cz = vox_centre(a.g.oz, k, a.g.vs);
   for (int e = 0; e < 7; e++) {
     if (!((mask >> e) & 1u)) continue;
     if (idx >= cap) return;
     const int c = mtet_dir_offset(e);
     const int dx = c & 1, dy = (c >> 1) & 1, dz = (c >> 2) & 1;
-    const long long vb_i = mesh_corner_word(a.g, v, c);
+    const long long vb_i = vox_corner_word(a.g, v, c);
     const uint32_t vb = a.g.vox[vb_i];
-    const float alpha = qa / (qa - (float)mesh_q(vb));
-    const float step = alpha * a.g.vs;
-    float nx = 0.0f, ny = 0.0f, nz = 0.0f, gbx, gby, gbz;
-    const bool has_b = mesh_gradient(a.g, vb_i, i + dx, j + dy, k + dz, vb, &gbx, &gby, &gbz);
-    if (has_a && has_b) {
-      const float mx = gax + alpha * (gbx - gax), my = gay + alpha * (gby - gay), mz = gaz + alpha * (gbz - gaz);
-      const float len = sqrtf((mx * mx + my * my) + mz * mz);
-      if (len > 0.0f) { nx = mx / len; ny = my / len; nz = mz / len; }
-    }
-    a.xyz0[idx] = make_float4(dx ? cx + step : cx, dy ? cy + step : cy, dz ? cz + step : cz, (float)e);
-    a.nrmw[idx] = make_float4(nx, ny, nz, (float)min(mesh_w(va), mesh_w(vb)));
+    const bool has_b = vox_gradient(a.g, vb_i, i + dx, j + dy, k + dz, vb, gb);
+    const VoxEdgePoint p = vox_edge_point(va, vb, has_a, ga, has_b, gb, cx, cy, cz, a.g.vs, dx, dy, dz);
+    a.xyz0[idx] = make_float4(p.x, p.y, p.z, (float)e);
+    a.nrmw[idx] = make_float4(p.nx, p.ny, p.nz, p.w);
     idx++;
   }
 }
@@ -209,7 +136,7 @@ __global__ void __launch_bounds__(kMeshBlock) volume_mesh_triangle_kernel(VolMes
     mesh_voxel(a.g, v, &mask, &live, &pos8);
     nt = live ? (unsigned)mtet_cell_count(pos8) : 0u;
   }
-  const unsigned rank = mesh_block_rank(nt, wsum);
+  const unsigned rank = scan_block<kMeshBlock>(nt, wsum).rank;
   unsigned long long idx = a.blk_off[2 * blockIdx.x + 1] + rank;
   const unsigned long long cap = (unsigned long long)a.triangle_capacity;
   if (!nt) return;
@@ -223,7 +150,7 @@ __global__ void __launch_bounds__(kMeshBlock) volume_mesh_triangle_kernel(VolMes
       for (int x = 0; x < 3; x++) {
         int c, e;
         mtet_lookup(c_mtet, t, m, r, x, &c, &e);
-        const long long owner = mesh_corner_word(a.g, v, c);   // (a live cell: all eight corners are inside the grid)
+        const long long owner = vox_corner_word(a.g, v, c);   // (a live cell: all eight corners are inside the grid)
         id[x] = (int)(a.vertex_base[owner] + (unsigned)__popc((unsigned)a.edge_mask[owner] & ((1u << e) - 1u)));
       }
       // the smallest index first, the cyclic order kept

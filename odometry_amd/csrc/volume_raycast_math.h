@@ -11,6 +11,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include "volume_math.h"
 
 #if defined(__HIPCC__)
 #define ODO_RC_HD __host__ __device__ __forceinline__
@@ -41,7 +42,7 @@ ODO_RC_HD float rc_pixel(int x, float c, float f) { return ((float)x - c) / f; }
 ODO_RC_HD float rc_dir(float G0, float G1, float G2, float dx, float dy) { return (G0 * dx + G1 * dy) + G2; }
 ODO_RC_HD float rc_t(float t_min, int n, float step) { return t_min + (float)n * step; }
 ODO_RC_HD bool rc_in(float b, int dim) { return b >= 0.0f && b <= (float)(dim - 2); }
-ODO_RC_HD float rc_q(uint32_t v) { return (float)(int)(int16_t)(v & 0xffffu); }
+ODO_RC_HD float rc_q(uint32_t v) { return (float)vox_q(v); }   // (the voxel word: volume_math.h)
 ODO_RC_HD uint32_t rc_min(uint32_t a, uint32_t b) { return a < b ? a : b; }
 
 // The sample at depth t: false = invalid (outside the cells of the grid, or a corner that was never observed). A sample that fails

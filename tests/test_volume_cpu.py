@@ -454,6 +454,78 @@ def test_update_rule_on_hand_made_values():
     assert np.allclose(M @ _pose((0.1, 0.2, 0.3), (1, 2, 3)), np.eye(4), atol=1e-6)
 
 
+# ---- the shared header under sanitizers ----------------------------------------------------------------------------------------------
+def words(q, w):
+    """The grid as the device holds it: one 32-bit word per voxel in raster order, q in the low half."""
+    return ((w.astype(np.uint32) << 16) | q.view(np.uint16).astype(np.uint32)).reshape(-1)
+
+
+def _run_harness(exe, tmp_path, mode, head, p, *arrays):
+    nx, ny, nz = p["dims"]
+    src, dst = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
+    with open(src, "wb") as f:
+        f.write(np.array([nx, ny, nz], "<i4").tobytes() + np.array([p["vs"], *p["origin"]], "<f4").tobytes() + head)
+        for a in arrays:
+            f.write(np.ascontiguousarray(a).tobytes())
+    out = subprocess.run([exe, mode, src, dst], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and out.stdout.strip().endswith("OK"), out.stdout[-1500:] + out.stderr[-3000:]
+    return dst, {ln.split()[0]: int(ln.split()[1]) for ln in out.stdout.splitlines()[:-1]}
+
+
+def test_shared_header_equals_the_loop_models_under_sanitizers(tmp_path):
+    """odometry_amd/csrc/volume_math.h — the lines the device compiles — as a stand-alone g++ program with AddressSanitizer and UBSan:
+    every frame of tiny_cases() integrated into the whole grid against integrate_loop, the points of those grids against
+    extract_loop, and the vertices of the mesh's random grids against its loop model, all bit for bit. The header's early-out
+    (zc > zc_far) is not a step of the model: it may only take voxels that the model skips for another reason, and one more case
+    puts voxels behind it."""
+    from test_volume_mesh_cpu import mesh_loop, small_grids
+    exe = str(tmp_path / "volume_math_harness")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "volume_math_harness.cpp"), "-o", exe])
+    cases = tiny_cases()
+    K, size = (40.0, 15.5, 11.5), (24, 32)
+    flat = np.full(size, 1500, np.uint16)
+    flat[::5, ::3] = 0
+    cases.append((params(K, 1000.0, size, dims=(4, 4, 12), vs=0.3, origin=(-0.6, -0.6, 0.5), mu=0.3, max_depth=2.0, max_weight=2),
+                  [(flat, _pose())] * 3))
+    total, grids = {}, []
+    for p, frames in cases:
+        q, w = empty_grid(p)
+        for raw, pose in frames:
+            M = world_to_camera(pose)
+            head = np.array([*p["size"], p["max_weight"]], "<i4").tobytes() + np.array(
+                [*p["K"], p["depth_scale"], p["max_depth"], p["mu"], *M[:3, :].T.reshape(12),
+                 f32(f32(p["max_depth"]) + f32(p["mu"])) * f32(1.001)], "<f4").tobytes()
+            dst, got = _run_harness(exe, tmp_path, "integrate", head, p, words(q, w), np.asarray(raw, np.uint16))
+            q, w, met = integrate_loop(q, w, raw, pose, p)
+            assert np.array_equal(np.fromfile(dst, "<u4"), words(q, w))
+            assert (got["updated"], got["band"], got["behind"], got["saturated"]) == (met["updated"], met["band"], met["behind"], met["saturated"])
+            assert got["past"] + got["outside"] + got["hole"] + got["far"] + got["beyond"] == \
+                met["outside"] + met["nan"] + met["hole"] + met["far"] + met["beyond"]
+            assert got["outside"] <= met["outside"] + met["nan"] and got["hole"] <= met["hole"] and got["far"] <= met["far"] and \
+                got["beyond"] <= met["beyond"]
+            for k, v in got.items():
+                total[k] = total.get(k, 0) + v
+        grids.append((p, q, w))
+    print(total)
+    assert all(v > 0 for v in total.values()), total   # every rejection, the early-out, the weight's clamp
+    met = {}
+    n_points = 0
+    for mode, loop, todo in (("extract", extract_loop, grids), ("mesh", lambda q, w, p: mesh_loop(q, w, p)[:2],
+                                                               [g for n, g in small_grids().items() if n.startswith("random")])):
+        for p, q, w in todo:
+            dst, got = _run_harness(exe, tmp_path, mode, b"", p, words(q, w))
+            P, N = loop(q, w, p)
+            rec = np.fromfile(dst, "<f4").reshape(-1, 8)
+            assert len(rec) == len(P) and np.array_equal(bits(rec[:, :4]), bits(P)) and np.array_equal(bits(rec[:, 4:]), bits(N)), mode
+            n_points += len(P)
+            for k, v in got.items():
+                met[mode + " " + k] = met.get(mode + " " + k, 0) + v
+    print(met, n_points)
+    assert len(met) == 8 and all(v > 0 for v in met.values()), met   # two-sided, either one-sided, none: in both modes
+    assert n_points > 500
+
+
 # ---- the model against the ground truth -----------------------------------------------------------------------------------------
 def test_pinned_case_against_the_corridors_planes(pinned):
     """True poses, ten frames. Measured with this model: 570-650 k voxels updated per frame, 41 011 points, distance to the nearest
