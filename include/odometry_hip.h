@@ -810,6 +810,67 @@ int odo_volume_icp_align_dev(odo_volume* v, const odo_icp_params* p, const float
 int odo_volume_track_dev(odo_volume* v, const odo_icp_params* p, const uint16_t* raw_dev, const float prev_pose_colmajor[16],
                          float abs_pose_colmajor[16], odo_icp_result* result);
 
+/* ---- The moving volume: the grid follows the camera, and what leaves it is kept ------------------------------------------------------
+ * Optional. A volume that is never shifted behaves and writes exactly as above, and allocates nothing more.
+ * Window. The volume remembers origin0, the origin given to odo_volume_create, and off, the cumulative shift in whole voxels (0 at
+ * create). After every shift origin_c = origin0_c + (float)off_c * voxel_size: one fp32 product and one fp32 sum, each rounded once,
+ * never accumulated shift by shift, so a shift by d followed by -d restores the origin bit for bit. |off_c| <= 2^24. Every operation
+ * above (integration, extraction, mesh, colour, ray-cast, alignment) reads the grid and its origin when it is called and so works in
+ * the moved window unchanged. odo_volume_clear empties the grids and the spill store; the window stays where it is.
+ * Shift by d = (dx, dy, dz) voxels: the origin moves by +d. New voxel (i, j, k) = old voxel (i + dx, j + dy, k + dz) if that lies in
+ * the old grid, else 0 (q = 0, w = 0: never observed); the colour grid likewise. |d_c| >= n_c on any axis leaves an empty grid. One
+ * launch writes both grids into a second pair of buffers (+4 B per voxel, +8 B with colour: 25 / 49 MB more for 240 x 128 x 200), and
+ * the host swaps the buffers when it enqueues; no atomics. The second buffers are allocated once, with hipMalloc, by whichever comes
+ * first of odo_volume_set_follow and the first shift (the colour grid's by the first of either after odo_volume_enable_colour), and
+ * kept until destroy: set the follow parameters before attaching and no frame call of the tracker allocates. The frame and update
+ * counters do not change.
+ * Spill store. Old voxel v leaves under d iff v_c - d_c lies outside [0, n_c) on some axis c. With a store, a shift first appends
+ * every point of odo_volume_extract (odo_volume_extract_colour on a volume with colour) on the PRE-shift grid whose edge a -> b has
+ * a or b leaving: position, normal from the whole pre-shift neighbourhood, weight and colour bit for bit the extraction's, in (voxel
+ * a in raster order, axis) order, behind the points of earlier shifts. An edge with both ends staying survives in the grid, and an
+ * entering voxel has w = 0 and carries none: as sets of edges, extraction before = spill + extraction after. (Positions and weights of
+ * the surviving points are unchanged; their normals may change where a neighbour left.) Points beyond the store's capacity are
+ * counted and dropped. Four launches in front of the shift's (the whole grid is walked, which keeps the order), no host wait. */
+/* Spill (if the volume has a store) and shift, enqueued on the volume's own stream behind everything pending; returns at once.
+ * d = (0, 0, 0): nothing enqueued, 0. -1 and nothing enqueued when |off_c + d_c| would exceed 2^24. */
+int odo_volume_shift(odo_volume* v, const int d[3]);
+/* The window now: the cumulative shift and the origin (either may be NULL). No wait. */
+int odo_volume_window(odo_volume* v, int off[3], float origin[3]);
+/* Allocates the store: capacity (1 .. 2^28) points of float4 xyz0, float4 nrmw and, when the volume has colour (enable it first),
+ * uint8[4] rgba: 32 or 36 B per point. Once, and not while attached to a tracker. */
+int odo_volume_enable_spill(odo_volume* v, long capacity);
+/* The store's points (waits for everything pending): the first min(points in the store, capacity) into xyz0 / nrmw and, unless NULL,
+ * rgba (refused on a volume without colour); *n_points = points copied, *n_dropped (may be NULL) = points that qualified since the
+ * store was last emptied and did not fit it. clear != 0 empties the store afterwards, whatever was copied. Legal while attached. */
+int odo_volume_spill_points(odo_volume* v, long capacity, float* xyz0, float* nrmw, uint8_t* rgba, long* n_points, long* n_dropped,
+                            int clear);
+/* Event timing (diagnostic, tools/volume_cost.py shift; waits; refused while attached): batches of reps (1 .. 10000) launches between
+ * events on the volume's own stream, the mean time of one in microseconds. us[0]: the shift by d into the second buffers, which are
+ * not swapped in, so the grids, the window and the store's counted points stay as they are; us[1]: device-to-device hipMemcpyAsync
+ * of the same bytes; us[2]: hipMemsetAsync of the same bytes; us[3], us[4], us[5]: the spill's count, scan and scatter for d (0
+ * without a store). */
+int odo_volume_shift_time(odo_volume* v, const int d[3], int reps, float us[6]);
+/* TEST ONLY, for the project's own suite; not part of the interface an integrator uses and free to change. The store's buffers are
+ * allocated with a guard of 64 points behind the capacity and filled with 0xAB once; a spill writes the points it appends and nothing
+ * else. *n_changed = bytes behind the store's last point, guard included, that no longer hold 0xAB (waits): 0 until the store is
+ * first emptied, unless a spill wrote where it must not. */
+int odo_debug_volume_spill_guard(odo_volume* v, long* n_changed);
+/* Following a camera. The host works in fp64 from the fp32 entries of the camera-to-world pose [R | t]: p = t + focus * R[:, 2] (the
+ * point `focus` metres along the optical axis); e_c = (p_c - (origin_c + 0.5 * n_c * vs)) / vs, its distance from the window's centre
+ * in voxels; if max |e_c| < threshold then d = 0, else d_c = nearbyint(e_c) (ties to even) clamped to +-n_c. */
+typedef struct {
+  float focus;             /* metres along the optical axis, finite >= 0 */
+  int threshold;           /* voxels, >= 1 */
+} odo_volume_follow_params;
+/* Sets the parameters; NULL turns following off. Validated before the volume is touched. Non-NULL also allocates the grids' second
+ * buffers if they are missing (-1 when that fails), so that the follow steps of an attached tracker do not. */
+int odo_volume_set_follow(odo_volume* v, const odo_volume_follow_params* p);
+/* The rule above for abs_pose, then odo_volume_shift(d); d_out (may be NULL) receives d. -1 and nothing enqueued for a pose with a
+ * non-finite entry or a volume without follow parameters. With parameters set, an attached tracker (odo_tracker_attach_volume) takes
+ * this step with every frame's abs_pose in front of that frame's integration, on the volume's own stream, without a host wait; the
+ * tracker's poses, masks and keyframe decisions stay bit-identical to those without a volume. */
+int odo_volume_follow(odo_volume* v, const float abs_pose_colmajor[16], int d_out[3]);
+
 /* ---- RGB-D front end: raw sensor frames -> the RGB-D tracker's inputs ----------------------------------------------------------
  * A sensor delivers interleaved 8-bit colour and a uint16 depth frame in the DEPTH imager's pixel grid (its own intrinsics, often
  * its own resolution, centimetres beside the colour imager); odo_tracker_*_rgbd take an fp32 grey image and a uint16 depth frame in

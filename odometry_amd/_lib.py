@@ -53,6 +53,10 @@ class VolumeColourParams(C.Structure):
     _fields_ = [("channels", C.c_int), ("bgr", C.c_int), ("max_weight", C.c_int)]
 
 
+class VolumeFollowParams(C.Structure):
+    _fields_ = [("focus", C.c_float), ("threshold", C.c_int)]
+
+
 class RaycastParams(C.Structure):
     _fields_ = [("rows", C.c_int), ("cols", C.c_int), ("f", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
                 ("t_min", C.c_float), ("step", C.c_float), ("n_steps", C.c_int)]
@@ -261,6 +265,14 @@ SIGNATURES = {
     "odo_volume_icp_align_dev": (C.c_int, [_vp, C.POINTER(IcpParams), _vp, _vp, _fp, _vp, _fp, _fp, C.POINTER(IcpResult),
                                            C.POINTER(IcpTraceRow), C.c_int, _ip]),
     "odo_volume_track_dev": (C.c_int, [_vp, C.POINTER(IcpParams), _vp, _fp, _fp, C.POINTER(IcpResult)]),
+    "odo_volume_shift": (C.c_int, [_vp, _ip]),
+    "odo_volume_window": (C.c_int, [_vp, _ip, _fp]),
+    "odo_volume_enable_spill": (C.c_int, [_vp, C.c_long]),
+    "odo_volume_spill_points": (C.c_int, [_vp, C.c_long, _fp, _fp, _u8p, C.POINTER(C.c_long), C.POINTER(C.c_long), C.c_int]),
+    "odo_volume_shift_time": (C.c_int, [_vp, _ip, C.c_int, _fp]),
+    "odo_debug_volume_spill_guard": (C.c_int, [_vp, C.POINTER(C.c_long)]),   # test only: not for integrators (include/odometry_hip.h)
+    "odo_volume_set_follow": (C.c_int, [_vp, C.POINTER(VolumeFollowParams)]),
+    "odo_volume_follow": (C.c_int, [_vp, _fp, _ip]),
 }
 
 _lib = None

@@ -904,6 +904,9 @@ class TsdfVolume:
         ctx = ctx_or_tracker._ctx if isinstance(ctx_or_tracker, Tracker) else ctx_or_tracker.h
         self._ctx = ctx
         self._tracker = None
+        self._follow = None           # (focus, threshold) while set_follow is on
+        self._spill_capacity = 0
+        self._spill_colour = False
         p = L.VolumeParams()
         p.nx, p.ny, p.nz = dims
         p.voxel_size = voxel_size
@@ -1212,7 +1215,7 @@ class TsdfVolume:
     def track(self, depth, prev_pose, integrate=False, params=None):
         """Frame-to-model tracking of one depth frame (a uint16 numpy array or a device handle): the volume is ray-cast from prev_pose
         and the frame aligned to that from prev_pose. Returns (abs_pose, result dict) as align(). integrate=True fuses the frame at
-        the returned pose when status is 0."""
+        the returned pose when status is 0, behind the follow step for that pose when set_follow is on."""
         p = self.icp_params() if params is None else params
         (raw_d,), temps = self._frames_dev([(depth, np.uint16, (self.rows, self.cols))])
         res = L.IcpResult()
@@ -1221,6 +1224,8 @@ class TsdfVolume:
             L.check(self.lib.odo_volume_track_dev(self.h, C.byref(p), raw_d, _fp(_colmajor(prev_pose)), _fp(pose), C.byref(res)),
                     "odo_volume_track_dev")
             if integrate and res.status == 0:
+                if self._follow is not None:   # the window moves for this pose before the frame is fused
+                    L.check(self.lib.odo_volume_follow(self.h, _fp(pose), None), "odo_volume_follow")
                 L.check(self.lib.odo_volume_integrate_dev(self.h, raw_d, _fp(pose)), "odo_volume_integrate_dev")
         finally:   # odo_dev_free waits for the context's stream: the integration has read the frame
             self._free_dev(temps)
@@ -1234,15 +1239,85 @@ class TsdfVolume:
     def clear(self):
         L.check(self.lib.odo_volume_clear(self.h), "odo_volume_clear")
 
-    def save_ply(self, path, capacity=1 << 22):
+    # ---- the moving window (odo_volume_shift, odo_volume_follow, the spill store) ----
+    def enable_spill(self, capacity):
+        """Adds the spill store: room for `capacity` (1 .. 2^28) surface points that shifts would destroy (32 B per point, 36 B with
+        colour: enable_colour first). Once, and not while attached to a tracker."""
+        L.check(self.lib.odo_volume_enable_spill(self.h, int(capacity)), "odo_volume_enable_spill")
+        self._spill_capacity = int(capacity)
+        self._spill_colour = self.has_colour   # (a store made before enable_colour has no colours)
+
+    def shift_time(self, d, reps=50):
+        """Event timing of a shift by d that is not applied: microseconds per launch or call, means over reps, of (shift, device-to-
+        device copy of the same bytes, memset of the same bytes, spill count, spill scan, spill scatter); the last three are 0
+        without a spill store. The grids, the window and the store's counted points stay as they are."""
+        d = (C.c_int * 3)(*[int(x) for x in d])
+        us = np.zeros(6, np.float32)
+        L.check(self.lib.odo_volume_shift_time(self.h, d, int(reps), _fp(us)), "odo_volume_shift_time")
+        return tuple(float(x) for x in us)
+
+    def shift(self, d):
+        """Moves the window by d = (dx, dy, dz) whole voxels: the origin moves by +d, new voxel (i, j, k) is old voxel (i + dx, j + dy,
+        k + dz) or empty. With a spill store the points on edges that lose a voxel are appended to it first. Enqueued, no wait."""
+        d = (C.c_int * 3)(*[int(x) for x in d])
+        L.check(self.lib.odo_volume_shift(self.h, d), "odo_volume_shift")
+
+    def window(self):
+        """(off, origin): the cumulative shift in voxels (3 ints) and the grid's origin now (3 float32)."""
+        off = (C.c_int * 3)()
+        origin = np.zeros(3, np.float32)
+        L.check(self.lib.odo_volume_window(self.h, off, _fp(origin)), "odo_volume_window")
+        return tuple(off), origin
+
+    def set_follow(self, focus=None, threshold=None):
+        """The follow rule's parameters: the window is kept centred on the point `focus` metres in front of the camera and moves once
+        that point is `threshold` voxels or more from its centre on some axis. set_follow() with neither turns following off. A
+        parameter left out takes its convenience default, focus = max_depth / 2 and threshold = min(dims) // 8 (at least 1)."""
+        if focus is None and threshold is None:
+            L.check(self.lib.odo_volume_set_follow(self.h, None), "odo_volume_set_follow")
+            self._follow = None
+            return
+        focus = self.params.max_depth / 2 if focus is None else focus
+        threshold = max(1, min(self.dims) // 8) if threshold is None else threshold
+        fp = L.VolumeFollowParams(focus, int(threshold))
+        L.check(self.lib.odo_volume_set_follow(self.h, C.byref(fp)), "odo_volume_set_follow")
+        self._follow = (fp.focus, fp.threshold)
+
+    def follow(self, abs_pose):
+        """The follow step for the 4x4 camera-to-world abs_pose: decides the shift by the rule of set_follow, applies it and returns
+        it as 3 ints ((0, 0, 0): the window stayed)."""
+        d = (C.c_int * 3)()
+        L.check(self.lib.odo_volume_follow(self.h, _fp(_colmajor(abs_pose)), d), "odo_volume_follow")
+        return tuple(d)
+
+    def spilled(self, clear=False, colour=False, with_dropped=False):
+        """The spill store's points as extract() returns them: (n, 4) float32 x, y, z, 0 and (n, 4) float32 nx, ny, nz, weight (colour:
+        also (n, 4) uint8 R, G, B, A; with_dropped: also the number of points that did not fit the store). clear=True empties the
+        store afterwards. Waits for everything pending."""
+        cap = self._spill_capacity
+        xyz0 = np.zeros((max(cap, 1), 4), np.float32)
+        nrmw = np.zeros((max(cap, 1), 4), np.float32)
+        rgba = np.zeros((max(cap, 1), 4), np.uint8) if colour else None
+        n, d = C.c_long(0), C.c_long(0)
+        L.check(self.lib.odo_volume_spill_points(self.h, cap, _fp(xyz0), _fp(nrmw), rgba.ctypes.data_as(L._u8p) if colour else None,
+                                                 C.byref(n), C.byref(d), int(bool(clear))), "odo_volume_spill_points")
+        out = (xyz0[:n.value].copy(), nrmw[:n.value].copy()) + ((rgba[:n.value].copy(),) if colour else ())
+        return out + (d.value,) if with_dropped else out
+
+    def save_ply(self, path, capacity=1 << 22, spill=False):
         """Binary little-endian PLY of the extracted surface: float x y z nx ny nz, and uchar red green blue when the volume has
-        colour."""
-        if self.has_colour:
-            xyz0, nrmw, rgba = self.extract(capacity, colour=True)
-            write_ply_normals(path, xyz0, nrmw, rgb=rgba)
+        colour. spill=True: the spill store's points in front of the extraction's (the whole surface of a volume that moved)."""
+        colour = self.has_colour
+        if spill and colour and not self._spill_colour:
+            raise ValueError("save_ply(spill=True): the spill store was enabled before enable_colour and holds no colours, the "
+                             "extraction has them; call enable_colour before enable_spill")
+        parts = [self.spilled(colour=colour)] if spill else []
+        parts.append(self.extract(capacity, colour=colour))
+        cols = [np.concatenate([p[i] for p in parts]) for i in range(3 if colour else 2)] if spill else list(parts[0])
+        if colour:
+            write_ply_normals(path, cols[0], cols[1], rgb=cols[2])
         else:
-            xyz0, nrmw = self.extract(capacity)
-            write_ply_normals(path, xyz0, nrmw)
+            write_ply_normals(path, cols[0], cols[1])
 
     def save_mesh_ply(self, path):
         """Binary little-endian PLY of the mesh: float x y z nx ny nz per vertex (and uchar red green blue when the volume has

@@ -177,4 +177,15 @@ inline void icp_frame(const float* P_m, const float* P_init, float* M, float* C0
   mul4(M, P_init, C0);
 }
 
+// The origin of a TSDF volume whose window has been shifted by `off` voxels in all since create (volume_shift_api.hip.h;
+// include/odometry_hip.h, odo_volume_shift): origin0_c + (float)off_c * vs, one fp32 product and one fp32 sum, each rounded once, from
+// the origin given to create — never accumulated shift by shift, so the same `off` always gives the same bits (|off_c| <= 2^24: the
+// conversion is exact).
+inline void window_origin(const float* origin0, const int* off, float vs, float* origin) {
+  for (int c = 0; c < 3; c++) {
+    const float step = (float)off[c] * vs;
+    origin[c] = origin0[c] + step;
+  }
+}
+
 }  // namespace hostfp

@@ -518,6 +518,8 @@ static int tracker_vol_integrate(odo_tracker* t, const uint16_t* depth, const fl
   odo_volume* v = t->vol;
   long before = t->vol_n - 1;   // the last integration of an earlier call
   if (abs_pose && pose_finite(abs_pose)) {
+    // a volume that follows the camera (odo_volume_set_follow) first moves its window for this pose: enqueued like the integration
+    if (v->follow && volume_follow("odo_tracker_track_rgbd", v, abs_pose, nullptr)) return -1;
     if (volume_integrate(v, depth, abs_pose, v->own, v->colour ? t->col_cur : nullptr)) return -1;
     HIP_OK(hipEventRecord(t->ev_vol[t->vol_n & 1], v->own));
     t->vol_n++;

@@ -7,6 +7,7 @@
 #include "volume_mesh.hip.h"
 #include "volume_colour.hip.h"
 #include "volume_raycast.hip.h"
+#include "volume_shift.hip.h"
 
 struct odo_volume {
   odo_ctx* ctx;                 // standalone integrations (odo_volume_integrate_dev) run on its stream
@@ -48,12 +49,24 @@ struct odo_volume {
   float4* d_ray_nrmw;
   uint32_t* d_ray_rgba;
   long ray_depth_capacity, ray_raw_capacity, ray_nrmw_capacity, ray_rgba_capacity;   // pixels
+  // the moving window (volume_shift_api.hip.h): p.origin = hostfp::window_origin(origin0, off, voxel_size) after every shift
+  float origin0[3];             // the origin given to create
+  int off[3];                   // the cumulative shift in voxels
+  uint32_t *d_vox2, *d_col2;    // the grids' second buffers: allocated on the first shift, swapped with d_vox / d_col by every shift
+  // the spill store (odo_volume_enable_spill; nothing below is allocated without it)
+  long spill_capacity;          // points, 0: no store
+  float4 *d_spill_xyz0, *d_spill_nrmw;
+  uint32_t* d_spill_rgba;       // with colour
+  VolSpillCounters* d_spill_ctr;
+  int follow;                   // 1: odo_volume_set_follow's parameters are set
+  odo_volume_follow_params fp;
 };
 
 static int volume_release(odo_volume* v) {
   void* ps[] = {v->d_vox, v->d_blk, v->d_ctr, v->d_wave, v->d_off, v->d_cnt, v->d_xyz0, v->d_nrmw,
                 v->d_mesh_mask, v->d_mesh_base, v->d_mesh_cnt, v->d_mesh_off, v->d_mesh_ctr, v->d_mesh_xyz0, v->d_mesh_nrmw, v->d_mesh_tri,
-                v->d_col, v->d_rgba, v->d_mesh_rgba, v->d_ray_depth, v->d_ray_raw, v->d_ray_nrmw, v->d_ray_rgba};
+                v->d_col, v->d_rgba, v->d_mesh_rgba, v->d_ray_depth, v->d_ray_raw, v->d_ray_nrmw, v->d_ray_rgba,
+                v->d_vox2, v->d_col2, v->d_spill_xyz0, v->d_spill_nrmw, v->d_spill_rgba, v->d_spill_ctr};
   for (void* p : ps) if (p) (void)hipFree(p);
   if (v->ev_last) (void)hipEventDestroy(v->ev_last);
   if (v->own) (void)hipStreamDestroy(v->own);
@@ -83,6 +96,7 @@ static int volume_reset(odo_volume* v) {
   HIP_OK(hipMemsetAsync(v->d_vox, 0, sizeof(uint32_t) * (size_t)v->n_vox, v->own));
   if (v->colour) HIP_OK(hipMemsetAsync(v->d_col, 0, sizeof(uint32_t) * (size_t)v->n_vox, v->own));
   HIP_OK(hipMemsetAsync(v->d_ctr, 0, sizeof(VolCounters), v->own));
+  if (v->d_spill_ctr) HIP_OK(hipMemsetAsync(v->d_spill_ctr, 0, sizeof(VolSpillCounters), v->own));   // (the window stays where it is)
   v->n_frames = 0;
   return volume_mark(v, v->own);
 }
@@ -105,6 +119,7 @@ extern "C" int odo_volume_create(odo_ctx* ctx, const odo_volume_params* p, odo_v
   if (!v) return fail("out of memory");
   v->ctx = ctx; v->device = ctx->device;   // (everything else is zero: new odo_volume())
   v->p = *p;
+  for (int c = 0; c < 3; c++) v->origin0[c] = p->origin[c];
   v->n_vox = (long)p->nx * p->ny * p->nz;
   bool ok = hipStreamCreateWithFlags(&v->own, hipStreamNonBlocking) == hipSuccess &&
             hipEventCreateWithFlags(&v->ev_last, hipEventDisableTiming) == hipSuccess &&

@@ -1,0 +1,270 @@
+// volume_shift_api.hip.h — the moving TSDF volume (odo_volume_shift, _follow, _enable_spill, _spill_points, _window, _set_follow):
+// the host side over the kernels of volume_shift_kernels.hip. The grid is shifted by whole voxels so that it follows the camera, and
+// the surface points a shift would destroy are first appended to a device-resident store. Included by odometry_hip.hip behind
+// volume_api.hip.h (the volume's object) and before tracker.hip.h (an attached tracker follows before it integrates).
+//
+// Nothing here waits for the device but odo_volume_spill_points (and the two diagnostics, odo_volume_shift_time and
+// odo_debug_volume_spill_guard): a spill and a shift are five launches on the volume's own stream.
+// The shift writes into the grids' second buffers and the host swaps the pointers when it enqueues: launches enqueued earlier hold
+// the old pointers by value and are ordered in front by volume_order_on / volume_mark, and every later launcher reads v->d_vox,
+// v->d_col and v->p.origin when it is called.
+#pragma once
+#include "volume_shift.hip.h"
+#include "volume_shift_math.h"
+
+// Test scaffolding, not part of the interface an integrator uses: every buffer of the spill store is allocated with a guard of this
+// many points behind its capacity and filled with 0xAB once, guard included. A spill writes the points [written, written + count) and
+// nothing else, so behind `written` every byte still holds 0xAB until the store is emptied for the first time:
+// odo_debug_volume_spill_guard counts the bytes there that do not (held by tests/test_gpu_volume_shift.py).
+constexpr long kSpillGuard = 64;
+
+// The grids' second buffers, which a shift writes into: allocated by the first of odo_volume_set_follow (so that an attached
+// tracker's frame call never allocates), the first shift, and the first shift after odo_volume_enable_colour; kept until destroy.
+static int volume_shift_buffers(const char* who, odo_volume* v) {
+  HIP_OK(hipSetDevice(v->device));
+  const size_t bytes = sizeof(uint32_t) * (size_t)v->n_vox;
+  if (!v->d_vox2 && hipMalloc((void**)&v->d_vox2, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    v->d_vox2 = nullptr;
+    return fail("%s: device allocation failed (the second voxel buffer, %ld voxels)", who, v->n_vox);
+  }
+  if (v->colour && !v->d_col2 && hipMalloc((void**)&v->d_col2, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    v->d_col2 = nullptr;
+    return fail("%s: device allocation failed (the second colour buffer, %ld voxels)", who, v->n_vox);
+  }
+  return 0;
+}
+
+static VolSpillArgs volume_spill_args(odo_volume* v, const int d[3]) {
+  VolSpillArgs sa;
+  memset(&sa, 0, sizeof(sa));
+  sa.a.g = volume_grid(v);
+  sa.a.n = (int)v->n_vox; sa.a.nblk = (int)((v->n_vox + kVolExtBlock - 1) / kVolExtBlock); sa.a.capacity = v->spill_capacity;
+  sa.a.wave_mask = v->d_wave; sa.a.blk = v->d_cnt; sa.a.blk_off = v->d_off;
+  sa.a.xyz0 = v->d_spill_xyz0; sa.a.nrmw = v->d_spill_nrmw;
+  sa.dx = d[0]; sa.dy = d[1]; sa.dz = d[2];
+  // (a store made before odo_volume_enable_colour has no colours: its points are spilled without them)
+  sa.col = v->d_spill_rgba ? v->d_col : nullptr; sa.rgba = v->d_spill_rgba;
+  sa.sc = v->d_spill_ctr;
+  return sa;
+}
+
+static VolShiftArgs volume_shift_args(odo_volume* v, const int d[3]) {
+  VolShiftArgs a;
+  memset(&a, 0, sizeof(a));
+  a.src = v->d_vox; a.dst = v->d_vox2;
+  if (v->colour) { a.src_col = v->d_col; a.dst_col = v->d_col2; }
+  a.nx = v->p.nx; a.ny = v->p.ny; a.nz = v->p.nz; a.n = (int)v->n_vox;
+  a.dx = d[0]; a.dy = d[1]; a.dz = d[2];
+  return a;
+}
+
+// Spill (when the volume has a store) and shift by d, on the volume's own stream. 0: enqueued, or d = 0 and nothing to do.
+static int volume_shift(const char* who, odo_volume* v, const int d[3]) {
+  int off[3];
+  for (int c = 0; c < 3; c++)
+    if (!shift_offset(v->off[c], d[c], &off[c]))
+      return fail("%s: the window would be %lld voxels from where it was created on axis %d (at most 2^24)", who, (long long)v->off[c] + d[c], c);
+  if (d[0] == 0 && d[1] == 0 && d[2] == 0) return 0;
+  if (volume_shift_buffers(who, v)) return -1;
+  if (volume_order_on(v, v->own)) return -1;
+  if (v->spill_capacity > 0) {
+    launch_volume_spill(volume_spill_args(v, d), v->own);
+    HIP_OK(hipGetLastError());
+  }
+  launch_volume_shift(volume_shift_args(v, d), v->own);
+  HIP_OK(hipGetLastError());
+  std::swap(v->d_vox, v->d_vox2);
+  if (v->colour) std::swap(v->d_col, v->d_col2);
+  for (int c = 0; c < 3; c++) v->off[c] = off[c];
+  hostfp::window_origin(v->origin0, v->off, v->p.voxel_size, v->p.origin);
+  return volume_mark(v, v->own);
+}
+
+extern "C" int odo_volume_shift(odo_volume* v, const int d[3]) {
+  if (!v || !d) return fail("odo_volume_shift: NULL arg");
+  return volume_shift("odo_volume_shift", v, d);
+}
+
+// Event timing (tools/volume_cost.py shift): batches of `reps` launches between events on the volume's own stream, the mean time of
+// one in microseconds. us[0] the shift by d into the second buffers (not swapped: the grids and the window stay as they are); us[1]
+// device-to-device hipMemcpyAsync of the same bytes (grid, and colour grid when there is one) into the second buffers; us[2]
+// hipMemsetAsync of the second buffers; us[3 .. 5] the spill's count, scan and scatter for d (0 without a store). The scatter writes
+// the store behind its counted points and the counters do not move, so the store's contents and counts read the same afterwards.
+extern "C" int odo_volume_shift_time(odo_volume* v, const int d[3], int reps, float us[6]) {
+  const char* who = "odo_volume_shift_time";
+  if (!v || !d || !us) return fail("%s: NULL arg", who);
+  if (reps < 1 || reps > 10000) return fail("%s: reps 1 .. 10000", who);
+  if (v->attached) return fail("%s: the volume is attached to a tracker (odo_tracker_attach_volume(t, NULL) first)", who);
+  if (volume_shift_buffers(who, v)) return -1;
+  if (volume_order_on(v, v->own)) return -1;
+  const VolShiftArgs a = volume_shift_args(v, d);
+  const bool store = v->spill_capacity > 0;
+  const VolSpillArgs sa = store ? volume_spill_args(v, d) : VolSpillArgs{};
+  const size_t bytes = sizeof(uint32_t) * (size_t)v->n_vox;
+  hipStream_t s = v->own;
+  hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool ok = true;
+  for (auto& e : ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+  if (ok) {
+    launch_volume_shift(a, s);   // (warm)
+    if (store) for (int st = 0; st < 3; st++) launch_volume_spill_stage(sa, st, s);
+    ok = hipEventRecord(ev[0], s) == hipSuccess;
+    for (int i = 0; i < reps; i++) launch_volume_shift(a, s);
+    ok = ok && hipEventRecord(ev[1], s) == hipSuccess;
+    for (int i = 0; i < reps && ok; i++) {
+      ok = hipMemcpyAsync(v->d_vox2, v->d_vox, bytes, hipMemcpyDeviceToDevice, s) == hipSuccess &&
+           (!v->colour || hipMemcpyAsync(v->d_col2, v->d_col, bytes, hipMemcpyDeviceToDevice, s) == hipSuccess);
+    }
+    ok = ok && hipEventRecord(ev[2], s) == hipSuccess;
+    for (int i = 0; i < reps && ok; i++) {
+      ok = hipMemsetAsync(v->d_vox2, 0, bytes, s) == hipSuccess && (!v->colour || hipMemsetAsync(v->d_col2, 0, bytes, s) == hipSuccess);
+    }
+    ok = ok && hipEventRecord(ev[3], s) == hipSuccess;
+    for (int st = 0; st < 3; st++) {
+      if (store) for (int i = 0; i < reps; i++) launch_volume_spill_stage(sa, st, s);
+      ok = ok && hipEventRecord(ev[4 + st], s) == hipSuccess;
+    }
+    ok = ok && hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+    for (int q = 0; q < 6 && ok; q++) {
+      float ms = 0.0f;
+      ok = hipEventElapsedTime(&ms, ev[q], ev[q + 1]) == hipSuccess;
+      us[q] = q >= 3 && !store ? 0.0f : 1e3f * ms / (float)reps;
+    }
+  }
+  for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+  if (!ok) {
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(s);
+    return fail("%s: timing failed", who);
+  }
+  return volume_mark(v, s);
+}
+
+extern "C" int odo_volume_window(odo_volume* v, int off[3], float origin[3]) {
+  if (!v) return fail("odo_volume_window: NULL volume");
+  for (int c = 0; c < 3; c++) {
+    if (off) off[c] = v->off[c];
+    if (origin) origin[c] = v->p.origin[c];
+  }
+  return 0;
+}
+
+extern "C" int odo_volume_enable_spill(odo_volume* v, long capacity) {
+  if (!v) return fail("odo_volume_enable_spill: NULL volume");
+  if (capacity < 1 || capacity > (1L << 28)) return fail("odo_volume_enable_spill: capacity %ld out of range (1 .. 2^28)", capacity);
+  if (v->spill_capacity > 0) return fail("odo_volume_enable_spill: the volume has a spill store already");
+  if (v->attached) return fail("odo_volume_enable_spill: the volume is attached to a tracker (odo_tracker_attach_volume(t, NULL) first)");
+  HIP_OK(hipSetDevice(v->device));
+  const int nblk = (int)((v->n_vox + kVolExtBlock - 1) / kVolExtBlock);
+  // the extraction's scratch is the spill's too (both run on the volume's own stream); whichever comes first allocates all three
+  const bool scratch = v->d_cnt != nullptr;
+  unsigned long long *wave = nullptr, *off = nullptr;
+  int* cnt = nullptr;
+  float4 *xyz0 = nullptr, *nrmw = nullptr;
+  uint32_t* rgba = nullptr;
+  VolSpillCounters* ctr = nullptr;
+  bool ok = (scratch || (hipMalloc((void**)&wave, sizeof(unsigned long long) * 3 * (kVolExtBlock / 64) * (size_t)nblk) == hipSuccess &&
+                         hipMalloc((void**)&off, sizeof(unsigned long long) * (size_t)nblk) == hipSuccess &&
+                         hipMalloc((void**)&cnt, sizeof(int) * (size_t)nblk) == hipSuccess)) &&
+            hipMalloc((void**)&xyz0, sizeof(float4) * (size_t)(capacity + kSpillGuard)) == hipSuccess &&
+            hipMalloc((void**)&nrmw, sizeof(float4) * (size_t)(capacity + kSpillGuard)) == hipSuccess &&
+            (!v->colour || hipMalloc((void**)&rgba, sizeof(uint32_t) * (size_t)(capacity + kSpillGuard)) == hipSuccess) &&
+            hipMalloc((void**)&ctr, sizeof(VolSpillCounters)) == hipSuccess;
+  ok = ok && volume_order_on(v, v->own) == 0 && hipMemsetAsync(ctr, 0, sizeof(VolSpillCounters), v->own) == hipSuccess &&
+       hipMemsetAsync(xyz0, 0xAB, sizeof(float4) * (size_t)(capacity + kSpillGuard), v->own) == hipSuccess &&
+       hipMemsetAsync(nrmw, 0xAB, sizeof(float4) * (size_t)(capacity + kSpillGuard), v->own) == hipSuccess &&
+       (!rgba || hipMemsetAsync(rgba, 0xAB, sizeof(uint32_t) * (size_t)(capacity + kSpillGuard), v->own) == hipSuccess) &&
+       volume_mark(v, v->own) == 0;
+  if (!ok) {
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(v->own);
+    void* ps[] = {wave, off, cnt, xyz0, nrmw, rgba, ctr};
+    for (void* p : ps) if (p) (void)hipFree(p);
+    return fail("odo_volume_enable_spill: device allocation failed (%ld points)", capacity);
+  }
+  if (!scratch) { v->d_wave = wave; v->d_off = off; v->d_cnt = cnt; }
+  v->d_spill_xyz0 = xyz0; v->d_spill_nrmw = nrmw; v->d_spill_rgba = rgba; v->d_spill_ctr = ctr;
+  v->spill_capacity = capacity;
+  return 0;
+}
+
+extern "C" int odo_volume_spill_points(odo_volume* v, long capacity, float* xyz0, float* nrmw, uint8_t* rgba, long* n_points,
+                                       long* n_dropped, int clear) {
+  if (!v || !n_points || capacity < 0 || capacity > (1L << 28) || (capacity > 0 && (!xyz0 || !nrmw)))
+    return fail("odo_volume_spill_points: bad arg (capacity 0 .. 2^28, buffers for `capacity` points)");
+  if (v->spill_capacity <= 0) return fail("odo_volume_spill_points: the volume has no spill store (odo_volume_enable_spill first)");
+  if (rgba && !v->d_spill_rgba)
+    return fail("odo_volume_spill_points: the store has no colours (odo_volume_enable_colour before odo_volume_enable_spill)");
+  if (volume_sync(v)) return -1;
+  VolSpillCounters c;
+  HIP_OK(hipMemcpyAsync(&c, v->d_spill_ctr, sizeof(c), hipMemcpyDeviceToHost, v->own));
+  HIP_OK(hipStreamSynchronize(v->own));
+  const size_t n = (size_t)std::min<unsigned long long>(c.written, (unsigned long long)capacity);
+  if (n > 0) {
+    HIP_OK(hipMemcpyAsync(xyz0, v->d_spill_xyz0, sizeof(float4) * n, hipMemcpyDeviceToHost, v->own));
+    HIP_OK(hipMemcpyAsync(nrmw, v->d_spill_nrmw, sizeof(float4) * n, hipMemcpyDeviceToHost, v->own));
+    if (rgba) HIP_OK(hipMemcpyAsync(rgba, v->d_spill_rgba, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, v->own));
+    HIP_OK(hipStreamSynchronize(v->own));
+  }
+  if (clear) {
+    HIP_OK(hipMemsetAsync(v->d_spill_ctr, 0, sizeof(VolSpillCounters), v->own));
+    if (volume_mark(v, v->own)) return -1;
+  }
+  *n_points = (long)n;
+  if (n_dropped) *n_dropped = (long)(c.total - c.written);
+  return 0;
+}
+
+extern "C" int odo_debug_volume_spill_guard(odo_volume* v, long* n_changed) {
+  if (!v || !n_changed) return fail("odo_debug_volume_spill_guard: NULL arg");
+  if (v->spill_capacity <= 0) return fail("odo_debug_volume_spill_guard: the volume has no spill store (odo_volume_enable_spill first)");
+  if (volume_sync(v)) return -1;
+  VolSpillCounters c;
+  HIP_OK(hipMemcpyAsync(&c, v->d_spill_ctr, sizeof(c), hipMemcpyDeviceToHost, v->own));
+  HIP_OK(hipStreamSynchronize(v->own));
+  const size_t from = (size_t)std::min<unsigned long long>(c.written, (unsigned long long)v->spill_capacity);
+  const size_t points = (size_t)(v->spill_capacity + kSpillGuard) - from;
+  std::vector<uint8_t> host;
+  try { host.resize(sizeof(float4) * points); } catch (...) { return fail("out of memory"); }
+  const void* at[3] = {v->d_spill_xyz0 + from, v->d_spill_nrmw + from, v->d_spill_rgba ? v->d_spill_rgba + from : nullptr};
+  const size_t bytes[3] = {sizeof(float4) * points, sizeof(float4) * points, sizeof(uint32_t) * points};
+  long bad = 0;
+  for (int b = 0; b < 3; b++) {
+    if (!at[b]) continue;
+    HIP_OK(hipMemcpyAsync(host.data(), at[b], bytes[b], hipMemcpyDeviceToHost, v->own));
+    HIP_OK(hipStreamSynchronize(v->own));
+    for (size_t i = 0; i < bytes[b]; i++) bad += host[i] != 0xAB;
+  }
+  *n_changed = bad;
+  return 0;
+}
+
+extern "C" int odo_volume_set_follow(odo_volume* v, const odo_volume_follow_params* p) {
+  if (!v) return fail("odo_volume_set_follow: NULL volume");
+  if (!p) { v->follow = 0; return 0; }
+  if (!(std::isfinite(p->focus) && p->focus >= 0.0f)) return fail("odo_volume_set_follow: focus must be finite and >= 0");
+  if (p->threshold < 1) return fail("odo_volume_set_follow: threshold %d (at least 1 voxel)", p->threshold);
+  if (volume_shift_buffers("odo_volume_set_follow", v)) return -1;   // (here, not in an attached tracker's frame call)
+  v->fp = *p; v->follow = 1;
+  return 0;
+}
+
+// The follow step: the shift that the pose asks for (volume_shift_math.h, follow_shift), applied. d_out may be nullptr.
+static int volume_follow(const char* who, odo_volume* v, const float* A, int* d_out) {
+  if (!v->follow) return fail("%s: no follow parameters (odo_volume_set_follow first)", who);
+  const int n[3] = {v->p.nx, v->p.ny, v->p.nz};
+  int d[3];
+  if (!follow_shift(A, v->p.origin, n, v->p.voxel_size, v->fp.focus, v->fp.threshold, d))
+    return fail("%s: the pose has a non-finite entry (a frame whose Solve failed?)", who);
+  if (volume_shift(who, v, d)) return -1;
+  if (d_out) for (int c = 0; c < 3; c++) d_out[c] = d[c];
+  return 0;
+}
+
+extern "C" int odo_volume_follow(odo_volume* v, const float abs_pose_colmajor[16], int d_out[3]) {
+  if (!v || !abs_pose_colmajor) return fail("odo_volume_follow: NULL arg");
+  if (!pose_finite(abs_pose_colmajor)) return fail("odo_volume_follow: the pose has a non-finite entry (a frame whose Solve failed?)");
+  return volume_follow("odo_volume_follow", v, abs_pose_colmajor, d_out);
+}

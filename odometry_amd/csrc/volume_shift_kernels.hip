@@ -1,0 +1,195 @@
+// volume_shift_kernels.hip — the moving TSDF volume's kernels (volume_shift.hip.h) as a translation unit of their own, plus their
+// host-side launchers: the shift of both grids by whole voxels, and the spill of the surface points that a shift destroys into the
+// volume's store. The rules are volume_shift_math.h's, the points volume_math.h's and volume_colour_math.h's (fp32, one rounding per
+// operation: the unit is built with -ffp-contract=off and correctly rounded divide / sqrt), so a spilled point is bit for bit the
+// point odo_volume_extract / _extract_colour gives for the same edge of the pre-shift grid. include/odometry_hip.h, odo_volume_shift;
+// DESIGN.md section 9.9.
+#include <hip/hip_runtime.h>
+#include "volume_shift.hip.h"
+#include "volume_shift_math.h"
+#include "volume_colour_math.h"
+#include "volume_scan.hip.h"
+
+namespace odo {
+
+// ---- the shift -------------------------------------------------------------------------------------------------------------------
+// Four x-consecutive voxels of the new grid per thread. Aligned on the destination: with nx % 4 == 0 (Vec) a thread's four words are
+// one 16-byte store and a wave's stores cover 1 KiB without a gap; the sources are dx words off and are read as one 16-byte load only
+// when dx % 4 == 0 and all four lie inside the old row, as four dword loads otherwise (the neighbouring lanes use the rest of every
+// line they touch). A row whose (j + dy, k + dz) lies outside the old grid loads nothing and stores zeros. Any nx: the same walk with
+// dword stores and a guard at the row's end.
+template <bool Vec>
+__device__ __forceinline__ void shift_quad(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, size_t drow, size_t srow, bool row_in,
+                                           int i0, int nx, int dx) {
+  uint32_t w[4] = {0u, 0u, 0u, 0u};
+  if (row_in) {
+    int s0, s3;
+    const bool in0 = shift_source(i0, dx, nx, &s0), in3 = shift_source(i0 + 3, dx, nx, &s3);
+    if (Vec && (dx & 3) == 0 && in0 && in3) {
+      const uint4 q = *reinterpret_cast<const uint4*>(src + srow + s0);   // (s0 = i0 + dx, a multiple of 4; rows are multiples of 4 words)
+      w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
+    } else {
+#pragma unroll
+      for (int t = 0; t < 4; t++) {
+        int si;
+        if (i0 + t < nx && shift_source(i0 + t, dx, nx, &si)) w[t] = src[srow + si];
+      }
+    }
+  }
+  if (Vec) {
+    *reinterpret_cast<uint4*>(dst + drow + i0) = make_uint4(w[0], w[1], w[2], w[3]);
+  } else {
+#pragma unroll
+    for (int t = 0; t < 4; t++)
+      if (i0 + t < nx) dst[drow + i0 + t] = w[t];
+  }
+}
+
+// A block is kVolShiftLanes x kVolShiftRows threads: threadIdx.y picks one of kVolShiftRows consecutive rows j of the plane k, and the
+// row's quads are walked kVolShiftLanes at a time; blockIdx.y walks the planes (in strides of the grid's y extent, which the launch
+// keeps within 65 535). No thread divides: j, k and the quad come straight from the launch geometry.
+template <bool Vec>
+__global__ void __launch_bounds__(kVolShiftBlock) volume_shift_kernel(VolShiftArgs a) {
+  const int qpr = (a.nx + 3) >> 2;                                             // quads per row
+  const int j = (int)blockIdx.x * kVolShiftRows + (int)threadIdx.y;
+  if (j >= a.ny) return;
+  int sj, sk;
+  const bool j_in = shift_source(j, a.dy, a.ny, &sj);
+  for (int k = (int)blockIdx.y; k < a.nz; k += (int)gridDim.y) {
+    const bool row_in = j_in & shift_source(k, a.dz, a.nz, &sk);
+    const size_t drow = ((size_t)k * a.ny + j) * a.nx, srow = row_in ? ((size_t)sk * a.ny + sj) * a.nx : 0;
+    for (int qi = (int)threadIdx.x; qi < qpr; qi += kVolShiftLanes) {
+      shift_quad<Vec>(a.src, a.dst, drow, srow, row_in, qi << 2, a.nx, a.dx);
+      if (a.src_col) shift_quad<Vec>(a.src_col, a.dst_col, drow, srow, row_in, qi << 2, a.nx, a.dx);
+    }
+  }
+}
+
+void launch_volume_shift(const VolShiftArgs& a, hipStream_t s) {
+  const dim3 grid((unsigned)((a.ny + kVolShiftRows - 1) / kVolShiftRows), (unsigned)(a.nz < 65535 ? a.nz : 65535)), block(kVolShiftLanes, kVolShiftRows);
+  if ((a.nx & 3) == 0) hipLaunchKernelGGL(volume_shift_kernel<true>, grid, block, 0, s, a);
+  else hipLaunchKernelGGL(volume_shift_kernel<false>, grid, block, 0, s, a);
+}
+
+// ---- the spill -------------------------------------------------------------------------------------------------------------------
+// volume_count_kernel's ballots with the predicate ANDed in: the edge a -> b counts iff it carries a point and a or b leaves.
+__global__ void __launch_bounds__(kVolExtBlock) volume_spill_count_kernel(VolSpillArgs sa) {
+  const VolExtractArgs& a = sa.a;
+  __shared__ int sh[kVolExtBlock / 64];
+  const int v = blockIdx.x * kVolExtBlock + threadIdx.x;
+  bool ex = false, ey = false, ez = false;
+  if (v < a.n) {
+    const uint32_t va = a.g.vox[v];
+    if (vox_w(va) > 0) {
+      int i, j, k;
+      vox_ijk(a.g, v, &i, &j, &k);
+      const size_t sy = (size_t)a.g.nx, sz = (size_t)a.g.nx * a.g.ny;
+      const bool la = shift_leaves(i, sa.dx, a.g.nx) || shift_leaves(j, sa.dy, a.g.ny) || shift_leaves(k, sa.dz, a.g.nz);
+      ex = i + 1 < a.g.nx && (la || shift_leaves(i + 1, sa.dx, a.g.nx)) && vox_edge(va, a.g.vox[v + 1]);
+      ey = j + 1 < a.g.ny && (la || shift_leaves(j + 1, sa.dy, a.g.ny)) && vox_edge(va, a.g.vox[v + sy]);
+      ez = k + 1 < a.g.nz && (la || shift_leaves(k + 1, sa.dz, a.g.nz)) && vox_edge(va, a.g.vox[v + sz]);
+    }
+  }
+  const unsigned long long bx = __ballot(ex), by = __ballot(ey), bz = __ballot(ez);
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    unsigned long long* wm = a.wave_mask + 3 * ((size_t)blockIdx.x * (kVolExtBlock / 64) + w);
+    wm[0] = bx; wm[1] = by; wm[2] = bz;
+    sh[w] = __popcll(bx) + __popcll(by) + __popcll(bz);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int t = 0;
+    for (int q = 0; q < kVolExtBlock / 64; q++) t += sh[q];
+    a.blk[blockIdx.x] = t;
+  }
+}
+
+// One block: exclusive scan of the per-block counts (volume_scan_kernel's walk); the sum is left for scatter's clamp and advance.
+__global__ void __launch_bounds__(kVolScanThreads) volume_spill_scan_kernel(VolSpillArgs sa) {
+  const VolExtractArgs& a = sa.a;
+  __shared__ unsigned wsum[kVolScanThreads / 64];
+  const int t = threadIdx.x;
+  unsigned long long base = 0;
+  for (int c0 = 0; c0 < a.nblk; c0 += kVolScanThreads) {
+    const int b = c0 + t;
+    const unsigned s = b < a.nblk ? (unsigned)a.blk[b] : 0u;   // (<= 3 072 per block: a chunk's sum stays far below 2^32)
+    const ScanRank r = scan_block<kVolScanThreads>(s, wsum);
+    if (b < a.nblk) a.blk_off[b] = base + (unsigned long long)r.rank;
+    base += r.total;
+    __syncthreads();   // wsum is written again
+  }
+  if (t == 0) sa.sc->pending = base;
+}
+
+// volume_scatter_kernel's points behind the store's earlier ones: index = written + block offset + rank; nothing at or beyond
+// capacity is written. The colour, when the store has one, is volume_extract_colour_kernel's.
+__global__ void __launch_bounds__(kVolExtBlock) volume_spill_scatter_kernel(VolSpillArgs sa) {
+  const VolExtractArgs& a = sa.a;
+  const int v = blockIdx.x * kVolExtBlock + threadIdx.x;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const unsigned long long* wm = a.wave_mask + 3 * (size_t)blockIdx.x * (kVolExtBlock / 64);
+  const unsigned long long bx = wm[3 * w], by = wm[3 * w + 1], bz = wm[3 * w + 2];
+  const unsigned long long bit = 1ull << lane;
+  if (v >= a.n || !((bx | by | bz) & bit)) return;
+  int pre = 0;
+  for (int q = 0; q < 3 * w; q++) pre += __popcll(wm[q]);
+  const unsigned long long below = bit - 1ull, cap = (unsigned long long)a.capacity;
+  unsigned long long idx = sa.sc->written + a.blk_off[blockIdx.x] +
+                           (unsigned long long)(pre + __popcll(bx & below) + __popcll(by & below) + __popcll(bz & below));
+  if (idx >= cap) return;   // (so are this voxel's later edges)
+  int i, j, k;
+  vox_ijk(a.g, v, &i, &j, &k);
+  const uint32_t va = a.g.vox[v];
+  float ga[3], gb[3];
+  const bool has_a = vox_gradient(a.g, v, i, j, k, va, ga);
+  const float cx = vox_centre(a.g.ox, i, a.g.vs), cy = vox_centre(a.g.oy, j, a.g.vs), cz = vox_centre(a.g.oz, k, a.g.vs);
+  const uint32_t ca = sa.col ? sa.col[v] : 0u;
+  const unsigned long long bits[3] = {bx, by, bz};
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    if (!(bits[c] & bit)) continue;
+    if (idx >= cap) return;
+    const int dx = c == 0, dy = c == 1, dz = c == 2;
+    const long long vb_i = vox_corner_word(a.g, v, 1 << c);
+    const uint32_t vb = a.g.vox[vb_i];
+    const bool has_b = vox_gradient(a.g, vb_i, i + dx, j + dy, k + dz, vb, gb);
+    const VoxEdgePoint e = vox_edge_point(va, vb, has_a, ga, has_b, gb, cx, cy, cz, a.g.vs, dx, dy, dz);
+    a.xyz0[idx] = make_float4(e.x, e.y, e.z, 0.0f);
+    a.nrmw[idx] = make_float4(e.nx, e.ny, e.nz, e.w);
+    if (sa.col) sa.rgba[idx] = colour_interpolate(ca, sa.col[vb_i], vox_alpha(va, vb));
+    idx++;
+  }
+}
+
+// One thread, behind the scatter that read `written`: the counters move on.
+__global__ void volume_spill_advance_kernel(VolSpillArgs sa) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  // Both stores carry values computed from the loads, so neither can be issued before its loads have returned, whichever kind of
+  // load the compiler picks. Volatile in addition makes the three reads vector loads that are each waited for: read from the
+  // gfx950 disassembly, flat_load_dwordx2 ... sc0 sc1 followed by s_waitcnt vmcnt(0), three times, in front of the two stores.
+  // (Only supposed, not shown: that a uniform read through a plain pointer, which the compiler may turn into a scalar load, can be
+  // overtaken by a store of this thread that does not depend on it. An earlier form of this kernel had such a store.)
+  volatile VolSpillCounters* sc = sa.sc;
+  const unsigned long long written = sc->written, total = sc->total, pending = sc->pending;
+  const unsigned long long cap = (unsigned long long)sa.a.capacity, end = written + pending;
+  sc->total = total + pending;
+  sc->written = end < cap ? end : cap;   // (pending stays: the next spill's scan writes it before anything reads it)
+}
+
+void launch_volume_spill(const VolSpillArgs& a, hipStream_t s) {
+  const dim3 grid(a.a.nblk), block(kVolExtBlock);
+  hipLaunchKernelGGL(volume_spill_count_kernel, grid, block, 0, s, a);
+  hipLaunchKernelGGL(volume_spill_scan_kernel, dim3(1), dim3(kVolScanThreads), 0, s, a);
+  hipLaunchKernelGGL(volume_spill_scatter_kernel, grid, block, 0, s, a);
+  hipLaunchKernelGGL(volume_spill_advance_kernel, dim3(1), dim3(64), 0, s, a);
+}
+
+void launch_volume_spill_stage(const VolSpillArgs& a, int stage, hipStream_t s) {
+  const dim3 grid(a.a.nblk), block(kVolExtBlock);
+  if (stage == 0) hipLaunchKernelGGL(volume_spill_count_kernel, grid, block, 0, s, a);
+  else if (stage == 1) hipLaunchKernelGGL(volume_spill_scan_kernel, dim3(1), dim3(kVolScanThreads), 0, s, a);
+  else hipLaunchKernelGGL(volume_spill_scatter_kernel, grid, block, 0, s, a);
+}
+
+}  // namespace odo

@@ -27,7 +27,10 @@
             over the drive) with no volume, the pinned grid and the large grid attached, runs interleaved mode by mode: frames/s
             (median, spread), the tracker's host timing, Solves redone on the step launches and depth jobs redone. Mode `coloured` is
             the pinned grid with a colour grid, every frame's colour named with odo_tracker_frame_colour (the price of colour:
-            --modes coloured,pinned,none alternating in one call).
+            --modes coloured,pinned,none alternating in one call). Mode `follow` is the pinned grid with a spill store of 2^22 points
+            and api.TsdfVolume.set_follow's defaults (focus max_depth / 2, threshold min(dims) // 8): the window moves with the
+            camera; its lines carry `shifts`, the times the window moved during the timed frames (the window is read after every
+            frame, a host call without a wait, in this mode only).
 
   icp       the frame-to-model alignment's two kernels timed with events (api.TsdfVolume.icp_time: `reps` launches of
             volume_icp_rows_kernel, then of volume_icp_step_kernel's fold, each batch between two events on the volume's stream):
@@ -36,10 +39,18 @@
             over `runs` batches, the pairs and the blocks, then the wall time of whole api.TsdfVolume.track calls (ray-cast, the
             alignment's launches, its allocations and its one wait).
 
+  shift     the moving volume's launches timed with events (api.TsdfVolume.shift_time: batches of `reps` between two events on the
+            volume's stream, the shift not applied): the pinned and the large grid after `frames` integrations at their true poses,
+            without and with a colour grid, each with a spill store, for a one-layer shift d = (0, 0, 1) and a quarter-grid shift
+            d = (0, 0, nz / 4). One JSON line per case with the medians over `runs` batches of the shift, of a device-to-device
+            hipMemcpyAsync of the same bytes, of a hipMemsetAsync of the same bytes, and of the spill's count, scan and scatter,
+            with the bytes moved and the points that shift spills.
+
   python tools/volume_cost.py kernels [--frames 10] [--extractions 3] [--json FILE]
   python tools/volume_cost.py icp [--frames 10] [--runs 7] [--reps 50]
+  python tools/volume_cost.py shift [--frames 10] [--runs 7] [--reps 20]
   python tools/volume_cost.py summary DIR [--json FILE]
-  python tools/volume_cost.py track [--runs 3] [--steps 200] [--warmup 20] [--frames 100] [--modes none,pinned,large[,coloured]]
+  python tools/volume_cost.py track [--runs 3] [--steps 200] [--warmup 20] [--frames 100] [--modes none,pinned,large[,coloured][,follow]]
 
 A build without the volume is measured with tools/rgbd_cost.py --modes tum (the same drive and loop as `track`'s mode `none`).
 """
@@ -65,10 +76,13 @@ GRIDS = dict(pinned=dict(dims=(240, 128, 200), origin=(-4.8, -3.3, 0.4)),
 
 def make_volume(owner, grid, size, K, colour=False):
     from odometry_amd import api
-    g = GRIDS["pinned" if grid == "coloured" else grid]
+    g = GRIDS["pinned" if grid in ("coloured", "follow") else grid]
     vol = api.TsdfVolume(owner, g["dims"], VS, g["origin"], MU, MAX_DEPTH, 65535, size, K, 1000.0)
     if colour or grid == "coloured":
         vol.enable_colour(3, False, 255)
+    if grid == "follow":
+        vol.enable_spill(1 << 22)
+        vol.set_follow(MAX_DEPTH / 2, min(g["dims"]) // 8)
     return vol
 
 
@@ -194,8 +208,9 @@ def track(args):
             if coloured:
                 trk.frame_colour(cdev[order[0]])
             trk.init(*dev[order[0]])
-            kf = 0
+            kf = shifts = 0
             t0 = None
+            win = vol.window()[0] if mode == "follow" else None
             for k in range(1, last + 1):
                 if k == args.warmup + 1:
                     trk._sync()
@@ -206,6 +221,10 @@ def track(args):
                 if coloured:
                     trk.frame_colour(cdev[order[k]])
                 kf += trk.track_into(*dev[order[k]], T, A)
+                if win is not None:
+                    now = vol.window()[0]
+                    shifts += t0 is not None and now != win
+                    win = now
             trk._sync()            # (waits for the pending integrations as well)
             fps = args.steps / (time.perf_counter() - t0)
             tm = trk.timing()
@@ -213,9 +232,12 @@ def track(args):
             groups, redo1 = trk.persistent_stats()
             res[mode].append(fps)
             st = vol.stats() if vol is not None else {}
+            if mode == "follow":
+                st = dict(st, shifts=int(shifts), window=list(win), spilled=len(vol.spilled(clear=True)[0]))
             print(json.dumps(dict(run=run, mode=mode, fps=round(fps, 1), keyframes=kf + 1, lm_persistent_groups=groups,
                                   solves_redone=redo1 - redo0, depth_jobs_redone=djob1 - djob0, frames_integrated=st.get("frames"),
-                                  updated_last=st.get("updated"), in_band_last=st.get("in_band"), **{k_: round(v, 1) for k_, v in tm.items()})), flush=True)
+                                  updated_last=st.get("updated"), in_band_last=st.get("in_band"),
+                                  **{k_: st[k_] for k_ in ("shifts", "window", "spilled") if k_ in st}, **{k_: round(v, 1) for k_, v in tm.items()})), flush=True)
     trk.attach_volume(None)
     print(json.dumps(dict(summary=True, **{m: dict(median_fps=round(float(np.median(res[m])), 1),
                                                    spread=[round(min(res[m]), 1), round(max(res[m]), 1)]) for m in modes})))
@@ -255,6 +277,37 @@ def icp(args):
     ctx.close()
 
 
+def shift(args):
+    from odometry_amd import api, synth
+    seq = synth.make_rgbd_sequence(args.frames, seed=0)
+    K = (seq["K"]["f0"], seq["K"]["cx0"], seq["K"]["cy0"])
+    ctx = api.Context(0)
+    names = ("shift", "copy", "memset", "spill_count", "spill_scan", "spill_scatter")
+    for grid in ("pinned", "large"):
+        nx, ny, nz = GRIDS[grid]["dims"]
+        for coloured in (False, True):
+            vol = make_volume(ctx, grid, (synth.TUM_ROWS, synth.TUM_COLS), K, colour=coloured)
+            cdev = [synth.colour_from_gray(g, 3, False, tint_seed=1) for g in seq["gray"]]
+            for d, c, A in zip(seq["depth"], cdev, seq["poses"]):
+                vol.integrate(d, A, colour=c if coloured else None)
+            vol.enable_spill(1 << 22)
+            points = len(vol.extract(1 << 22)[0])
+            for tag, d in (("one layer", (0, 0, 1)), ("quarter grid", (0, 0, nz // 4))):
+                us = np.array([vol.shift_time(d, reps=args.reps) for _ in range(args.runs)])
+                row = dict(grid=grid, coloured=coloured, shift=tag, d=list(d), voxels=nx * ny * nz, extraction_points=points,
+                           bytes_read_and_written=2 * (8 if coloured else 4) * nx * ny * nz)
+                for k, n in enumerate(names):
+                    row[n + "_us_median"] = round(float(np.median(us[:, k])), 2)
+                    row[n + "_us_min_max"] = [round(float(us[:, k].min()), 2), round(float(us[:, k].max()), 2)]
+                print(json.dumps(row), flush=True)
+            for tag, d in (("one layer", (0, 0, 1)), ("quarter grid", (0, 0, nz // 4))):   # what either really spills, applied in turn
+                vol.shift(d)
+                got = vol.spilled(clear=True, with_dropped=True)
+                print(json.dumps(dict(grid=grid, coloured=coloured, shift=tag, applied=True, spilled=len(got[0]), dropped=got[-1])), flush=True)
+            vol.close()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -275,8 +328,12 @@ def main():
     i.add_argument("--frames", type=int, default=10)
     i.add_argument("--runs", type=int, default=7)
     i.add_argument("--reps", type=int, default=50)
+    h = sub.add_parser("shift")
+    h.add_argument("--frames", type=int, default=10)
+    h.add_argument("--runs", type=int, default=7)
+    h.add_argument("--reps", type=int, default=20)
     args = ap.parse_args()
-    dict(kernels=kernels, summary=summary, track=track, icp=icp)[args.cmd](args)
+    dict(kernels=kernels, summary=summary, track=track, icp=icp, shift=shift)[args.cmd](args)
 
 
 if __name__ == "__main__":
