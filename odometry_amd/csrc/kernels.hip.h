@@ -1312,9 +1312,9 @@ __device__ __forceinline__ void lm_hot_store(const LmHot& h, LmState& s) {  // o
 __device__ __forceinline__ void lm_state_machine_hot(LmHot& h, const StepLevel* lv, int n_levels, float lambda0, float precision,
                                                      LmState& s_sh, const double* acc_sh, LmTraceRow* __restrict__ trace,
                                                      float* __restrict__ cost_stat, bool publisher,
-                                                     unsigned long long* smdbg = nullptr, int stop_level = 0) {
+                                                     unsigned long long* smdbg = nullptr, int stop_level = 0, bool have_sums = true) {
   const int t = threadIdx.x;
-  if (t < 64) {
+  if (t < 64 && have_sums) {   // (have_sums: wave 0's own; false = its gather gave up, only the closing barrier is left to do)
     unsigned long long c0 = smdbg ? __builtin_readcyclecounter() : 0, c1 = c0, c2 = c0, c3 = c0;
     const int iter0 = h.iter, lvl0 = h.level;
     const float err_last0 = h.err_last;
@@ -2084,7 +2084,7 @@ ODO_KERNEL void __launch_bounds__(kCoarseBlock) lm_coarse_full_kernel_batch(cons
 // Placement: blocks are dealt round-robin over the 8 XCDs, so the launch has 8 x K blocks of which every eighth takes part
 // (they share an XCD and its L2; the others return at once). That is for speed only: the workgroups tell each other their XCC id
 // first, and only if all agree do the rows go out as plain stores (they stay in that L2); otherwise as agent-scope stores, which
-// are coherent at any placement. Every wait is bounded by the device wall clock (kFineWaitTicks: 4 ms): a workgroup that waits longer gives up
+// are coherent at any placement. (A launch whose workgroups were picked by their XCC id — a home XCD — has nothing to ask: `placed`.) Every wait is bounded by the device wall clock (kFineWaitTicks: 4 ms): a workgroup that waits longer gives up
 // and the Solve reports status -2 (the host redoes it on the step launches) instead of hanging the device.
 // =============================================================================================
 constexpr int kFineGran = 2 * ODO_NACC;          // granules per partial row
@@ -2240,6 +2240,19 @@ __device__ __forceinline__ void fine_publish(unsigned long long* __restrict__ bu
     __hip_atomic_store(g + 1, g1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
+// Levels of up to kFineSoloRows virtual blocks are gathered by wave 0 alone (lm_fine_body, step (c)): kFineSoloU rows per segment.
+constexpr int kFineSoloRows = 8;
+constexpr int kFineSoloU = kFineSoloRows / 8;
+static_assert(kFineSoloRows % 8 == 0 && kFineSoloRows <= 8 * kFineChunk, "whole segments, one chunk of the four-wave gather");
+// Lane l < 32 gets lane l + 32's x (lanes >= 32 keep theirs): v_permlane32_swap exchanges the upper half of its first operand
+// with the lower half of its second, so with x as both the second result holds the upper half's x in either half.
+__device__ __forceinline__ double fine_upper_half(double x) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+  const unsigned lo = (unsigned)b, hi = (unsigned)(b >> 32);
+  const auto rl = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+  const auto rh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+  return __longlong_as_double((long long)(((unsigned long long)rh[1] << 32) | (unsigned long long)rl[1]));
+}
 __device__ __forceinline__ int fine_xcc_id() {
   int v;
   asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
@@ -2341,7 +2354,8 @@ __device__ __forceinline__ float fine_tdist_sigma(unsigned long long* __restrict
 // kTrace = false: no per-evaluation trace rows / cost statistics (see lm_coarse_body's kFull) — the trackers' optimisers.
 template <bool kTdist, bool kTrace>
 __device__ __forceinline__ void lm_fine_body(const StepArgs& a, const StepLaunch& q, int K, int w, unsigned long long* __restrict__ xbuf,
-                                             int fault, int lo_level, const unsigned* __restrict__ lv_src) {
+                                             int fault, int lo_level, const unsigned* __restrict__ lv_src, bool placed) {
+  // placed (launch-uniform): the caller picked this launch's workgroups BY their XCC id — they share an XCD, nothing to ask
 #if ODO_PHASE_STAMPS
   const unsigned long long w_entry = (unsigned long long)wall_clock64();
 #endif
@@ -2367,7 +2381,7 @@ __device__ __forceinline__ void lm_fine_body(const StepArgs& a, const StepLaunch
 #pragma unroll
     for (int i = 0; i < 4; i++) sm_sh[i] = 0;
     // where am I? (agent-scope store: this exchange must work at any placement)
-    __hip_atomic_store(place + w, ((unsigned long long)(unsigned)fine_xcc_id() << 32) | tag_base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!placed) __hip_atomic_store(place + w, ((unsigned long long)(unsigned)fine_xcc_id() << 32) | tag_base, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   __syncthreads();
   // state in (left by the coarse launch, or initialised), a pending evaluation of an earlier launch consumed, pyramid walk started
@@ -2376,7 +2390,8 @@ __device__ __forceinline__ void lm_fine_body(const StepArgs& a, const StepLaunch
   LmHot hot;                    // wave 0's copy of the state between evaluations (lm_state_machine_hot)
   lm_hot_load(hot, s_sh);
   // does every workgroup of this launch share my XCD? (wave 0, lane i asks about workgroup i; the answer is the same everywhere)
-  if (t < 64) {
+  // A placed launch knows: no placement words, no polling, no barrier.
+  if (!placed && t < 64) {
     bool same = true, got = false;
     if (t < K) {
       unsigned long long pw = 0;
@@ -2393,8 +2408,8 @@ __device__ __forceinline__ void lm_fine_body(const StepArgs& a, const StepLaunch
     const bool all_got = __all(got), all_same = __all(same);
     if (t == 0) { local_sh = (all_got && all_same) ? 1 : 0; if (!all_got) bail_sh = 1; }
   }
-  __syncthreads();
-  const bool local = local_sh != 0;
+  if (!placed) __syncthreads();
+  const bool local = placed || local_sh != 0;
   constexpr int kS = 8;  // sub-lanes per quantity: 29 x 8 = 232 accumulating threads per half (the step kernel's)
   const int my_q = tl / kS, my_s = tl % kS;
   int rowA = 0, rowB = 0;
@@ -2496,51 +2511,128 @@ __device__ __forceinline__ void lm_fine_body(const StepArgs& a, const StepLaunch
     lap(c_eval);
 #endif
     // ---- (c): gather every row in the fold's order (lm_fused_prologue: segment seg adds rows seg, seg + 8, ... ascending) ----
-    double v = 0.0;
-    __builtin_amdgcn_s_setprio(0);  // waiting is not urgent: the depth stream's waves on this CU go first while we poll
-    if (fq < ODO_NACC && fseg < 8) {
-      for (int b0 = fseg; b0 < nblk; b0 += 8 * kFineChunk) {
-        FineG2 g2[kFineChunk];   // {hi granule, lo granule} of one double: one 16-byte load that bypasses L1
+    bool have_sums = true;   // (wave 0's) the gather below got every row
+    if (resident && nblk <= kFineSoloRows) {
+      // A small level: only wave 0 consumes the sums, so only wave 0 gathers — one poller in this CU's memory queue instead of
+      // four, no fold_sh round trip, no barrier between gather and state machine. Lane l: quantity l & 31, segments 4 (l >> 5) ..
+      // + 3, every row of them (<= kFineSoloU each) in flight before the first tag compare. The sums are the four-wave gather's
+      // bit for bit: per segment 0.0 + rows ascending, then 0.0 + segments 0 .. 7 (an empty segment adds its + 0.0 as there).
+      // The other waves go straight to the state machine's closing barrier. (resident: the barrier behind rows_store_z above is
+      // what keeps wave 0's state machine behind every wave's read of s_sh at the head of this evaluation.)
+      if (t < 64) {
+        // One base and one row bound per lane, the rows at constant offsets from them: a per-row index would be hoisted out of
+        // the evaluation loop row by row (29 VGPRs held through evaluation and state machine).
+        const int sq = t & 31, sg0 = 4 * (t >> 5), nrel = nblk - sg0;
+        const unsigned long long* row0 = buf + (size_t)sg0 * kFineGran + 2 * sq;
+        // The granules one by one, as relaxed agent-scope loads (L1-bypassing like the four-wave gather's): a volatile load is
+        // waited for on the spot (s_waitcnt vmcnt(0) behind each), eight of them are eight trips to L2 in a row. (The poll relies
+        // on what LLVM guarantees for atomics: a relaxed atomic load is neither hoisted out of the loop nor merged with the
+        // previous pass's. Every 8-byte granule carries its own tag, so two loads per pair cannot tear a value.)
+        unsigned long long gh[4][kFineSoloU] = {}, gl[4][kFineSoloU] = {};   // (set: an unset element of an absent row would carry
+                                                                             //  its register around the evaluation loop)
         bool all = false;
         FineDeadline dl = {0ull, 0ull, wait_limit};
+        __builtin_amdgcn_s_setprio(0);  // waiting is not urgent (see below)
         for (int spin = 0; !all; spin++) {
-          if (spin == 1) dl = FineDeadline::begin(wait_limit);   // the first pass succeeds three times in four: no clock read then
+          if (spin == 1) dl = FineDeadline::begin(wait_limit);
           if (spin > 0) { if (dl.expired(spin)) break; __builtin_amdgcn_s_sleep(1); }
-          all = true;
+          bool mine = true;
+          if (sq < ODO_NACC) {
 #pragma unroll
-          for (int u = 0; u < kFineChunk; u++) {
-            const int b = b0 + 8 * u;
-            if (b < nblk) g2[u] = *(const volatile FineG2Global*)(buf + (size_t)b * kFineGran + 2 * fq);  // re-read every pass, sc0 sc1
-          }
+            for (int j = 0; j < 4; j++)
 #pragma unroll
-          for (int u = 0; u < kFineChunk; u++) {
-            const int b = b0 + 8 * u;
-            if (b < nblk) all = all && (g2[u].x == tag) && (g2[u].z == tag);
+              for (int u = 0; u < kFineSoloU; u++)
+                if (j + 8 * u < nrel) {   // re-read every pass
+                  gh[j][u] = __hip_atomic_load(row0 + (j + 8 * u) * kFineGran, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                  gl[j][u] = __hip_atomic_load(row0 + (j + 8 * u) * kFineGran + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+#pragma unroll
+              for (int u = 0; u < kFineSoloU; u++)
+                if (j + 8 * u < nrel) mine = mine && ((unsigned)gh[j][u] == tag) && ((unsigned)gl[j][u] == tag);
           }
+          all = __all(mine);
         }
-        if (!all) bail_sh = 1;  // a workgroup of this Solve never published: report failure, do not hang
+        __builtin_amdgcn_s_setprio(3);
+        double vs[4] = {0.0, 0.0, 0.0, 0.0}, up[4];
+        if (sq < ODO_NACC) {
 #pragma unroll
-        for (int u = 0; u < kFineChunk; u++) {
-          const int b = b0 + 8 * u;
-          if (b < nblk) v += __longlong_as_double((long long)(((unsigned long long)g2[u].y << 32) | (unsigned long long)g2[u].w));
+          for (int j = 0; j < 4; j++)
+#pragma unroll
+            for (int u = 0; u < kFineSoloU; u++)
+              if (j + 8 * u < nrel) vs[j] += __longlong_as_double((long long)(((gh[j][u] >> 32) << 32) | (gl[j][u] >> 32)));
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) up[j] = fine_upper_half(vs[j]);   // segments 4 .. 7 come down to the lanes that hold 0 .. 3
+        if (t < ODO_NACC) {
+          double acc = 0.0;
+#pragma unroll
+          for (int j = 0; j < 4; j++) acc += vs[j];
+#pragma unroll
+          for (int j = 0; j < 4; j++) acc += up[j];
+          acc_sh[t] = acc;   // (written and read by wave 0 only)
+        }
+        have_sums = all;
+        // A workgroup of this Solve never published: report failure, do not hang. The flag is read block-uniformly at the loop's
+        // head, behind the closing barrier. The other waves also read it once earlier, just behind the rows barrier of THIS
+        // evaluation (the scale passes' give-up): wave 0 can only write it a whole wait bound (milliseconds) after it passed that
+        // barrier itself, so a wave would have to stall that long between the barrier and its read to see it there — the window
+        // the four-wave gather has always had between its polling waves and the other four.
+        if (!all && t == 0) bail_sh = 1;
+      }
+      lap(c_xchg);
+    } else {
+      double v = 0.0;
+      __builtin_amdgcn_s_setprio(0);  // waiting is not urgent: the depth stream's waves on this CU go first while we poll
+      if (fq < ODO_NACC && fseg < 8) {
+        for (int b0 = fseg; b0 < nblk; b0 += 8 * kFineChunk) {
+          FineG2 g2[kFineChunk] = {};   // {hi granule, lo granule} of one double (set: see above)
+          bool all = false;
+          FineDeadline dl = {0ull, 0ull, wait_limit};
+          for (int spin = 0; !all; spin++) {
+            if (spin == 1) dl = FineDeadline::begin(wait_limit);   // the first pass succeeds three times in four: no clock read then
+            if (spin > 0) { if (dl.expired(spin)) break; __builtin_amdgcn_s_sleep(1); }
+            all = true;
+#pragma unroll
+            for (int u = 0; u < kFineChunk; u++) {
+              const int b = b0 + 8 * u;
+              if (b < nblk) {   // re-read every pass; the two granules as relaxed agent-scope loads (see the solo gather)
+                const unsigned long long h = __hip_atomic_load(buf + (size_t)b * kFineGran + 2 * fq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const unsigned long long l = __hip_atomic_load(buf + (size_t)b * kFineGran + 2 * fq + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                g2[u].x = (unsigned)h; g2[u].y = (unsigned)(h >> 32); g2[u].z = (unsigned)l; g2[u].w = (unsigned)(l >> 32);
+              }
+            }
+#pragma unroll
+            for (int u = 0; u < kFineChunk; u++) {
+              const int b = b0 + 8 * u;
+              if (b < nblk) all = all && (g2[u].x == tag) && (g2[u].z == tag);
+            }
+          }
+          if (!all) bail_sh = 1;  // a workgroup of this Solve never published: report failure, do not hang
+#pragma unroll
+          for (int u = 0; u < kFineChunk; u++) {
+            const int b = b0 + 8 * u;
+            if (b < nblk) v += __longlong_as_double((long long)(((unsigned long long)g2[u].y << 32) | (unsigned long long)g2[u].w));
+          }
         }
       }
-    }
-    __builtin_amdgcn_s_setprio(3);
-    if (fseg < 8) fold_sh[fseg * 32 + fq] = v;
-    __syncthreads();
-    if (t < ODO_NACC) {
-      double acc = 0.0;
+      __builtin_amdgcn_s_setprio(3);
+      if (fseg < 8) fold_sh[fseg * 32 + fq] = v;
+      __syncthreads();
+      if (t < ODO_NACC) {
+        double acc = 0.0;
 #pragma unroll
-      for (int g = 0; g < 8; g++) acc += fold_sh[g * 32 + t];
-      acc_sh[t] = acc;
+        for (int g = 0; g < 8; g++) acc += fold_sh[g * 32 + t];
+        acc_sh[t] = acc;
+      }
+      // (no second barrier: written and read by wave 0 only, see lm_coarse_body; bail_sh was set in front of the barrier above)
+      lap(c_xchg);
+      if (bail_sh) break;
     }
-    // (no second barrier: written and read by wave 0 only, see lm_coarse_body; bail_sh was set in front of the barrier above)
-    lap(c_xchg);
-    if (bail_sh) break;
     // ---- (d): the state machine, every workgroup for itself ----
     lm_state_machine_hot(hot, lv_sh, a.n_levels, a.lambda0, a.precision, s_sh, acc_sh, (kTrace ? a.trace : (LmTraceRow*)nullptr), a.cost_stat, publisher,
-                         (ODO_DBG(a) && publisher) ? sm_sh : nullptr, a.stop_level);
+                         (ODO_DBG(a) && publisher) ? sm_sh : nullptr, a.stop_level, have_sums);
     lap(c_sm);
   }
 #if ODO_PHASE_STAMPS
@@ -2595,7 +2687,8 @@ __device__ __forceinline__ void lm_fine_entry(const StepArgs& a, int K, unsigned
   }
   if (!fine_on_home(a.fine_home) || lm_chain_skip(a)) return;
   const StepLaunch q = {a.st_in, a.st_out, a.part_in, a.part_out, a.seq, a.first_of_solve, a.span};
-  lm_fine_body<kTdist, kTrace>(a, q, K, (int)(blockIdx.x >> 3), xbuf, fault, lo_level, lm_kernarg_words());
+  // (home >= 0: every block that got here found itself on the home XCD — fine_on_home)
+  lm_fine_body<kTdist, kTrace>(a, q, K, (int)(blockIdx.x >> 3), xbuf, fault, lo_level, lm_kernarg_words(), a.fine_home >= 0);
 }
 #ifdef ODO_LM_CHAIN_TU
 static __global__ void __launch_bounds__(kFineThreads) lm_fine_kernel(StepArgs a, int K, unsigned long long* __restrict__ xbuf, int fault,
@@ -2640,10 +2733,11 @@ __device__ __forceinline__ void lm_fine_batch_entry(const StepArgs* __restrict__
     // nothing to evaluate here, but the launch number is the whole batch's: one workgroup carries the sequence's state from this
     // launch's input buffer to its output buffer (prologue + publish, no level at or above lo_level = none), as a step launch of a
     // finished sequence does
-    if (w == 0) lm_fine_body<false, kTrace>(a, q, 1, 0, a.xbuf, 0, ODO_MAX_LEVELS_K + 1, (const unsigned*)&table[i]);
+    if (w == 0) lm_fine_body<false, kTrace>(a, q, 1, 0, a.xbuf, 0, ODO_MAX_LEVELS_K + 1, (const unsigned*)&table[i], true);
     return;
   }
-  lm_fine_body<false, kTrace>(a, q, K, w, a.xbuf, fault, a.fine_lo, (const unsigned*)&table[i]);   // (a batched Solve never carries t-distribution weights: lm_batch_begin)
+  // (a batched Solve never carries t-distribution weights: lm_batch_begin; XCC ids known: a sequence's blocks were picked by theirs above)
+  lm_fine_body<false, kTrace>(a, q, K, w, a.xbuf, fault, a.fine_lo, (const unsigned*)&table[i], xcc.id[0] >= 0);
 }
 ODO_KERNEL void __launch_bounds__(kFineThreads) lm_fine_kernel_batch(const StepArgs* __restrict__ table, int n, int K, int seq,
                                                                      int first_of_solve, unsigned long long* span, int fault, XccIds xcc,
