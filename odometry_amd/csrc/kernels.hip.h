@@ -2214,6 +2214,23 @@ ODO_KERNEL void __launch_bounds__(kTsThreads) lm_tdist_scale_multi_kernel(const 
 
 constexpr int kFineThreads = 2 * kLmBlock;       // a workgroup works on TWO virtual blocks at a time, one per half
 constexpr int kFineKMax = 32;                     // workgroups of one launch: they wait for each other, so each needs a CU of the XCD (32) to itself
+// Which scale kernel takes n stored residuals (host side; the one copy of the rule — lm_launch_scale and the test harness call it).
+// list: a level a fused kernel could also take (<= 2 * kFineKMax virtual blocks) — one workgroup in the fused kernels' order. Otherwise
+// G workgroups of lm_tdist_scale_multi_kernel, eight residuals per thread until the grid is full, if the level `fits` their registers;
+// single_order: the order of the single-workgroup kernel that stands behind (or, when nothing fits, in place of) the multi launch.
+struct TdistScalePlan { int list, G, fits, single_order; };
+static inline TdistScalePlan tdist_scale_plan(int n) {
+  TdistScalePlan p;
+  p.list = (n <= 2 * kFineKMax * kLmBlock) ? 1 : 0;
+  const long per_wg = (long)kTsThreads * 8;
+  long G = (n + per_wg - 1) / per_wg;
+  if (G > kTsMaxWg) G = kTsMaxWg;
+  if (G < 2) G = 2;
+  p.G = (int)G;
+  p.fits = ((long)n <= G * kTsThreads * (long)kTsPerThread) ? 1 : 0;
+  p.single_order = (n <= 64 * kTdistChunksMax) ? 1 : 0;   // (what the single-workgroup kernel can hold in registers)
+  return p;
+}
 // t-distribution scale passes (robust == 2): one fp64 sum per 64-point chunk (wave) and pass, double-buffered by pass parity,
 // as a 16-byte granule pair {upper 32 bits | tag, lower 32 bits | tag}; the chunk's residual count as {count | tag} (pass 0 only).
 constexpr int kScaleChunks = 4 * 2 * kFineKMax;  // 256: four waves per virtual block, <= 2 * kFineKMax virtual blocks per level

@@ -1160,17 +1160,13 @@ static inline int lm_grid_for(const odo_lm* m, int level, int rows, int cols) {
 // odo_lm_tdist_stats counts them.
 static void lm_launch_scale(odo_lm* m, int n, int level) {
   hipStream_t s = m->ctx->stream;
-  if (n <= 2 * kFineKMax * kLmBlock) {
+  const TdistScalePlan plan = tdist_scale_plan(n);   // (kernels.hip.h)
+  if (plan.list) {
     hipLaunchKernelGGL(lm_tdist_scale_kernel, dim3(1), dim3(1024), 0, s, m->d_res, n, m->ust, level, m->d_scale, 1, (int*)nullptr);
     return;
   }
-  const long per_wg = (long)kTsThreads * 8;   // eight residuals per thread until the grid is full
-  long G = (n + per_wg - 1) / per_wg;
-  if (G > kTsMaxWg) G = kTsMaxWg;
-  if (G < 2) G = 2;
-  const bool fits = (long)n <= G * kTsThreads * (long)kTsPerThread;
-  const int single_order = (n <= 64 * kTdistChunksMax) ? 1 : 0;   // (what the single-workgroup kernel can hold in registers)
-  if (!m->ts_multi || !fits) {
+  const int G = plan.G, single_order = plan.single_order;
+  if (!m->ts_multi || !plan.fits) {
     hipLaunchKernelGGL(lm_tdist_scale_kernel, dim3(1), dim3(1024), 0, s, m->d_res, n, m->ust, level, m->d_scale, single_order, (int*)nullptr);
     return;
   }

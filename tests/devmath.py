@@ -117,7 +117,7 @@ def mirror_layout():
 ENTRIES = ("dm_layout_count", "dm_layout", "dm_dense_fast_ok", "dm_level_k", "dm_sincos", "dm_se3_exp", "dm_se3_roundtrip", "dm_se3_left_update",
            "dm_solve_damped", "dm_robust_weight", "dm_apply_step", "dm_depth_schedule", "dm_lm_script", "dm_sincos_pair_wave",
            "dm_se3_exp_wave", "dm_solve_damped_wave", "dm_apply_step_wave", "dm_pixels", "dm_dense_pixels", "dm_div32", "dm_div64",
-           "dm_callsites")
+           "dm_callsites", "dm_dense_runs", "dm_dense_eval", "dm_dense_eval_batch", "dm_tdist_scale")
 
 
 def _p(a):
@@ -287,6 +287,56 @@ class Ops:
         rc = self.lib.dm_dense_pixels(C.byref(L), _p(Tc), int(robust), C.c_float(huber_delta), C.c_float(scale_sqr), int(fast), _p(hit), _p(acc))
         assert rc == 0, "dm_dense_pixels: HIP error %d" % rc
         return hit, acc
+
+    # -- the dense scan block by block, the scale kernels (device only) --
+    @staticmethod
+    def _dense_level(I1, I2, D1, k):
+        rows, cols = I1.shape
+        return DenseLevel(I1.ctypes.data, I2.ctypes.data, D1.ctypes.data, rows, cols, LevelK(*k))
+
+    def dense_runs(self, rows, cols, cap, n_rows):
+        """((n_strips, n_rg, nblk), dense_block_run of every block [nblk, 5]) as the device computes them for grid cap `cap`."""
+        L = DenseLevel(None, None, None, rows, cols, LevelK(1.0, 0.0, 0.0, 0))
+        geom, out = np.zeros(3, np.int32), np.full((n_rows, 5), -1, np.int32)
+        rc = self.lib.dm_dense_runs(C.byref(L), int(cap), int(n_rows), _p(geom), _p(out))
+        assert rc == 0, "dm_dense_runs: HIP error %d" % rc
+        return tuple(int(v) for v in geom), out[:geom[2]]
+
+    def dense_eval(self, I1, I2, D1, k, T, cap, n_rows, robust=1, huber_delta=28.0, scale_sqr=1.0, plain_div=0):
+        """lm_dense_eval_kernel as launch_dense_eval launches it: the partial rows [n_rows, 29] (rows past the level's nblk keep their
+        0xAB fill)."""
+        I1, I2, D1 = _f32(I1), _f32(I2), _f32(D1)
+        L = self._dense_level(I1, I2, D1, k)
+        Tc = _f32(np.asarray(T, np.float32).T).reshape(16)
+        out = np.zeros((n_rows, 29), np.float64)
+        rc = self.lib.dm_dense_eval(C.byref(L), int(cap), _p(Tc), int(robust), C.c_float(huber_delta), C.c_float(scale_sqr), int(plain_div),
+                                    int(n_rows), _p(out))
+        assert rc == 0, "dm_dense_eval: HIP error %d" % rc
+        return out
+
+    def dense_eval_batch(self, items, plain_div=0):
+        """lm_dense_eval_batch_kernel over items = [dict(I1, I2, D1, k, T, cap, n_rows, robust, huber_delta, scale_sqr, active)]: one
+        array of partial rows per item."""
+        n = len(items)
+        keep = [[_f32(it[a]) for a in ("I1", "I2", "D1")] for it in items]
+        Ls = (DenseLevel * n)(*[self._dense_level(*imgs, it["k"]) for imgs, it in zip(keep, items)])
+        T = _f32(np.stack([np.asarray(it["T"], np.float32).T.reshape(16) for it in items]))
+        off = _i32(np.concatenate([[0], np.cumsum([it["n_rows"] for it in items])]))
+        out = np.zeros((int(off[-1]), 29), np.float64)
+        rc = self.lib.dm_dense_eval_batch(n, Ls, _p(_i32([it["cap"] for it in items])), _p(T), _p(_i32([it["robust"] for it in items])),
+                                          _p(_f32([it["huber_delta"] for it in items])), _p(_f32([it["scale_sqr"] for it in items])),
+                                          _p(_i32([it["active"] for it in items])), int(plain_div), _p(off), _p(out))
+        assert rc == 0, "dm_dense_eval_batch: HIP error %d" % rc
+        return [out[off[i]:off[i + 1]] for i in range(n)]
+
+    def tdist_scale(self, res, order, reps=1):
+        """The t-distribution scale of a residual vector (NaN: no residual). order 0: list order, 1: strided, 2: the product's launch
+        sequence. Returns (sigma^2 [reps] float32, info [reps, 4] = (G, gave up, writer: 0 list / 1 strided / 2 multi, 0))."""
+        res = _f32(res)
+        s2, info = np.zeros(reps, np.float32), np.zeros((reps, 4), np.int32)
+        rc = self.lib.dm_tdist_scale(_p(res), len(res), int(order), int(reps), _p(s2), _p(info))
+        assert rc == 0, "dm_tdist_scale: HIP error %d" % rc
+        return s2, info
 
     def dense_fast_ok(self, fl, cx, cy, rows, cols):
         return int(self.lib.dm_dense_fast_ok(float(fl), float(cx), float(cy), int(rows), int(cols)))

@@ -9,6 +9,11 @@
 // Every entry point takes HOST pointers, allocates, copies, launches on the null stream, synchronises, copies back and frees, and
 // returns the first HIP error code (0 = hipSuccess). Every kernel is a bounded loop over its cases: no waiting on memory, nothing of
 // the persistent kernels' hand-over paths, no inline assembly.
+//
+// For tests/test_gpu_dense_cases.py it also launches product kernels as they are: lm_dense_eval_kernel and lm_dense_eval_batch_kernel (dense.hip.h)
+// block by block with the grid cap chosen by the test, dense_block_run of every block, and the t-distribution scale kernels over a
+// residual vector (dm_tdist_scale). The only waiting among them is lm_tdist_scale_multi_kernel's own bounded exchange (4 ms a wait),
+// launched exactly as lm_launch_scale launches it, with its fall-back queued behind it.
 #include <hip/hip_runtime.h>
 #define ODO_LM_CHAIN_TU 1
 #define ODO_DENSE_KERNELS 1
@@ -239,6 +244,21 @@ __global__ void __launch_bounds__(kEachBlock) dense_pixel_kernel(DenseLevel L, D
 #pragma unroll
     for (int k = 0; k < ODO_NACC; k++) acc_out[(size_t)o * ODO_NACC + k] = acc[k];
   }
+}
+
+// ---- the dense scan's decomposition: dense_block_run of every block of a level ----------------------------------------------------
+__global__ void __launch_bounds__(64) dense_runs_kernel(DenseLevel L, int* __restrict__ out5) {
+  const DenseRun r = dense_block_run(L, (int)blockIdx.x);
+  if (threadIdx.x == 0) {
+    int* o = out5 + 5 * (size_t)blockIdx.x;
+    o[0] = r.strip; o[1] = r.rg; o[2] = r.rg0; o[3] = r.rg1; o[4] = r.count;
+  }
+}
+// A state as the evaluation kernels read it: the pose, `active`, `level`.
+__global__ void __launch_bounds__(64) dense_state_kernel(LmState* __restrict__ st, const float* __restrict__ T, int n, const int* __restrict__ active,
+                                                         int level) {
+  for (int i = (int)threadIdx.x; i < n * 16; i += 64) st[i / 16].T[i % 16] = T[i];
+  for (int i = (int)threadIdx.x; i < n; i += 64) { st[i].active = active[i]; st[i].level = level; }
 }
 
 // ---- the shared-reciprocal divisions against the plain `/` of the same unit -------------------------------------------------------
@@ -515,6 +535,141 @@ int dm_dense_pixels(const DenseLevel* L, const float* T, int robust, float huber
   const long n = (long)(L->cols - 8) * (L->rows - 8);
   if (L->cols > 8 && L->rows > 8) DM_LAUNCH(P, dense_pixel_kernel, each_grid(n), kEachBlock, D, a, dh, dacc);
   P.down(hit, dh, npx); P.down(acc, dacc, ODO_NACC * npx);
+  return P.done();
+}
+
+// ---- the dense scan block by block ----
+// A level as lm_dense_level describes it, with the grid cap given by the caller (the product's is kDenseGridCap; a small cap gives a
+// small frame the runs of several units the product builds above 1024 units): images uploaded, geometry and fast_ok filled in.
+static bool dense_device_level(Pool& P, const DenseLevel& H, int cap, DenseLevel* D) {
+  if (H.rows < 2 || H.cols < 2 || H.rows > 65535 || H.cols > 65535 || cap < 1 || cap > kDenseMaxBlocks) return false;
+  const size_t npx = (size_t)H.rows * H.cols;
+  memset(D, 0, sizeof(*D));
+  D->I1 = P.up(H.I1, npx); D->I2 = P.up(H.I2, npx); D->D1 = P.up(H.D1, npx);
+  D->rows = H.rows; D->cols = H.cols; D->k = H.k;
+  D->fast_ok = dense_fast_ok(H.k.fl, H.k.cx, H.k.cy, H.rows, H.cols);
+  dense_level_geometry(D, kDenseBlock, cap);
+  return true;
+}
+constexpr int kDmExpectLevel = 2;   // the level the states below sit on (any value: the kernels compare it with their argument)
+static LmState* dense_device_states(Pool& P, int n, const float* T, const int* active) {
+  LmState* st = P.zeros<LmState>(n);
+  const float* dT = P.up(T, 16 * (size_t)n);
+  const int* da = P.up(active, n);
+  DM_LAUNCH(P, dense_state_kernel, 1, 64, st, dT, n, da, kDmExpectLevel);
+  return st;
+}
+static double* dense_device_partials(Pool& P, int nblk) {   // every byte 0xAB: a row the kernel did not write shows
+  double* p = (double*)P.raw(sizeof(double) * ODO_NACC * (size_t)nblk);
+  if (p && P.err == hipSuccess) P.err = hipMemset(p, 0xAB, sizeof(double) * ODO_NACC * (size_t)nblk);
+  return p;
+}
+// geom3 = {n_strips, n_rg, nblk}; out5 = dense_block_run of blocks 0 .. nblk - 1 (n_rows: the rows out5 has room for).
+int dm_dense_runs(const DenseLevel* L, int cap, int n_rows, int* geom3, int* out5) {
+  DenseLevel D;
+  memset(&D, 0, sizeof(D));
+  D.rows = L->rows; D.cols = L->cols;
+  if (cap < 1 || cap > kDenseMaxBlocks) return (int)hipErrorInvalidValue;
+  dense_level_geometry(&D, kDenseBlock, cap);
+  geom3[0] = D.n_strips; geom3[1] = D.n_rg; geom3[2] = D.nblk;
+  if (D.nblk > n_rows) return (int)hipErrorInvalidValue;
+  Pool P;
+  int* d = P.zeros<int>(5 * (size_t)D.nblk);
+  DM_LAUNCH(P, dense_runs_kernel, D.nblk, 64, D, d);
+  P.down(out5, d, 5 * (size_t)D.nblk);
+  return P.done();
+}
+// lm_dense_eval_kernel launched as launch_dense_eval launches it (grid = nblk blocks of kDenseBlock threads) on a state with
+// active = 1 at pose T. partials: n_rows x 29, n_rows >= the level's nblk; rows past nblk come back as 0xAB bytes.
+int dm_dense_eval(const DenseLevel* L, int cap, const float* T, int robust, float huber_delta, float scale_sqr, int plain_div, int n_rows,
+                  double* partials) {
+  Pool P;
+  DenseLevel D;
+  if (!dense_device_level(P, *L, cap, &D) || D.nblk > n_rows) return (int)hipErrorInvalidValue;
+  const int one = 1;
+  const LmState* st = dense_device_states(P, 1, T, &one);
+  const float* dscale = P.up(&scale_sqr, 1);
+  double* dp = dense_device_partials(P, n_rows);
+  if (plain_div) DM_LAUNCH(P, (lm_dense_eval_kernel<kDenseBlock, 1, kDenseWaves>), D.nblk, kDenseBlock, D, st, kDmExpectLevel, robust, huber_delta, dscale, dp);
+  else DM_LAUNCH(P, (lm_dense_eval_kernel<kDenseBlock, 0, kDenseWaves>), D.nblk, kDenseBlock, D, st, kDmExpectLevel, robust, huber_delta, dscale, dp);
+  P.down(partials, dp, ODO_NACC * (size_t)n_rows);
+  return P.done();
+}
+// lm_dense_eval_batch_kernel over n items of different sizes, launched as launch_dense_eval_batch launches it: grid = (largest nblk
+// rounded up to a multiple of 8, n). Item i: level Ls[i] with cap caps[i], pose T + 16 i, state active[i]; its partial rows are
+// partials + 29 row_off[i] .. 29 row_off[i + 1] (row_off[i + 1] - row_off[i] >= its nblk).
+int dm_dense_eval_batch(int n, const DenseLevel* Ls, const int* caps, const float* T, const int* robust, const float* huber_delta,
+                        const float* scale_sqr, const int* active, int plain_div, const int* row_off, double* partials) {
+  if (n < 1 || n > 64) return (int)hipErrorInvalidValue;
+  Pool P;
+  std::vector<DenseBatchItem> items((size_t)n);
+  std::vector<double*> dps((size_t)n);
+  LmState* st = dense_device_states(P, n, T, active);
+  const float* dscale = P.up(scale_sqr, n);
+  int max_nblk = 1;
+  for (int i = 0; i < n; i++) {
+    DenseBatchItem& it = items[i];
+    memset(&it, 0, sizeof(it));
+    const int rows = row_off[i + 1] - row_off[i];
+    if (!dense_device_level(P, Ls[i], caps[i], &it.L) || it.L.nblk > rows) return (int)hipErrorInvalidValue;
+    dps[i] = dense_device_partials(P, rows);
+    it.st = st + i; it.scale_sqr = dscale + i; it.partials = dps[i];
+    it.expect_level = kDmExpectLevel; it.robust = robust[i]; it.huber_delta = huber_delta[i];
+    if (it.L.nblk > max_nblk) max_nblk = it.L.nblk;
+  }
+  const DenseBatchItem* dit = P.up(items.data(), (size_t)n);
+  const dim3 grid((unsigned)((max_nblk + 7) / 8 * 8), (unsigned)n);
+  if (plain_div) DM_LAUNCH(P, (lm_dense_eval_batch_kernel<kDenseBlock, 1, kDenseWaves>), grid, kDenseBlock, dit);
+  else DM_LAUNCH(P, (lm_dense_eval_batch_kernel<kDenseBlock, 0, kDenseWaves>), grid, kDenseBlock, dit);
+  for (int i = 0; i < n; i++) P.down(partials + ODO_NACC * (size_t)row_off[i], dps[i], ODO_NACC * (size_t)(row_off[i + 1] - row_off[i]));
+  return P.done();
+}
+
+// ---- the t-distribution scale over stored residuals ----
+// order 0: lm_tdist_scale_kernel in list order (n <= 64 kTdistChunksMax); 1: the same kernel's strided order; 2: what lm_launch_scale
+// queues for n residuals (tdist_scale_plan: the list order, or the multi-workgroup kernel with the single-workgroup kernel behind it
+// on only_if, or the single-workgroup kernel alone when n does not fit), `reps` times in a row on ONE exchange buffer with the
+// launch epoch counting up as the library's does. The multi-workgroup kernel's waits are bounded (its default: 4 ms), and its test
+// hook stays off. scale_sqr[reps]; info[4 reps] = {G (0: no multi launch), gave up, writer (0 list order, 1 strided, 2 multi), 0}.
+int dm_tdist_scale(const float* res, int n, int order, int reps, float* scale_sqr, int* info) {
+  if (n < 0 || reps < 1 || reps > 16 || order < 0 || order > 2 || (order == 0 && n > 64 * kTdistChunksMax)) return (int)hipErrorInvalidValue;
+  Pool P;
+  const float* dres = P.up(res, (size_t)n);
+  const int one = 1;
+  float eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  const LmState* st = dense_device_states(P, 1, eye, &one);
+  float* dscale = (float*)P.raw(sizeof(float));
+  unsigned long long* xbuf = P.zeros<unsigned long long>(kTsXbufWords);
+  int* gave_up = P.zeros<int>(2);   // {flag, passes redone by the fall-back}
+  const TdistScalePlan plan = tdist_scale_plan(n);
+  unsigned epoch = 0;
+  for (int r = 0; r < reps; r++) {
+    int* o = info + 4 * r;
+    o[0] = o[1] = o[2] = o[3] = 0;
+    if (dscale && P.err == hipSuccess) P.err = hipMemset(dscale, 0xff, sizeof(float));   // (a NaN: a launch that writes nothing shows)
+    if (order != 2 || plan.list) {
+      const int list_order = (order == 1) ? 0 : 1;
+      DM_LAUNCH(P, lm_tdist_scale_kernel<0>, 1, 1024, dres, n, st, kDmExpectLevel, dscale, list_order, (int*)nullptr);
+      o[2] = list_order ? 0 : 1;
+    } else if (!plan.fits) {
+      DM_LAUNCH(P, lm_tdist_scale_kernel<0>, 1, 1024, dres, n, st, kDmExpectLevel, dscale, plan.single_order, (int*)nullptr);
+      o[2] = plan.single_order ? 0 : 1;
+    } else if (P.err == hipSuccess) {
+      epoch++;
+      int before[2] = {0, 0}, after[2] = {0, 0};
+      P.down(before, gave_up, 2);
+      hipLaunchKernelGGL(lm_tdist_scale_multi_kernel<0>, dim3((unsigned)plan.G), dim3(kTsThreads), 0, nullptr, dres, n, st, kDmExpectLevel,
+                         dscale, xbuf, epoch, 0u, gave_up, 0);
+      hipLaunchKernelGGL(lm_tdist_scale_kernel<0>, dim3(1), dim3(1024), 0, nullptr, dres, n, st, kDmExpectLevel, dscale, plan.single_order,
+                         gave_up);
+      P.ran();
+      P.down(after, gave_up, 2);
+      o[0] = plan.G;
+      o[1] = (after[1] != before[1]) ? 1 : 0;
+      o[2] = o[1] ? (plan.single_order ? 0 : 1) : 2;
+    }
+    P.down(scale_sqr + r, dscale, 1);
+  }
   return P.done();
 }
 

@@ -147,6 +147,16 @@ def test_dense_1080p_accumulators_match_oracle(api, O, scene, level):
     assert st == 0 and ref["status"] == 0
     assert acc[28] == ref["acc"][28] > 0
     np.testing.assert_allclose(acc, ref["acc"], rtol=1e-11, atol=1e-6)
+    if level == 0:
+        # t-distribution weights on the 2 M residuals of level 0: the only accumulator test whose scale runs on 128 workgroups
+        # (lm_tdist_scale_multi_kernel); sigma enters every weight, so the sums hold it to the oracle's far below one ulp
+        lm2 = api.LevenbergMarquardtOptimizer(0.01, 0.995, [10, 20, 30, 30], np.eye(4), None, 2, 28.0, intrinsics=K)
+        st2, acc2 = lm2.accumulate(p0, d0, p1, level, T)
+        ref2 = O.lm_accumulate(i0, i1, dd, level, T, robust=2, huber_delta=28.0, K=KD)
+        assert st2 == 0 and ref2["status"] == 0
+        assert acc2[28] == ref2["acc"][28] == acc[28]
+        assert lm2.tdist_stats()[0] == 1
+        np.testing.assert_allclose(acc2, ref2["acc"], rtol=1e-11, atol=1e-6)
 
 
 def test_shared_reciprocal_divisions_equal_plain_divisions(api, scene):
