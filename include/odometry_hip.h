@@ -810,6 +810,68 @@ int odo_volume_icp_align_dev(odo_volume* v, const odo_icp_params* p, const float
 int odo_volume_track_dev(odo_volume* v, const odo_icp_params* p, const uint16_t* raw_dev, const float prev_pose_colmajor[16],
                          float abs_pose_colmajor[16], odo_icp_result* result);
 
+/* ---- Frame-to-model tracking with a photometric term: the model's colour frame observes what its geometry cannot ------------------
+ * Beside each geometric row above, a row that compares the sensor's grey value with the grey of the ray-cast's colour frame at the
+ * pixel's projection, in the same normal equations (DESIGN.md section 9.10 holds the same table). Inputs beyond those above: grey,
+ * rows x cols float32, the sensor's grey frame (what the RGB-D path tracks on); rgba_m, rows x cols uint8[4], the ray-cast's colour
+ * frame from P_m; weight (lambda > 0, metres per grey level) and huber_delta (grey levels, >= 0). fp32, one rounding per operation.
+ * Per sensor pixel (x, y) on the stride:
+ *   1. Steps 1 .. 3 above unchanged (r, D, p, pm, pm_z > 0), then u, v as in step 4. A pixel skipped here has neither row.
+ *   2. x0 = floorf(u), y0 = floorf(v); skipped unless x0 >= 0 && x0 < cols - 1 && y0 >= 0 && y0 < rows - 1, compared as floats.
+ *   3. xi = floorf(u + 0.5f), yi = floorf(v + 0.5f) (in range by 2); zm = depth_m[yi cols + xi]; skipped unless zm > 0 and
+ *      fabsf(pm_z - zm) <= dist_max (equality keeps the pair): the nearest model pixel is the occlusion gate.
+ *   4. The four words of rgba_m at (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1): g00, g01, g10, g11. Skipped unless all
+ *      four have A != 0. g = (float)((R 4899 + G 9617 + B 1868 + 8192) >> 14) in integers, the front end's rule.
+ *   5. ax = u - x0, ay = v - y0; dt = g01 - g00, db = g11 - g10; top = g00 + ax dt, bot = g10 + ax db;
+ *      val = top + ay (bot - top); gx = dt + ay (db - dt); gy = bot - top.
+ *   6. res = lambda (val - grey[y cols + x]); a = (lambda f) / pm_z; jx = a gx, jy = a gy, jz = -((jx pm_x + jy pm_y) / pm_z);
+ *      J = (jx, jy, jz, pm_y jz - pm_z jy, pm_z jx - pm_x jz, pm_x jy - pm_y jx);
+ *      w = (|res| <= lambda huber_delta ? 1 : lambda huber_delta / |res|) if huber_delta > 0, else 1. A flat patch (gx = gy = 0)
+ *      is still a pair: it adds cost and count only.
+ * The geometric row of the pixel is the one above, unchanged; a pixel can have both rows, either, or none.
+ * Sums: 31 doubles. 0 .. 27 are the 28 sums above over geometric and photometric rows together (exact fp64 products), 28 the
+ * geometric pairs, 29 the photometric pairs, 30 the photometric rows' share of sum 27. The step, min_pairs (geometric pairs: texture
+ * without a model surface is not an alignment), the eigenvalues and min_eig_ratio are those above on the first 29. The order of the
+ * sums is fixed (volume_icp_photo.hip.h), no atomics: two calls on the same inputs give the same bits. */
+typedef struct {
+  float weight;                /* lambda, metres per grey level: finite > 0 */
+  float huber_delta;           /* grey levels, finite >= 0; 0: no robust weight on the photometric rows */
+} odo_icp_photo_params;
+typedef struct {
+  odo_icp_result icp;          /* as above; pairs counts geometric pairs, cost both kinds of row */
+  double photo_pairs, photo_cost;   /* of the last evaluation: the photometric pairs and their share of cost */
+} odo_icp_photo_result;
+typedef struct {               /* one step of an alignment */
+  int level, iteration;
+  double acc[31];
+  float delta[6];
+  float C[16];
+} odo_icp_photo_trace_row;
+/* One evaluation at C for one stride: acc receives the 31 sums; rows_dev (device, 16-byte aligned, may be NULL) receives float[16]
+ * per pixel of the frame, {J_0 .. J_5, res, w} of the geometric row and then of the photometric row, zeros for a missing row and for
+ * pixels off the stride. grey_dev and rgba_m_dev are 4-byte aligned. Validated, ordered and legal as odo_volume_icp_eval_dev. */
+int odo_volume_icp_photo_eval_dev(odo_volume* v, const float* depth_m_dev, const float* nrmw_m_dev, const uint8_t* rgba_m_dev,
+                                  const float model_pose_colmajor[16], const uint16_t* raw_dev, const float* grey_dev,
+                                  const float C_colmajor[16], int stride, float dist_max, float huber_delta,
+                                  const odo_icp_photo_params* photo, double acc[31], float* rows_dev);
+/* Event timing of the two kernels of this path, as odo_volume_icp_time_dev. */
+int odo_volume_icp_photo_time_dev(odo_volume* v, const float* depth_m_dev, const float* nrmw_m_dev, const uint8_t* rgba_m_dev,
+                                  const float model_pose_colmajor[16], const uint16_t* raw_dev, const float* grey_dev,
+                                  const float C_colmajor[16], int stride, float dist_max, float huber_delta,
+                                  const odo_icp_photo_params* photo, int reps, float us[2]);
+/* The alignment, as odo_volume_icp_align_dev with the photometric rows: launches, single wait, status, NaNs and validation alike. */
+int odo_volume_icp_photo_align_dev(odo_volume* v, const odo_icp_params* p, const odo_icp_photo_params* photo, const float* depth_m_dev,
+                                   const float* nrmw_m_dev, const uint8_t* rgba_m_dev, const float model_pose_colmajor[16],
+                                   const uint16_t* raw_dev, const float* grey_dev, const float init_pose_colmajor[16],
+                                   float abs_pose_colmajor[16], odo_icp_photo_result* result, odo_icp_photo_trace_row* trace,
+                                   int trace_capacity, int* trace_n);
+/* Frame-to-model tracking of one depth and grey frame: odo_volume_track_dev's ray-cast with the colour frame as well, into frames that
+ * the volume owns, then odo_volume_icp_photo_align_dev with model_pose = init_pose = prev_pose. Refused on a volume without a colour
+ * grid. It does not integrate. */
+int odo_volume_track_photo_dev(odo_volume* v, const odo_icp_params* p, const odo_icp_photo_params* photo, const uint16_t* raw_dev,
+                               const float* grey_dev, const float prev_pose_colmajor[16], float abs_pose_colmajor[16],
+                               odo_icp_photo_result* result);
+
 /* ---- The moving volume: the grid follows the camera, and what leaves it is kept ------------------------------------------------------
  * Optional. A volume that is never shifted behaves and writes exactly as above, and allocates nothing more.
  * Window. The volume remembers origin0, the origin given to odo_volume_create, and off, the cumulative shift in whole voxels (0 at

@@ -78,6 +78,22 @@ class IcpTraceRow(C.Structure):
                 ("C", C.c_float * 16)]
 
 
+NACC_PHOTO = 31
+
+
+class IcpPhotoParams(C.Structure):
+    _fields_ = [("weight", C.c_float), ("huber_delta", C.c_float)]
+
+
+class IcpPhotoResult(C.Structure):
+    _fields_ = [("icp", IcpResult), ("photo_pairs", C.c_double), ("photo_cost", C.c_double)]
+
+
+class IcpPhotoTraceRow(C.Structure):
+    _fields_ = [("level", C.c_int), ("iteration", C.c_int), ("acc", C.c_double * NACC_PHOTO), ("delta", C.c_float * 6),
+                ("C", C.c_float * 16)]
+
+
 _fp = C.POINTER(C.c_float)
 _dp = C.POINTER(C.c_double)
 _u8p = C.POINTER(C.c_uint8)
@@ -265,6 +281,14 @@ SIGNATURES = {
     "odo_volume_icp_align_dev": (C.c_int, [_vp, C.POINTER(IcpParams), _vp, _vp, _fp, _vp, _fp, _fp, C.POINTER(IcpResult),
                                            C.POINTER(IcpTraceRow), C.c_int, _ip]),
     "odo_volume_track_dev": (C.c_int, [_vp, C.POINTER(IcpParams), _vp, _fp, _fp, C.POINTER(IcpResult)]),
+    "odo_volume_icp_photo_eval_dev": (C.c_int, [_vp, _vp, _vp, _vp, _fp, _vp, _vp, _fp, C.c_int, C.c_float, C.c_float,
+                                                C.POINTER(IcpPhotoParams), _dp, _vp]),
+    "odo_volume_icp_photo_time_dev": (C.c_int, [_vp, _vp, _vp, _vp, _fp, _vp, _vp, _fp, C.c_int, C.c_float, C.c_float,
+                                                C.POINTER(IcpPhotoParams), C.c_int, _fp]),
+    "odo_volume_icp_photo_align_dev": (C.c_int, [_vp, C.POINTER(IcpParams), C.POINTER(IcpPhotoParams), _vp, _vp, _vp, _fp, _vp, _vp, _fp,
+                                                 _fp, C.POINTER(IcpPhotoResult), C.POINTER(IcpPhotoTraceRow), C.c_int, _ip]),
+    "odo_volume_track_photo_dev": (C.c_int, [_vp, C.POINTER(IcpParams), C.POINTER(IcpPhotoParams), _vp, _vp, _fp, _fp,
+                                             C.POINTER(IcpPhotoResult)]),
     "odo_volume_shift": (C.c_int, [_vp, _ip]),
     "odo_volume_window": (C.c_int, [_vp, _ip, _fp]),
     "odo_volume_enable_spill": (C.c_int, [_vp, C.c_long]),

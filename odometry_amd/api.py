@@ -1099,6 +1099,11 @@ class TsdfVolume:
     # at 120 x 160: eig_min / eig_max is at most 6.5e-4 on the plain corridor, which cannot be tracked, and at
     # least 4.95e-3 on a narrow ribbed one, which can; their geometric mean 1.8e-3 separates the two by a factor 2.8 only.
     ICP_MIN_EIG_RATIO = 0.0
+    # Defaults of the photometric term (photo_params): of the grid weight {0.001, 0.003, 0.01, 0.03} x huber_delta {0, 4, 12, 36} the
+    # pair with the smallest sum of the two pinned cases' worst translation errors, measured with the fp32 model at 120 x 160
+    # (DESIGN.md section 9.10 holds the whole grid; tests/test_volume_icp_photo_cpu.py holds these constants to the rule).
+    ICP_PHOTO_WEIGHT = 0.01
+    ICP_PHOTO_HUBER = 4.0
 
     def icp_params(self, strides=(4, 2, 1), iters=(4, 5, 10), dist_max=None, huber_delta=0.0, eps_t=1e-5, eps_r=1e-5, min_pairs=None,
                    min_eig_ratio=None):
@@ -1117,6 +1122,12 @@ class TsdfVolume:
         p.min_pairs = max(6, lattice // 64) if min_pairs is None else int(min_pairs)
         p.min_eig_ratio = self.ICP_MIN_EIG_RATIO if min_eig_ratio is None else min_eig_ratio
         return p
+
+    def photo_params(self, weight=None, huber_delta=None):
+        """The odo_icp_photo_params of the photometric term: weight in metres per grey level, huber_delta in grey levels (0: no
+        robust weight); the measured defaults unless given."""
+        return L.IcpPhotoParams(self.ICP_PHOTO_WEIGHT if weight is None else weight,
+                                self.ICP_PHOTO_HUBER if huber_delta is None else huber_delta)
 
     def _frames_dev(self, frames):
         """Device handles of frames given as numpy arrays (uploaded; the second list names the temporaries) or as handles."""
@@ -1146,16 +1157,34 @@ class TsdfVolume:
         size = (self.rows, self.cols)
         return self._frames_dev([(depth, np.uint16, size), (model_depth, np.float32, size), (model_nrmw, np.float32, size + (4,))])
 
+    def _photo_frames(self, depth, grey, model_depth, model_nrmw, model_rgba):
+        if grey is None or model_rgba is None:
+            raise ValueError("the photometric term needs both grey (the sensor's grey frame) and model_rgba (the ray-cast's colours)")
+        size = (self.rows, self.cols)
+        return self._frames_dev([(depth, np.uint16, size), (grey, np.float32, size), (model_depth, np.float32, size),
+                                 (model_nrmw, np.float32, size + (4,)), (model_rgba, np.uint8, size + (4,))])
+
+    @staticmethod
+    def _icp_photo_result(r):
+        out = TsdfVolume._icp_result(r.icp)
+        out.update(photo_pairs=r.photo_pairs, photo_cost=r.photo_cost)
+        return out
+
     @staticmethod
     def _icp_result(r):
         return dict(status=r.status, iterations=r.iterations, pairs=r.pairs, cost=r.cost, eig_min=r.eig_min, eig_max=r.eig_max,
                     C=_from_colmajor(list(r.C)))
 
     def icp_eval(self, depth, model_depth, model_nrmw, model_pose, C_sensor_to_model, stride=1, dist_max=None, huber_delta=0.0,
-                 rows=False):
+                 rows=False, grey=None, model_rgba=None, photo=None):
         """One evaluation of the alignment's rows at the 4x4 transform C_sensor_to_model: the 29 sums (float64), with rows=True also
         (rows, cols, 8) float32 {J0 .. J5, res, w} per pixel. depth: the sensor's uint16 frame; model_depth / model_nrmw: a ray-cast
-        from model_pose at the volume's size and K; each a numpy array or a device handle."""
+        from model_pose at the volume's size and K; each a numpy array or a device handle. With grey (the sensor's float32 grey
+        frame) and model_rgba (the ray-cast's colours) the photometric rows are evaluated as well: 31 sums, and (rows, cols, 16) rows,
+        the geometric eight and then the photometric eight; photo: photo_params()."""
+        if grey is not None or model_rgba is not None:
+            return self._icp_photo_eval(depth, grey, model_depth, model_nrmw, model_rgba, model_pose, C_sensor_to_model, stride, dist_max,
+                                        huber_delta, rows, photo)
         (raw_d, dep_d, nrm_d), temps = self._model_frames(depth, model_depth, model_nrmw)
         acc = np.zeros(L.NACC, np.float64)
         out = None
@@ -1177,6 +1206,46 @@ class TsdfVolume:
         finally:
             self._free_dev(temps)
 
+    def _icp_photo_eval(self, depth, grey, model_depth, model_nrmw, model_rgba, model_pose, Cm, stride, dist_max, huber_delta, rows, photo):
+        (raw_d, grey_d, dep_d, nrm_d, rgba_d), temps = self._photo_frames(depth, grey, model_depth, model_nrmw, model_rgba)
+        ph = self.photo_params() if photo is None else photo
+        acc = np.zeros(L.NACC_PHOTO, np.float64)
+        out = None
+        nbytes = self.rows * self.cols * 64
+        try:
+            if rows:
+                out = C.c_void_p()
+                L.check(self.lib.odo_dev_alloc(self._ctx, nbytes, C.byref(out)), "odo_dev_alloc")
+                temps.append(out)
+                L.check(self.lib.odo_dev_upload(self._ctx, out, np.full(nbytes, 0xAB, np.uint8).ctypes.data_as(C.c_void_p), nbytes),
+                        "odo_dev_upload")
+            L.check(self.lib.odo_volume_icp_photo_eval_dev(self.h, dep_d, nrm_d, rgba_d, _fp(_colmajor(model_pose)), raw_d, grey_d,
+                                                           _fp(_colmajor(Cm)), int(stride),
+                                                           2 * self.params.mu if dist_max is None else dist_max, huber_delta, C.byref(ph),
+                                                           acc.ctypes.data_as(L._dp), out), "odo_volume_icp_photo_eval_dev")
+            if rows:
+                got = np.empty((self.rows, self.cols, 16), np.float32)
+                L.check(self.lib.odo_dev_download(self._ctx, got.ctypes.data_as(C.c_void_p), out, got.nbytes), "odo_dev_download")
+                return acc, got
+            return acc
+        finally:
+            self._free_dev(temps)
+
+    def icp_photo_time(self, depth, grey, model_depth, model_nrmw, model_rgba, model_pose, C_sensor_to_model, stride=1, dist_max=None,
+                       huber_delta=0.0, photo=None, reps=50):
+        """Event timing of the two kernels of the alignment with the photometric term: (rows, step) microseconds per launch."""
+        (raw_d, grey_d, dep_d, nrm_d, rgba_d), temps = self._photo_frames(depth, grey, model_depth, model_nrmw, model_rgba)
+        ph = self.photo_params() if photo is None else photo
+        us = np.zeros(2, np.float32)
+        try:
+            L.check(self.lib.odo_volume_icp_photo_time_dev(self.h, dep_d, nrm_d, rgba_d, _fp(_colmajor(model_pose)), raw_d, grey_d,
+                                                           _fp(_colmajor(C_sensor_to_model)), int(stride),
+                                                           2 * self.params.mu if dist_max is None else dist_max, huber_delta, C.byref(ph),
+                                                           int(reps), _fp(us)), "odo_volume_icp_photo_time_dev")
+        finally:
+            self._free_dev(temps)
+        return float(us[0]), float(us[1])
+
     def icp_time(self, depth, model_depth, model_nrmw, model_pose, C_sensor_to_model, stride=1, dist_max=None, huber_delta=0.0, reps=50):
         """Event timing of the alignment's two kernels: (rows, step) microseconds per launch, means over reps launches each."""
         (raw_d, dep_d, nrm_d), temps = self._model_frames(depth, model_depth, model_nrmw)
@@ -1189,11 +1258,16 @@ class TsdfVolume:
             self._free_dev(temps)
         return float(us[0]), float(us[1])
 
-    def align(self, depth, model_depth, model_nrmw, model_pose, init_pose, trace=False, params=None):
+    def align(self, depth, model_depth, model_nrmw, model_pose, init_pose, trace=False, params=None, grey=None, model_rgba=None,
+              photo=None):
         """Aligns the sensor's depth frame to a model frame (a ray-cast from model_pose at the volume's size and K) from the first
         guess init_pose: (abs_pose 4x4 float32 — NaNs unless status is 0 —, result dict: status, iterations, pairs, cost, eig_min,
-        eig_max, C), with trace=True also the steps as a list of dicts (level, iteration, acc, delta, C)."""
+        eig_max, C), with trace=True also the steps as a list of dicts (level, iteration, acc, delta, C). With grey and model_rgba
+        the photometric rows join the geometric ones (photo: photo_params()); the result gains photo_pairs and photo_cost and a
+        trace entry's acc has 31 sums."""
         p = self.icp_params() if params is None else params
+        if grey is not None or model_rgba is not None:
+            return self._photo_align(depth, grey, model_depth, model_nrmw, model_rgba, model_pose, init_pose, trace, p, photo)
         (raw_d, dep_d, nrm_d), temps = self._model_frames(depth, model_depth, model_nrmw)
         cap = sum(p.iters[:p.levels]) if trace else 0
         rows = (L.IcpTraceRow * max(cap, 1))()
@@ -1212,11 +1286,63 @@ class TsdfVolume:
                           C=_from_colmajor(list(r.C))) for r in rows[:n.value]],)
         return out
 
-    def track(self, depth, prev_pose, integrate=False, params=None):
+    def _photo_align(self, depth, grey, model_depth, model_nrmw, model_rgba, model_pose, init_pose, trace, p, photo):
+        (raw_d, grey_d, dep_d, nrm_d, rgba_d), temps = self._photo_frames(depth, grey, model_depth, model_nrmw, model_rgba)
+        ph = self.photo_params() if photo is None else photo
+        cap = sum(p.iters[:p.levels]) if trace else 0
+        rows = (L.IcpPhotoTraceRow * max(cap, 1))()
+        n = C.c_int(0)
+        res = L.IcpPhotoResult()
+        pose = np.zeros(16, np.float32)
+        try:
+            L.check(self.lib.odo_volume_icp_photo_align_dev(self.h, C.byref(p), C.byref(ph), dep_d, nrm_d, rgba_d, _fp(_colmajor(model_pose)),
+                                                            raw_d, grey_d, _fp(_colmajor(init_pose)), _fp(pose), C.byref(res),
+                                                            rows if trace else None, cap, C.byref(n)), "odo_volume_icp_photo_align_dev")
+        finally:
+            self._free_dev(temps)
+        out = (_from_colmajor(pose), self._icp_photo_result(res))
+        if trace:
+            out += ([dict(level=r.level, iteration=r.iteration, acc=np.array(r.acc, np.float64), delta=np.array(r.delta, np.float32),
+                          C=_from_colmajor(list(r.C))) for r in rows[:n.value]],)
+        return out
+
+    def _photo_track(self, depth, grey, prev_pose, integrate, p, colour, photo):
+        size = (self.rows, self.cols)
+        frames = [(depth, np.uint16, size), (grey, np.float32, size)]
+        if colour is not None:
+            if not self.has_colour:
+                raise L.OdoError("TsdfVolume.track: the volume has no colour grid (enable_colour first)")
+            frames.append((colour, np.uint8, size + (self.colour_params.channels,)))
+        handles, temps = self._frames_dev(frames)
+        ph = self.photo_params() if photo is None else photo
+        res = L.IcpPhotoResult()
+        pose = np.zeros(16, np.float32)
+        try:
+            L.check(self.lib.odo_volume_track_photo_dev(self.h, C.byref(p), C.byref(ph), handles[0], handles[1], _fp(_colmajor(prev_pose)),
+                                                        _fp(pose), C.byref(res)), "odo_volume_track_photo_dev")
+            if integrate and res.icp.status == 0:
+                if self._follow is not None:   # the window moves for this pose before the frame is fused
+                    L.check(self.lib.odo_volume_follow(self.h, _fp(pose), None), "odo_volume_follow")
+                if colour is not None:
+                    L.check(self.lib.odo_volume_integrate_colour_dev(self.h, handles[0], handles[2], _fp(pose)),
+                            "odo_volume_integrate_colour_dev")
+                else:
+                    L.check(self.lib.odo_volume_integrate_dev(self.h, handles[0], _fp(pose)), "odo_volume_integrate_dev")
+        finally:   # odo_dev_free waits for the context's stream: the integration has read the frames
+            self._free_dev(temps)
+        return _from_colmajor(pose), self._icp_photo_result(res)
+
+    def track(self, depth, prev_pose, integrate=False, params=None, grey=None, colour=None, photo=None):
         """Frame-to-model tracking of one depth frame (a uint16 numpy array or a device handle): the volume is ray-cast from prev_pose
         and the frame aligned to that from prev_pose. Returns (abs_pose, result dict) as align(). integrate=True fuses the frame at
-        the returned pose when status is 0, behind the follow step for that pose when set_follow is on."""
+        the returned pose when status is 0, behind the follow step for that pose when set_follow is on. With grey (the frame's
+        float32 grey image; a volume with colour) the ray-cast includes the colours and the alignment the photometric rows (photo:
+        photo_params()); integrate=True with colour (the frame's uint8 colour pixels) then fuses the coloured frame."""
         p = self.icp_params() if params is None else params
+        if grey is not None:
+            return self._photo_track(depth, grey, prev_pose, integrate, p, colour, photo)
+        if colour is not None or photo is not None:
+            raise ValueError("TsdfVolume.track: colour and photo belong to the photometric path (give grey)")
         (raw_d,), temps = self._frames_dev([(depth, np.uint16, (self.rows, self.cols))])
         res = L.IcpResult()
         pose = np.zeros(16, np.float32)

@@ -37,7 +37,10 @@
             the pinned grid after `frames` integrations at their true poses, the ray-cast from the last pose but one as the model
             frame, the last frame as the sensor frame, at 480 x 640 and strides 4, 2 and 1. One JSON line per stride with the medians
             over `runs` batches, the pairs and the blocks, then the wall time of whole api.TsdfVolume.track calls (ray-cast, the
-            alignment's launches, its allocations and its one wait).
+            alignment's launches, its allocations and its one wait). With --photo the volume has a colour grid (every frame fused
+            with its grey replicated into R, G and B), the ray-cast includes the colours, and each line carries the two kernels of
+            the alignment with the photometric term (api.TsdfVolume.icp_photo_time) beside the geometric two, timed in alternating
+            batches of the same call; the last line gives the wall time of track(grey=...) beside the geometric track's.
 
   shift     the moving volume's launches timed with events (api.TsdfVolume.shift_time: batches of `reps` between two events on the
             volume's stream, the shift not applied): the pinned and the large grid after `frames` integrations at their true poses,
@@ -47,7 +50,7 @@
             with the bytes moved and the points that shift spills.
 
   python tools/volume_cost.py kernels [--frames 10] [--extractions 3] [--json FILE]
-  python tools/volume_cost.py icp [--frames 10] [--runs 7] [--reps 50]
+  python tools/volume_cost.py icp [--frames 10] [--runs 7] [--reps 50] [--photo]
   python tools/volume_cost.py shift [--frames 10] [--runs 7] [--reps 20]
   python tools/volume_cost.py summary DIR [--json FILE]
   python tools/volume_cost.py track [--runs 3] [--steps 200] [--warmup 20] [--frames 100] [--modes none,pinned,large[,coloured][,follow]]
@@ -277,6 +280,47 @@ def icp(args):
     ctx.close()
 
 
+def _med(a):
+    return dict(median=round(float(np.median(a)), 2), min_max=[round(float(np.min(a)), 2), round(float(np.max(a)), 2)])
+
+
+def icp_photo(args):
+    """`icp --photo`: the geometric and the photometric kernels in alternating batches on one coloured volume."""
+    from odometry_amd import api, synth
+    seq = synth.make_rgbd_sequence(args.frames, seed=0)
+    K = (seq["K"]["f0"], seq["K"]["cx0"], seq["K"]["cy0"])
+    ctx = api.Context(0)
+    vol = make_volume(ctx, "pinned", (synth.TUM_ROWS, synth.TUM_COLS), K, colour=True)
+    for d, g, A in zip(seq["depth"][:-1], seq["gray"][:-1], seq["poses"][:-1]):
+        vol.integrate(d, A, colour=synth.colour_from_gray(g))
+    P_m = seq["poses"][-2]
+    depth, nrmw, rgba = vol.raycast(P_m, colour=True)
+    raw, grey = seq["depth"][-1], seq["gray"][-1]
+    for stride in (4, 2, 1):
+        acc = vol.icp_eval(raw, depth, nrmw, P_m, np.eye(4), stride=stride, grey=grey, model_rgba=rgba)
+        geo, photo = [], []
+        for _ in range(args.runs):
+            geo.append(vol.icp_time(raw, depth, nrmw, P_m, np.eye(4), stride=stride, reps=args.reps))
+            photo.append(vol.icp_photo_time(raw, grey, depth, nrmw, rgba, P_m, np.eye(4), stride=stride, reps=args.reps))
+        geo, photo = np.array(geo), np.array(photo)
+        lx, ly = -(-synth.TUM_COLS // stride), -(-synth.TUM_ROWS // stride)
+        print(json.dumps(dict(stride=stride, lattice=lx * ly, pairs=int(acc[28]), photo_pairs=int(acc[29]), blocks=(-(-lx // 16)) * (-(-ly // 16)),
+                              rows_us=_med(geo[:, 0]), photo_rows_us=_med(photo[:, 0]), step_fold_us=_med(geo[:, 1]),
+                              photo_step_fold_us=_med(photo[:, 1]))), flush=True)
+    wall = dict(geo=[], photo=[])
+    for _ in range(args.runs):
+        t0 = time.perf_counter()
+        _, g_res = vol.track(raw, P_m)
+        t1 = time.perf_counter()
+        _, p_res = vol.track(raw, P_m, grey=grey)
+        wall["geo"].append(1e3 * (t1 - t0))
+        wall["photo"].append(1e3 * (time.perf_counter() - t1))
+    print(json.dumps(dict(track_call_ms=_med(wall["geo"]), track_photo_call_ms=_med(wall["photo"]), status=[g_res["status"], p_res["status"]],
+                          iterations=[g_res["iterations"], p_res["iterations"]], pairs=p_res["pairs"], photo_pairs=p_res["photo_pairs"])), flush=True)
+    vol.close()
+    ctx.close()
+
+
 def shift(args):
     from odometry_amd import api, synth
     seq = synth.make_rgbd_sequence(args.frames, seed=0)
@@ -328,11 +372,14 @@ def main():
     i.add_argument("--frames", type=int, default=10)
     i.add_argument("--runs", type=int, default=7)
     i.add_argument("--reps", type=int, default=50)
+    i.add_argument("--photo", action="store_true")
     h = sub.add_parser("shift")
     h.add_argument("--frames", type=int, default=10)
     h.add_argument("--runs", type=int, default=7)
     h.add_argument("--reps", type=int, default=20)
     args = ap.parse_args()
+    if args.cmd == "icp" and args.photo:
+        return icp_photo(args)
     dict(kernels=kernels, summary=summary, track=track, icp=icp, shift=shift)[args.cmd](args)
 
 
