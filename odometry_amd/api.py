@@ -1153,27 +1153,46 @@ class TsdfVolume:
         for p in temps:
             self.lib.odo_dev_free(self._ctx, p)
 
-    def _model_frames(self, depth, model_depth, model_nrmw):
-        size = (self.rows, self.cols)
-        return self._frames_dev([(depth, np.uint16, size), (model_depth, np.float32, size), (model_nrmw, np.float32, size + (4,))])
+    class _IcpPath:
+        """What the two paths of frame-to-model tracking differ in, for icp_eval, the timings, align and track: the geometric path, or
+        with photometric=True the one with the photometric term. It knows the frames to upload, the entry point (odo_volume_icp_* /
+        odo_volume_icp_photo_*, whose arguments are the geometric ones with the extra frames behind the model's and the sensor's and
+        the photometric parameters where `ph` is spliced in) and the shape of the result."""
 
-    def _photo_frames(self, depth, grey, model_depth, model_nrmw, model_rgba):
-        if grey is None or model_rgba is None:
-            raise ValueError("the photometric term needs both grey (the sensor's grey frame) and model_rgba (the ray-cast's colours)")
-        size = (self.rows, self.cols)
-        return self._frames_dev([(depth, np.uint16, size), (grey, np.float32, size), (model_depth, np.float32, size),
-                                 (model_nrmw, np.float32, size + (4,)), (model_rgba, np.uint8, size + (4,))])
+        def __init__(self, vol, photometric, photo=None):
+            self.vol, self.photometric = vol, photometric
+            self.nacc, self.row_floats = (L.NACC_PHOTO, 16) if photometric else (L.NACC, 8)
+            self.Result, self.TraceRow = (L.IcpPhotoResult, L.IcpPhotoTraceRow) if photometric else (L.IcpResult, L.IcpTraceRow)
+            self.ph = [C.byref(vol.photo_params() if photo is None else photo)] if photometric else []
 
-    @staticmethod
-    def _icp_photo_result(r):
-        out = TsdfVolume._icp_result(r.icp)
-        out.update(photo_pairs=r.photo_pairs, photo_cost=r.photo_cost)
-        return out
+        def frames(self, depth, grey, model=None, colour=None):
+            """Device handles of the sensor's frames ([raw] or [raw, grey]) and of the others (the model's [depth, nrmw] or [depth,
+            nrmw, rgba] of model = (depth, nrmw, rgba), then a colour frame to fuse), and the temporaries to free."""
+            size = (self.vol.rows, self.vol.cols)
+            if self.photometric and (grey is None or (model is not None and model[2] is None)):
+                raise ValueError("the photometric term needs both grey (the sensor's grey frame) and model_rgba (the ray-cast's colours)")
+            frames = [(depth, np.uint16, size)] + ([(grey, np.float32, size)] if self.photometric else [])
+            n = len(frames)
+            if model is not None:
+                frames += [(model[0], np.float32, size), (model[1], np.float32, size + (4,))]
+                frames += [(model[2], np.uint8, size + (4,))] if self.photometric else []
+            if colour is not None:
+                frames.append((colour, np.uint8, size + (self.vol.colour_params.channels,)))
+            handles, temps = self.vol._frames_dev(frames)
+            return handles[:n], handles[n:], temps
 
-    @staticmethod
-    def _icp_result(r):
-        return dict(status=r.status, iterations=r.iterations, pairs=r.pairs, cost=r.cost, eig_min=r.eig_min, eig_max=r.eig_max,
-                    C=_from_colmajor(list(r.C)))
+        def call(self, name, *args):
+            """The entry point `name`, its {} filled with "_photo" on the photometric path, on the volume."""
+            name = name.format("_photo" if self.photometric else "")
+            L.check(getattr(self.vol.lib, name)(self.vol.h, *args), name)
+
+        def result(self, r):
+            icp = r.icp if self.photometric else r
+            out = dict(status=icp.status, iterations=icp.iterations, pairs=icp.pairs, cost=icp.cost, eig_min=icp.eig_min,
+                       eig_max=icp.eig_max, C=_from_colmajor(list(icp.C)))
+            if self.photometric:
+                out.update(photo_pairs=r.photo_pairs, photo_cost=r.photo_cost)
+            return out
 
     def icp_eval(self, depth, model_depth, model_nrmw, model_pose, C_sensor_to_model, stride=1, dist_max=None, huber_delta=0.0,
                  rows=False, grey=None, model_rgba=None, photo=None):
@@ -1182,36 +1201,11 @@ class TsdfVolume:
         from model_pose at the volume's size and K; each a numpy array or a device handle. With grey (the sensor's float32 grey
         frame) and model_rgba (the ray-cast's colours) the photometric rows are evaluated as well: 31 sums, and (rows, cols, 16) rows,
         the geometric eight and then the photometric eight; photo: photo_params()."""
-        if grey is not None or model_rgba is not None:
-            return self._icp_photo_eval(depth, grey, model_depth, model_nrmw, model_rgba, model_pose, C_sensor_to_model, stride, dist_max,
-                                        huber_delta, rows, photo)
-        (raw_d, dep_d, nrm_d), temps = self._model_frames(depth, model_depth, model_nrmw)
-        acc = np.zeros(L.NACC, np.float64)
+        path = self._IcpPath(self, grey is not None or model_rgba is not None, photo)
+        sensor, model, temps = path.frames(depth, grey, (model_depth, model_nrmw, model_rgba))
+        acc = np.zeros(path.nacc, np.float64)
         out = None
-        try:
-            if rows:
-                out = C.c_void_p()
-                L.check(self.lib.odo_dev_alloc(self._ctx, self.rows * self.cols * 32, C.byref(out)), "odo_dev_alloc")
-                temps.append(out)
-                L.check(self.lib.odo_dev_upload(self._ctx, out, np.full(self.rows * self.cols * 32, 0xAB, np.uint8).ctypes.data_as(C.c_void_p),
-                                                self.rows * self.cols * 32), "odo_dev_upload")
-            L.check(self.lib.odo_volume_icp_eval_dev(self.h, dep_d, nrm_d, _fp(_colmajor(model_pose)), raw_d, _fp(_colmajor(C_sensor_to_model)),
-                                                     int(stride), 2 * self.params.mu if dist_max is None else dist_max, huber_delta,
-                                                     acc.ctypes.data_as(L._dp), out), "odo_volume_icp_eval_dev")
-            if rows:
-                got = np.empty((self.rows, self.cols, 8), np.float32)
-                L.check(self.lib.odo_dev_download(self._ctx, got.ctypes.data_as(C.c_void_p), out, got.nbytes), "odo_dev_download")
-                return acc, got
-            return acc
-        finally:
-            self._free_dev(temps)
-
-    def _icp_photo_eval(self, depth, grey, model_depth, model_nrmw, model_rgba, model_pose, Cm, stride, dist_max, huber_delta, rows, photo):
-        (raw_d, grey_d, dep_d, nrm_d, rgba_d), temps = self._photo_frames(depth, grey, model_depth, model_nrmw, model_rgba)
-        ph = self.photo_params() if photo is None else photo
-        acc = np.zeros(L.NACC_PHOTO, np.float64)
-        out = None
-        nbytes = self.rows * self.cols * 64
+        nbytes = self.rows * self.cols * path.row_floats * 4
         try:
             if rows:
                 out = C.c_void_p()
@@ -1219,44 +1213,36 @@ class TsdfVolume:
                 temps.append(out)
                 L.check(self.lib.odo_dev_upload(self._ctx, out, np.full(nbytes, 0xAB, np.uint8).ctypes.data_as(C.c_void_p), nbytes),
                         "odo_dev_upload")
-            L.check(self.lib.odo_volume_icp_photo_eval_dev(self.h, dep_d, nrm_d, rgba_d, _fp(_colmajor(model_pose)), raw_d, grey_d,
-                                                           _fp(_colmajor(Cm)), int(stride),
-                                                           2 * self.params.mu if dist_max is None else dist_max, huber_delta, C.byref(ph),
-                                                           acc.ctypes.data_as(L._dp), out), "odo_volume_icp_photo_eval_dev")
+            path.call("odo_volume_icp{}_eval_dev", *model, _fp(_colmajor(model_pose)), *sensor, _fp(_colmajor(C_sensor_to_model)), int(stride),
+                      2 * self.params.mu if dist_max is None else dist_max, huber_delta, *path.ph, acc.ctypes.data_as(L._dp), out)
             if rows:
-                got = np.empty((self.rows, self.cols, 16), np.float32)
+                got = np.empty((self.rows, self.cols, path.row_floats), np.float32)
                 L.check(self.lib.odo_dev_download(self._ctx, got.ctypes.data_as(C.c_void_p), out, got.nbytes), "odo_dev_download")
                 return acc, got
             return acc
         finally:
             self._free_dev(temps)
 
-    def icp_photo_time(self, depth, grey, model_depth, model_nrmw, model_rgba, model_pose, C_sensor_to_model, stride=1, dist_max=None,
-                       huber_delta=0.0, photo=None, reps=50):
-        """Event timing of the two kernels of the alignment with the photometric term: (rows, step) microseconds per launch."""
-        (raw_d, grey_d, dep_d, nrm_d, rgba_d), temps = self._photo_frames(depth, grey, model_depth, model_nrmw, model_rgba)
-        ph = self.photo_params() if photo is None else photo
+    def _icp_time(self, path, depth, grey, model, model_pose, Cm, stride, dist_max, huber_delta, reps):
+        sensor, model, temps = path.frames(depth, grey, model)
         us = np.zeros(2, np.float32)
         try:
-            L.check(self.lib.odo_volume_icp_photo_time_dev(self.h, dep_d, nrm_d, rgba_d, _fp(_colmajor(model_pose)), raw_d, grey_d,
-                                                           _fp(_colmajor(C_sensor_to_model)), int(stride),
-                                                           2 * self.params.mu if dist_max is None else dist_max, huber_delta, C.byref(ph),
-                                                           int(reps), _fp(us)), "odo_volume_icp_photo_time_dev")
+            path.call("odo_volume_icp{}_time_dev", *model, _fp(_colmajor(model_pose)), *sensor, _fp(_colmajor(Cm)), int(stride),
+                      2 * self.params.mu if dist_max is None else dist_max, huber_delta, *path.ph, int(reps), _fp(us))
         finally:
             self._free_dev(temps)
         return float(us[0]), float(us[1])
 
+    def icp_photo_time(self, depth, grey, model_depth, model_nrmw, model_rgba, model_pose, C_sensor_to_model, stride=1, dist_max=None,
+                       huber_delta=0.0, photo=None, reps=50):
+        """Event timing of the two kernels of the alignment with the photometric term: (rows, step) microseconds per launch."""
+        return self._icp_time(self._IcpPath(self, True, photo), depth, grey, (model_depth, model_nrmw, model_rgba), model_pose,
+                              C_sensor_to_model, stride, dist_max, huber_delta, reps)
+
     def icp_time(self, depth, model_depth, model_nrmw, model_pose, C_sensor_to_model, stride=1, dist_max=None, huber_delta=0.0, reps=50):
         """Event timing of the alignment's two kernels: (rows, step) microseconds per launch, means over reps launches each."""
-        (raw_d, dep_d, nrm_d), temps = self._model_frames(depth, model_depth, model_nrmw)
-        us = np.zeros(2, np.float32)
-        try:
-            L.check(self.lib.odo_volume_icp_time_dev(self.h, dep_d, nrm_d, _fp(_colmajor(model_pose)), raw_d, _fp(_colmajor(C_sensor_to_model)),
-                                                     int(stride), 2 * self.params.mu if dist_max is None else dist_max, huber_delta, int(reps),
-                                                     _fp(us)), "odo_volume_icp_time_dev")
-        finally:
-            self._free_dev(temps)
-        return float(us[0]), float(us[1])
+        return self._icp_time(self._IcpPath(self, False), depth, None, (model_depth, model_nrmw, None), model_pose, C_sensor_to_model,
+                              stride, dist_max, huber_delta, reps)
 
     def align(self, depth, model_depth, model_nrmw, model_pose, init_pose, trace=False, params=None, grey=None, model_rgba=None,
               photo=None):
@@ -1266,71 +1252,23 @@ class TsdfVolume:
         the photometric rows join the geometric ones (photo: photo_params()); the result gains photo_pairs and photo_cost and a
         trace entry's acc has 31 sums."""
         p = self.icp_params() if params is None else params
-        if grey is not None or model_rgba is not None:
-            return self._photo_align(depth, grey, model_depth, model_nrmw, model_rgba, model_pose, init_pose, trace, p, photo)
-        (raw_d, dep_d, nrm_d), temps = self._model_frames(depth, model_depth, model_nrmw)
+        path = self._IcpPath(self, grey is not None or model_rgba is not None, photo)
+        sensor, model, temps = path.frames(depth, grey, (model_depth, model_nrmw, model_rgba))
         cap = sum(p.iters[:p.levels]) if trace else 0
-        rows = (L.IcpTraceRow * max(cap, 1))()
+        rows = (path.TraceRow * max(cap, 1))()
         n = C.c_int(0)
-        res = L.IcpResult()
+        res = path.Result()
         pose = np.zeros(16, np.float32)
         try:
-            L.check(self.lib.odo_volume_icp_align_dev(self.h, C.byref(p), dep_d, nrm_d, _fp(_colmajor(model_pose)), raw_d,
-                                                      _fp(_colmajor(init_pose)), _fp(pose), C.byref(res), rows if trace else None, cap,
-                                                      C.byref(n)), "odo_volume_icp_align_dev")
+            path.call("odo_volume_icp{}_align_dev", C.byref(p), *path.ph, *model, _fp(_colmajor(model_pose)), *sensor,
+                      _fp(_colmajor(init_pose)), _fp(pose), C.byref(res), rows if trace else None, cap, C.byref(n))
         finally:
             self._free_dev(temps)
-        out = (_from_colmajor(pose), self._icp_result(res))
+        out = (_from_colmajor(pose), path.result(res))
         if trace:
             out += ([dict(level=r.level, iteration=r.iteration, acc=np.array(r.acc, np.float64), delta=np.array(r.delta, np.float32),
                           C=_from_colmajor(list(r.C))) for r in rows[:n.value]],)
         return out
-
-    def _photo_align(self, depth, grey, model_depth, model_nrmw, model_rgba, model_pose, init_pose, trace, p, photo):
-        (raw_d, grey_d, dep_d, nrm_d, rgba_d), temps = self._photo_frames(depth, grey, model_depth, model_nrmw, model_rgba)
-        ph = self.photo_params() if photo is None else photo
-        cap = sum(p.iters[:p.levels]) if trace else 0
-        rows = (L.IcpPhotoTraceRow * max(cap, 1))()
-        n = C.c_int(0)
-        res = L.IcpPhotoResult()
-        pose = np.zeros(16, np.float32)
-        try:
-            L.check(self.lib.odo_volume_icp_photo_align_dev(self.h, C.byref(p), C.byref(ph), dep_d, nrm_d, rgba_d, _fp(_colmajor(model_pose)),
-                                                            raw_d, grey_d, _fp(_colmajor(init_pose)), _fp(pose), C.byref(res),
-                                                            rows if trace else None, cap, C.byref(n)), "odo_volume_icp_photo_align_dev")
-        finally:
-            self._free_dev(temps)
-        out = (_from_colmajor(pose), self._icp_photo_result(res))
-        if trace:
-            out += ([dict(level=r.level, iteration=r.iteration, acc=np.array(r.acc, np.float64), delta=np.array(r.delta, np.float32),
-                          C=_from_colmajor(list(r.C))) for r in rows[:n.value]],)
-        return out
-
-    def _photo_track(self, depth, grey, prev_pose, integrate, p, colour, photo):
-        size = (self.rows, self.cols)
-        frames = [(depth, np.uint16, size), (grey, np.float32, size)]
-        if colour is not None:
-            if not self.has_colour:
-                raise L.OdoError("TsdfVolume.track: the volume has no colour grid (enable_colour first)")
-            frames.append((colour, np.uint8, size + (self.colour_params.channels,)))
-        handles, temps = self._frames_dev(frames)
-        ph = self.photo_params() if photo is None else photo
-        res = L.IcpPhotoResult()
-        pose = np.zeros(16, np.float32)
-        try:
-            L.check(self.lib.odo_volume_track_photo_dev(self.h, C.byref(p), C.byref(ph), handles[0], handles[1], _fp(_colmajor(prev_pose)),
-                                                        _fp(pose), C.byref(res)), "odo_volume_track_photo_dev")
-            if integrate and res.icp.status == 0:
-                if self._follow is not None:   # the window moves for this pose before the frame is fused
-                    L.check(self.lib.odo_volume_follow(self.h, _fp(pose), None), "odo_volume_follow")
-                if colour is not None:
-                    L.check(self.lib.odo_volume_integrate_colour_dev(self.h, handles[0], handles[2], _fp(pose)),
-                            "odo_volume_integrate_colour_dev")
-                else:
-                    L.check(self.lib.odo_volume_integrate_dev(self.h, handles[0], _fp(pose)), "odo_volume_integrate_dev")
-        finally:   # odo_dev_free waits for the context's stream: the integration has read the frames
-            self._free_dev(temps)
-        return _from_colmajor(pose), self._icp_photo_result(res)
 
     def track(self, depth, prev_pose, integrate=False, params=None, grey=None, colour=None, photo=None):
         """Frame-to-model tracking of one depth frame (a uint16 numpy array or a device handle): the volume is ray-cast from prev_pose
@@ -1339,23 +1277,27 @@ class TsdfVolume:
         float32 grey image; a volume with colour) the ray-cast includes the colours and the alignment the photometric rows (photo:
         photo_params()); integrate=True with colour (the frame's uint8 colour pixels) then fuses the coloured frame."""
         p = self.icp_params() if params is None else params
-        if grey is not None:
-            return self._photo_track(depth, grey, prev_pose, integrate, p, colour, photo)
-        if colour is not None or photo is not None:
+        if grey is None and (colour is not None or photo is not None):
             raise ValueError("TsdfVolume.track: colour and photo belong to the photometric path (give grey)")
-        (raw_d,), temps = self._frames_dev([(depth, np.uint16, (self.rows, self.cols))])
-        res = L.IcpResult()
+        if colour is not None and not self.has_colour:
+            raise L.OdoError("TsdfVolume.track: the volume has no colour grid (enable_colour first)")
+        path = self._IcpPath(self, grey is not None, photo)
+        sensor, fuse, temps = path.frames(depth, grey, colour=colour)
+        res = path.Result()
         pose = np.zeros(16, np.float32)
         try:
-            L.check(self.lib.odo_volume_track_dev(self.h, C.byref(p), raw_d, _fp(_colmajor(prev_pose)), _fp(pose), C.byref(res)),
-                    "odo_volume_track_dev")
-            if integrate and res.status == 0:
+            path.call("odo_volume_track{}_dev", C.byref(p), *path.ph, *sensor, _fp(_colmajor(prev_pose)), _fp(pose), C.byref(res))
+            result = path.result(res)
+            if integrate and result["status"] == 0:
                 if self._follow is not None:   # the window moves for this pose before the frame is fused
                     L.check(self.lib.odo_volume_follow(self.h, _fp(pose), None), "odo_volume_follow")
-                L.check(self.lib.odo_volume_integrate_dev(self.h, raw_d, _fp(pose)), "odo_volume_integrate_dev")
-        finally:   # odo_dev_free waits for the context's stream: the integration has read the frame
+                if colour is not None:
+                    L.check(self.lib.odo_volume_integrate_colour_dev(self.h, sensor[0], fuse[0], _fp(pose)), "odo_volume_integrate_colour_dev")
+                else:
+                    L.check(self.lib.odo_volume_integrate_dev(self.h, sensor[0], _fp(pose)), "odo_volume_integrate_dev")
+        finally:   # odo_dev_free waits for the context's stream: the integration has read the frames
             self._free_dev(temps)
-        return _from_colmajor(pose), self._icp_result(res)
+        return _from_colmajor(pose), result
 
     def stats(self):
         o = (C.c_long * 4)()

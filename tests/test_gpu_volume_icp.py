@@ -14,7 +14,7 @@ from conftest import se3_log_norm
 from test_gpu_volume import _grid_equal, _volume
 from test_volume_cpu import _pose, bits, empty_grid, integrate_model
 from test_volume_icp_cpu import (MEASURED_R_DEG, MEASURED_T_M, NACC, REFUSAL_RATIO, ROOT, bad_params, branch_rows, build_host_library,
-                                 corridor_sequence, host_step, icp, icp_acc, icp_align_model, icp_frame, icp_rows_model, pose_error,
+                                 corridor_sequence, host_step, icp, icp_acc, icp_acc_kernel_order, icp_align_model, icp_frame, icp_rows_model, pose_error,
                                  random_frames, ribbed_sequence, rows_equal)
 
 pytestmark = pytest.mark.gpu
@@ -59,6 +59,8 @@ def _check_eval(vol, p, raw, depth, nrmw, P_m, Cm, stride, dist_max, huber, tag)
     bound = n * 2.0 ** -52 * mag
     print(f"{tag}: {n} pairs, largest |acc - sum| / bound {np.max(np.abs(acc - s)[bound > 0] / bound[bound > 0]) if (bound > 0).any() else 0:.3f}")
     assert (np.abs(acc - s) <= bound).all(), (tag, acc - s, bound)
+    order = icp_acc_kernel_order(want, mask, stride)
+    assert np.array_equal(acc.view(np.uint64), order.view(np.uint64)), (tag, acc - order)
     again = vol.icp_eval(raw, depth, nrmw, P_m, Cm, stride=stride, dist_max=dist_max, huber_delta=huber)
     assert np.array_equal(acc.view(np.uint64), again.view(np.uint64)), tag
     return n

@@ -20,7 +20,8 @@ f32 = np.float32
 
 assert TILE * TILE == BLOCK
 SIZES = [(1, 1), (2, 2), (64 // TILE, TILE), (TILE, TILE), (TILE + 1, TILE), (TILE, TILE + 1), (17, 23), (64, 1), (1, 64), (65, 33)]
-CASES = [(size, s) for size in SIZES for s in (1, 2, 4)]
+SIZES_S1 = [(120, 160)]                                            # 80 blocks: the step kernel's unrolled fold runs a whole body
+CASES = [(size, s) for size in SIZES for s in (1, 2, 4)] + [(size, 1) for size in SIZES_S1]
 CASES += [((TILE * s + dr, TILE * s + dc), s) for s in (2, 4) for dr, dc in ((0, 0), (1, 0), (0, 1))]   # the same seams on the stride's lattice
 WORST = [0.0]                                                      # the largest |acc - sum| / bound met by this module
 
@@ -65,6 +66,8 @@ def _check_eval(vol, p, raw, grey, depth, nrmw, rgba, P_m, Cm, stride, dist_max,
     WORST[0] = max(WORST[0], frac)
     print(f"{tag}: {int(mg.sum())} + {int(mp.sum())} pairs, largest |acc - sum| / bound {frac:.3f}")
     assert (np.abs(acc - s) <= bound).all(), (tag, acc - s, bound)
+    order = pc.icp_photo_acc_kernel_order(want, mg, mp, stride)
+    assert np.array_equal(acc.view(np.uint64), order.view(np.uint64)), (tag, acc - order)
     again = vol.icp_eval(raw, depth, nrmw, P_m, Cm, **kw)
     assert np.array_equal(acc.view(np.uint64), again.view(np.uint64)), tag
     return int(mg.sum()), int(mp.sum())

@@ -25,7 +25,8 @@ f32 = np.float32
 NACC = 29
 
 NEW_SYMBOLS = ["odo_volume_icp_eval_dev", "odo_volume_icp_align_dev", "odo_volume_track_dev", "odo_volume_icp_time_dev"]
-ICP_KERNELS = ["volume_icp_rows_kernel", "volume_icp_step_kernel", "volume_icp_init_kernel"]
+# The instantiations for 29 sums of the kernel templates of volume_icp_kernels.hip, as the code object names them.
+ICP_KERNELS = ["volume_icp_rows_kernelILi29E", "volume_icp_step_kernelILi29E", "volume_icp_init_kernelILi29E"]
 TALLIES = ("raw0", "far", "behind", "off_left", "off_right", "off_top", "off_bottom", "nan_proj", "model_hole", "normal_zero", "gated",
            "on_gate", "huber_below", "huber_on", "huber_above", "pairs", "lattice")
 
@@ -134,6 +135,49 @@ def icp_acc(rows8, mask):
     """The 29 sums in fp64 (numpy's pairwise order) and, per sum, the sum of the terms' magnitudes."""
     t = icp_terms(rows8, mask)
     return t.sum(0), np.abs(t).sum(0)
+
+
+ICP_TILE, ICP_LANES = 16, 8      # kIcpTile and kIcpFoldLanes of odometry_amd/csrc/volume_icp.hip.h
+
+
+def icp_lane_sums(terms):
+    """(n, k) fp64 terms, summed as eight lanes do: lane s starts at +0.0 and adds rows s, s + 8, s + 16, ... in that order, then the
+    lanes are folded as ((0 + 4) + (2 + 6)) + ((1 + 5) + (3 + 7))."""
+    terms = np.asarray(terms, np.float64)
+    v = np.zeros((ICP_LANES,) + terms.shape[1:])
+    with np.errstate(all="ignore"):
+        for i in range(0, len(terms), ICP_LANES):
+            chunk = terms[i:i + ICP_LANES]
+            v[:len(chunk)] += chunk
+        return ((v[0] + v[4]) + (v[2] + v[6])) + ((v[1] + v[5]) + (v[3] + v[7]))
+
+
+def icp_tiles(stride, *frames):
+    """The frames on the stride's lattice, cut into the rows kernel's blocks in the order block = blockIdx.y * gridDim.x + blockIdx.x:
+    per block and frame an array whose first axis is the thread, t = (t % tile, t / tile); zeros outside the frame."""
+    lat = [np.asarray(a)[::stride, ::stride] for a in frames]
+    ly, lx = lat[0].shape[:2]
+    T = ICP_TILE
+    for by in range(-(-ly // T)):
+        for bx in range(-(-lx // T)):
+            out = []
+            for a in lat:
+                tile = np.zeros((T, T) + a.shape[2:], a.dtype)
+                part = a[by * T:(by + 1) * T, bx * T:(bx + 1) * T]
+                tile[:part.shape[0], :part.shape[1]] = part
+                out.append(tile.reshape((T * T,) + a.shape[2:]))
+            yield out
+
+
+def icp_acc_kernel_order(rows8, mask, stride):
+    """The 29 sums in the kernels' order: per block of the rows kernel the 256 rows of its threads (all-zero where there is no pair)
+    through icp_lane_sums, then the blocks' partials through icp_lane_sums again. The device's bits."""
+    partials = []
+    for r, m in icp_tiles(stride, rows8, mask):
+        t = icp_terms(r, np.ones(len(r), bool))
+        t[:, NACC - 1] = m
+        partials.append(icp_lane_sums(t))
+    return icp_lane_sums(np.array(partials))
 
 
 # ---- the same, one fp32 operation at a time --------------------------------------------------------------------------------------
@@ -625,6 +669,23 @@ def test_vectorised_rows_equal_the_loop_bit_for_bit():
     print(len(cases), "evaluations:", total)
     for k in ("raw0", "far", "model_hole", "normal_zero", "gated", "huber_below", "huber_above", "pairs", "off_left", "off_right"):
         assert total[k] > 0, (k, total)
+
+
+def test_the_kernels_order_of_the_sums_is_one_of_the_orders():
+    """icp_acc_kernel_order, which tests/test_gpu_volume_icp.py holds the GPU to bit for bit: inside the bound of any order round the
+    pairwise sums and the count exact, on one block, on several, with two partials per lane and with more than 64 blocks; a single
+    row comes out as its own terms."""
+    for size, stride, blocks in (((1, 1), 1, 1), ((17, 23), 1, 4), ((65, 33), 1, 15), ((65, 33), 4, 2), (SMALL, 1, 80)):
+        K = (1.3 * max(*size, 8), (size[1] - 1) / 2, (size[0] - 1) / 2)
+        p, raw, depth, nrmw, P_m, P_init = random_frames(0, size, K)
+        rows8, mask = icp_rows_model(raw, depth, nrmw, *icp_frame(P_m, P_init), p, stride, 0.3, 0.01)
+        assert len(list(icp_tiles(stride, mask))) == blocks
+        s, mag = icp_acc(rows8, mask)
+        order = icp_acc_kernel_order(rows8, mask, stride)
+        n = int(mask.sum())
+        assert n > 0 and order[28] == n and (np.abs(order - s) <= n * 2.0 ** -52 * mag).all(), (size, stride)
+        if n == 1:
+            assert np.array_equal(order, icp_terms(rows8, mask)[0])
 
 
 @pytest.mark.parametrize("row", branch_rows(), ids=lambda r: r[0])

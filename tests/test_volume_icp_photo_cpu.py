@@ -26,7 +26,8 @@ f32 = np.float32
 
 NEW_SYMBOLS = ["odo_volume_icp_photo_eval_dev", "odo_volume_icp_photo_align_dev", "odo_volume_track_photo_dev",
                "odo_volume_icp_photo_time_dev"]
-PHOTO_KERNELS = ["volume_icp_photo_rows_kernel", "volume_icp_photo_step_kernel", "volume_icp_photo_init_kernel"]
+# The instantiations for 31 sums of the kernel templates of volume_icp_kernels.hip, as the code object names them.
+PHOTO_KERNELS = ["volume_icp_rows_kernelILi31E", "volume_icp_step_kernelILi31E", "volume_icp_init_kernelILi31E"]
 # Measured with this model at the defaults (test_ground_truth_with_the_photometric_term prints them): the largest error of the six
 # frames of either case. The assertions there and in tests/test_gpu_volume_icp_photo.py are twice these.
 MEASURED_CORRIDOR_T_M = 0.031702      # frame 1 (geometric only: 0.56718, frame 1)
@@ -144,6 +145,19 @@ def test_vectorised_rows_equal_the_loop_bit_for_bit():
     for k in ("no_point", "off_left", "off_top", "model_hole", "gated", "tap00", "tap01", "tap10", "tap11", "huber_below", "huber_above",
               "pairs", "geo_only", "photo_only", "both", "neither"):
         assert total[k] > 0, (k, total)
+
+
+def test_the_kernels_order_of_the_sums_is_one_of_the_orders():
+    """icp_photo_acc_kernel_order, which tests/test_gpu_volume_icp_photo.py holds the GPU to bit for bit: inside the bound of any order
+    round the pairwise sums and both counts exact, on one block, on several, with two partials per lane and with more than 64 blocks."""
+    for size, stride in (((2, 2), 1), ((17, 23), 1), ((65, 33), 1), ((65, 33), 4), ((120, 160), 1)):
+        K = (1.3 * max(*size, 8), (size[1] - 1) / 2, (size[0] - 1) / 2)
+        p, raw, grey, depth, nrmw, rgba, P_m, P_init = pc.random_photo_frames(0, size, K)
+        rows16, mg, mp = pc.icp_photo_rows_model(raw, grey, depth, nrmw, rgba, *icp_frame(P_m, P_init), p, stride, 0.3, 0.01, 0.01, 6.0)
+        s, mag, n = pc.icp_photo_acc(rows16, mg, mp)
+        order = pc.icp_photo_acc_kernel_order(rows16, mg, mp, stride)
+        assert n > 0 and order[28] == mg.sum() and order[29] == mp.sum(), (size, stride)
+        assert (np.abs(order - s) <= n * 2.0 ** -52 * mag).all(), (size, stride)
 
 
 @pytest.mark.parametrize("row", pc.photo_branch_rows(), ids=lambda r: r[0])

@@ -6,8 +6,8 @@ import numpy as np
 
 from test_volume_cpu import _pose, empty_grid, params
 from test_volume_colour_cpu import empty_colour, integrate_colour_model
-from test_volume_icp_cpu import (EXACT_K, RIBBED_GRID, RIBBED_SCENE, SMALL, acc_matrix, exact_frame, icp, icp_frame, icp_rows_loop,
-                                 icp_rows_model, icp_step_py, mul4, small_K)
+from test_volume_icp_cpu import (EXACT_K, RIBBED_GRID, RIBBED_SCENE, SMALL, acc_matrix, exact_frame, icp, icp_frame, icp_lane_sums,
+                                 icp_rows_loop, icp_rows_model, icp_step_py, icp_tiles, mul4, small_K)
 from test_volume_raycast_cpu import default_view, raycast_model
 
 f32 = np.float32
@@ -101,6 +101,19 @@ def icp_photo_acc(rows16, mask_g, mask_p):
     acc = np.concatenate([t.sum(0), [float(len(tg)), float(len(tp)), tp[:, 27].sum()]])
     mag = np.concatenate([np.abs(t).sum(0), [float(len(tg)), float(len(tp)), np.abs(tp[:, 27]).sum()]])
     return acc, mag, len(tg) + len(tp)
+
+
+def icp_photo_acc_kernel_order(rows16, mask_g, mask_p, stride):
+    """The 31 sums in the kernels' order: per block of the rows kernel 512 rows, the geometric ones of its 256 threads and then the
+    photometric ones (all-zero where a row is missing), through icp_lane_sums — sums 0 .. 27 over all 512, the geometric count over
+    the first 256, the photometric count and cost over the last 256 — then the blocks' partials through icp_lane_sums again. The
+    device's bits."""
+    partials = []
+    for r, mg, mp in icp_tiles(stride, rows16, mask_g, mask_p):
+        tg, tp = _terms28(r[:, :8]), _terms28(r[:, 8:])
+        partials.append(np.concatenate([icp_lane_sums(np.concatenate([tg, tp])),
+                                        [icp_lane_sums(mg), icp_lane_sums(mp), icp_lane_sums(tp[:, 27])]]))
+    return icp_lane_sums(np.array(partials))
 
 
 # ---- the same, one fp32 operation at a time --------------------------------------------------------------------------------------

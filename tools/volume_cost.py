@@ -33,13 +33,14 @@
             frame, a host call without a wait, in this mode only).
 
   icp       the frame-to-model alignment's two kernels timed with events (api.TsdfVolume.icp_time: `reps` launches of
-            volume_icp_rows_kernel, then of volume_icp_step_kernel's fold, each batch between two events on the volume's stream):
+            volume_icp_rows_kernel<29>, then of volume_icp_step_kernel<29>'s fold, each batch between two events on the volume's stream):
             the pinned grid after `frames` integrations at their true poses, the ray-cast from the last pose but one as the model
             frame, the last frame as the sensor frame, at 480 x 640 and strides 4, 2 and 1. One JSON line per stride with the medians
             over `runs` batches, the pairs and the blocks, then the wall time of whole api.TsdfVolume.track calls (ray-cast, the
             alignment's launches, its allocations and its one wait). With --photo the volume has a colour grid (every frame fused
             with its grey replicated into R, G and B), the ray-cast includes the colours, and each line carries the two kernels of
-            the alignment with the photometric term (api.TsdfVolume.icp_photo_time) beside the geometric two, timed in alternating
+            the alignment with the photometric term (api.TsdfVolume.icp_photo_time: volume_icp_rows_kernel<31> and
+            volume_icp_step_kernel<31>, the same templates instantiated for 31 sums) beside the geometric two, timed in alternating
             batches of the same call; the last line gives the wall time of track(grey=...) beside the geometric track's.
 
   shift     the moving volume's launches timed with events (api.TsdfVolume.shift_time: batches of `reps` between two events on the
