@@ -719,6 +719,25 @@ int odo_volume_raycast_dev(odo_volume* v, const odo_raycast_params* p, const flo
  * the volume); the call waits and copies. */
 int odo_volume_raycast(odo_volume* v, const odo_raycast_params* p, const float abs_pose_colmajor[16], float* depth, uint16_t* raw,
                        float* nrmw, uint8_t* rgba);
+/* How the ray-cast's colour frame samples the colour grid (DESIGN.md section 9.11 holds the same rule). mode 0, the state at create:
+ * the nearest voxel, as the table above states it. mode 1, trilinear: on a hit whose cell evaluation at t = z is valid, with cw_d the
+ * colour words of the cell's eight corners d (bit 0 = x, bit 1 = y, bit 2 = z, the corners c_xyz above), m_d = (wc_d > 0) ? 1.0f :
+ * 0.0f; M = the interpolation above (l, m, F with fr_x, fr_y, fr_z of that cell evaluation) over m_d in place of the corners; per
+ * channel k, P_k = the same over m_d * (float)C_dk. If M > 0.0f the pixel is ((uint8)fminf(255.0f, rintf(P_k / M)), 255) with an IEEE
+ * fp32 divide, else four zeros; a cell that is not valid and a pixel without a hit give four zeros, as in mode 0. Eight coloured
+ * corners have M == 1.0f exactly. depth, raw and nrmw do not depend on the mode, bit for bit.
+ * The mode is read when a ray-cast is enqueued: odo_volume_raycast_dev, odo_volume_raycast and odo_volume_track_photo_dev (whose
+ * model frame then carries the interpolated colours) follow it; a ray-cast without rgba and odo_volume_track_dev launch what they
+ * launch in mode 0. Refused (-1, nothing enqueued, the mode unchanged) on a volume without a colour grid and for any other mode.
+ * Legal while the volume is attached; odo_volume_clear leaves the mode. odo_volume_colour_sampling returns the mode (-1: NULL). */
+int odo_volume_set_colour_sampling(odo_volume* v, int mode);
+int odo_volume_colour_sampling(odo_volume* v);
+/* Diagnostic: one ray-cast to warm and then `reps` (1 .. 10000) of them between two events on the volume's stream, into the frames
+ * that the volume owns (depth and nrmw; rgba as well if with_colour), under the colour sampling mode as it is; the call waits.
+ * *us: microseconds per ray-cast (the launch and the event that orders a later integration behind it). Validation as
+ * odo_volume_raycast. */
+int odo_volume_raycast_time(odo_volume* v, const odo_raycast_params* p, const float abs_pose_colmajor[16], int with_colour, int reps,
+                            float* us);
 
 /* ---- Frame-to-model tracking: a depth frame aligned to the volume's ray-cast by point-to-plane ICP --------------------------------
  * The model frame is a ray-cast of the volume at the volume's own rows, cols and K (f = K.f0, cx = K.cx0, cy = K.cy0): depth

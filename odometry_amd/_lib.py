@@ -276,6 +276,9 @@ SIGNATURES = {
     "odo_rgbd_frontend_colour": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "odo_volume_raycast_dev": (C.c_int, [_vp, C.POINTER(RaycastParams), _fp, _vp, _vp, _vp, _vp]),
     "odo_volume_raycast": (C.c_int, [_vp, C.POINTER(RaycastParams), _fp, _fp, C.POINTER(C.c_uint16), _fp, _u8p]),
+    "odo_volume_set_colour_sampling": (C.c_int, [_vp, C.c_int]),
+    "odo_volume_colour_sampling": (C.c_int, [_vp]),
+    "odo_volume_raycast_time": (C.c_int, [_vp, C.POINTER(RaycastParams), _fp, C.c_int, C.c_int, _fp]),
     "odo_volume_icp_eval_dev": (C.c_int, [_vp, _vp, _vp, _fp, _vp, _fp, C.c_int, C.c_float, C.c_float, _dp, _vp]),
     "odo_volume_icp_time_dev": (C.c_int, [_vp, _vp, _vp, _fp, _vp, _fp, C.c_int, C.c_float, C.c_float, C.c_int, _fp]),
     "odo_volume_icp_align_dev": (C.c_int, [_vp, C.POINTER(IcpParams), _vp, _vp, _fp, _vp, _fp, _fp, C.POINTER(IcpResult),

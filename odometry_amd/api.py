@@ -1093,6 +1093,31 @@ class TsdfVolume:
             out += (rgba,)
         return out
 
+    def raycast_time(self, abs_pose, size=None, K=None, t_min=0.0, step=None, n_steps=None, colour=False, reps=20):
+        """Microseconds per ray-cast: `reps` of them between two events on the volume's stream (odo_volume_raycast_time), with the
+        colour frame if colour, under the colour sampling mode as it is."""
+        rp = self.raycast_params(size, K, t_min, step, n_steps)
+        us = C.c_float(0)
+        L.check(self.lib.odo_volume_raycast_time(self.h, C.byref(rp), _fp(_colmajor(abs_pose)), int(bool(colour)), int(reps), C.byref(us)),
+                "odo_volume_raycast_time")
+        return us.value
+
+    COLOUR_SAMPLING = ("nearest", "trilinear")
+
+    def set_colour_sampling(self, mode):
+        """How the ray-cast's colour frame samples the colour grid: "nearest" (the voxel nearest to the hit, the state at create) or
+        "trilinear" (the average of the hit cell's coloured corners). raycast(colour=True) and track(grey=...) follow it from the next
+        call on; depth and normals do not depend on it. Refused on a volume without a colour grid."""
+        if mode not in self.COLOUR_SAMPLING:
+            raise ValueError(f"colour sampling {mode!r}: one of {self.COLOUR_SAMPLING}")
+        L.check(self.lib.odo_volume_set_colour_sampling(self.h, self.COLOUR_SAMPLING.index(mode)), "odo_volume_set_colour_sampling")
+
+    @property
+    def colour_sampling(self):
+        mode = self.lib.odo_volume_colour_sampling(self.h)
+        L.check(min(mode, 0), "odo_volume_colour_sampling")
+        return self.COLOUR_SAMPLING[mode]
+
     # ---- frame-to-model tracking (odo_volume_icp_*, odo_volume_track_dev) ----
     ICP_STATUS = ("aligned", "too few pairs", "rank-deficient")
     # Default of min_eig_ratio: 0, nothing is refused as rank-deficient unless the caller sets a ratio. Measured with the fp32 model

@@ -43,6 +43,7 @@ struct odo_volume {
   uint32_t* d_col;              // [n_vox]: {R, G, B, wc}
   uint32_t *d_rgba, *d_mesh_rgba;   // the colours of the extraction's points / the mesh's vertices, grown on demand
   long rgba_capacity, mesh_rgba_capacity;
+  int colour_sampling;          // of the ray-cast's colour frame: 0 nearest voxel, 1 trilinear (odo_volume_set_colour_sampling)
   // ray-cast (odo_volume_raycast's frames on the device: sized on first use, grown on demand)
   float* d_ray_depth;
   uint16_t* d_ray_raw;
@@ -477,9 +478,22 @@ static int volume_raycast_launch(odo_volume* v, const odo_raycast_params* rp, co
   a.ex = e[0]; a.ey = e[1]; a.ez = e[2];
   a.g00 = G[0]; a.g01 = G[1]; a.g02 = G[2]; a.g10 = G[3]; a.g11 = G[4]; a.g12 = G[5]; a.g20 = G[6]; a.g21 = G[7]; a.g22 = G[8];
   a.depth = depth; a.raw = raw; a.nrmw = nrmw; a.rgba = rgba;
-  launch_volume_raycast(a, v->own);
+  launch_volume_raycast(a, v->colour_sampling == 1, v->own);   // (the mode as it is now: nothing caches it)
   HIP_OK(hipGetLastError());
   return volume_mark(v, v->own);
+}
+
+extern "C" int odo_volume_set_colour_sampling(odo_volume* v, int mode) {
+  if (!v) return fail("odo_volume_set_colour_sampling: NULL volume");
+  if (mode != 0 && mode != 1) return fail("odo_volume_set_colour_sampling: mode %d (0 nearest, 1 trilinear)", mode);
+  if (!v->colour) return fail("odo_volume_set_colour_sampling: the volume has no colour grid (odo_volume_enable_colour first)");
+  v->colour_sampling = mode;
+  return 0;
+}
+
+extern "C" int odo_volume_colour_sampling(odo_volume* v) {
+  if (!v) return fail("odo_volume_colour_sampling: NULL volume");
+  return v->colour_sampling;
 }
 
 extern "C" int odo_volume_raycast_dev(odo_volume* v, const odo_raycast_params* rp, const float abs_pose_colmajor[16], float* depth_dev,
@@ -521,6 +535,37 @@ extern "C" int odo_volume_raycast(odo_volume* v, const odo_raycast_params* rp, c
   if (nrmw) HIP_OK(hipMemcpyAsync(nrmw, v->d_ray_nrmw, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, v->own));
   if (rgba) HIP_OK(hipMemcpyAsync(rgba, v->d_ray_rgba, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, v->own));
   HIP_OK(hipStreamSynchronize(v->own));
+  return 0;
+}
+
+// Diagnostic: one ray-cast to warm, then `reps` of them between two events on the volume's stream, into the frames the volume owns
+// (depth and nrmw; rgba as well with_colour), under the colour sampling mode as it is. *us: microseconds per launch.
+extern "C" int odo_volume_raycast_time(odo_volume* v, const odo_raycast_params* rp, const float abs_pose_colmajor[16], int with_colour,
+                                       int reps, float* us) {
+  const char* who = "odo_volume_raycast_time";
+  if (!v || !rp || !abs_pose_colmajor || !us) return fail("%s: NULL arg", who);
+  if (reps < 1 || reps > 10000) return fail("%s: reps 1 .. 10000", who);
+  if (raycast_check(who, rp, abs_pose_colmajor)) return -1;
+  if (with_colour && !v->colour) return fail("%s: the volume has no colour grid (odo_volume_enable_colour first)", who);
+  HIP_OK(hipSetDevice(v->device));
+  if (volume_ray_frames(who, v, (long)rp->rows * rp->cols, with_colour != 0)) return -1;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  bool ok = true;
+  for (auto& x : ev) ok = ok && hipEventCreate(&x) == hipSuccess;
+  float ms = 0.0f;
+  for (int i = 0; ok && i <= reps; i++) {
+    ok = volume_raycast_launch(v, rp, abs_pose_colmajor, v->d_ray_depth, nullptr, v->d_ray_nrmw, with_colour ? v->d_ray_rgba : nullptr) == 0;
+    if (i == 0) ok = ok && hipEventRecord(ev[0], v->own) == hipSuccess;   // (behind the warming launch)
+  }
+  ok = ok && hipEventRecord(ev[1], v->own) == hipSuccess && hipStreamSynchronize(v->own) == hipSuccess &&
+       hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess;
+  for (auto& x : ev) if (x) (void)hipEventDestroy(x);
+  if (!ok) {
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(v->own);
+    return fail("%s: timing failed", who);
+  }
+  *us = 1e3f * ms / (float)reps;
   return 0;
 }
 

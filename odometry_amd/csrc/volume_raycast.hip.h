@@ -32,6 +32,8 @@ struct VolRaycastArgs {
   uint32_t* rgba;          // likewise
 };
 
-void launch_volume_raycast(const VolRaycastArgs& a, hipStream_t s);
+// interp: the colour frame is the trilinear average of the cell's coloured corners (volume_raycast_interp_kernel, DESIGN.md section
+// 9.11) instead of the nearest voxel's colour. Without a colour frame the two kernels write the same frames, and the first is launched.
+void launch_volume_raycast(const VolRaycastArgs& a, bool interp, hipStream_t s);
 
 }  // namespace odo

@@ -113,6 +113,35 @@ ODO_RC_HD uint32_t rc_nearest(const RcCell& o, const RcRay& r) {
   return ((uint32_t)iz * (uint32_t)r.ny + (uint32_t)iy) * (uint32_t)r.nx + (uint32_t)ix;
 }
 
+// The colour of the cell evaluation's point as the trilinear average of the cell's coloured corners. cp: the
+// colour words {R, G, B, wc} of the eight corners as four x-adjacent pairs, in the order of rc_cell's loads (the corner order of
+// RcCell::c). A corner counts with m = 1 if its wc > 0, else 0; the coverage M and per channel the sum P are rc_interp itself over m
+// and over m * (float)C with the cell's fractions, so eight coloured corners give M == 1.0f exactly. (R, G, B, 255) with
+// (uint8)fminf(255.0f, rintf(P / M)) per channel if M > 0.0f, else four zeros.
+ODO_RC_HD uint32_t rc_colour_interp(const RcCell& o, const uint64_t cp[4]) {
+  const uint32_t cw[8] = {(uint32_t)cp[0], (uint32_t)(cp[0] >> 32), (uint32_t)cp[1], (uint32_t)(cp[1] >> 32),
+                          (uint32_t)cp[2], (uint32_t)(cp[2] >> 32), (uint32_t)cp[3], (uint32_t)(cp[3] >> 32)};
+  RcCell m = o, p = o;   // (the fractions)
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+  for (int d = 0; d < 8; d++) m.c[d] = (cw[d] >> 24) ? 1.0f : 0.0f;
+  const float M = rc_interp(m);
+  if (!(M > 0.0f)) return 0u;
+  uint32_t out = 0xff000000u;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+  for (int k = 0; k < 3; k++) {
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int d = 0; d < 8; d++) p.c[d] = m.c[d] * (float)((cw[d] >> (8 * k)) & 0xffu);
+    out |= (uint32_t)__builtin_fminf(255.0f, __builtin_rintf(rc_interp(p) / M)) << (8 * k);
+  }
+  return out;
+}
+
 // The march: the ray ends at its first valid sample with F <= 0 and is a hit iff the sample before exists, is valid and is positive.
 // Lanes of a wave leave the loop one by one; the wave leaves it when the last has.
 template <class Load2>

@@ -8,7 +8,10 @@
             beside volume_integrate_kernel in one trace — followed by coloured extractions and meshes (one colour launch behind each).
             Every leg ends with ray-casts (api.TsdfVolume.raycast: one volume_raycast_kernel launch each) at 480 x 640 with the
             volume's K from the first and the last pose of the drive, t_min = 0, step = mu / 2, samples up to max_depth + mu; the
-            coloured legs ask for the colour frame as well.
+            coloured legs ask for the colour frame as well, and then time the ray-cast with its colour frame under both sampling
+            modes of odo_volume_set_colour_sampling (volume_raycast_kernel and volume_raycast_interp_kernel), alternating in the one
+            call: medians over `runs` batches of `reps` launches between two events (api.TsdfVolume.raycast_time), in the line's
+            `raycast_colour_us`.
             Run it under the profiler, in a run of its own (no counters in that run), then summarise:
               rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/volume_cost.py kernels
               python tools/volume_cost.py summary <dir>
@@ -42,6 +45,8 @@
             the alignment with the photometric term (api.TsdfVolume.icp_photo_time: volume_icp_rows_kernel<31> and
             volume_icp_step_kernel<31>, the same templates instantiated for 31 sums) beside the geometric two, timed in alternating
             batches of the same call; the last line gives the wall time of track(grey=...) beside the geometric track's.
+            --sampling nearest | trilinear | both sets the colour sampling of the model frame for those whole track(grey=...) calls
+            (both: the two modes alternating in the same loop, a line for each).
 
   shift     the moving volume's launches timed with events (api.TsdfVolume.shift_time: batches of `reps` between two events on the
             volume's stream, the shift not applied): the pinned and the large grid after `frames` integrations at their true poses,
@@ -50,8 +55,8 @@
             hipMemcpyAsync of the same bytes, of a hipMemsetAsync of the same bytes, and of the spill's count, scan and scatter,
             with the bytes moved and the points that shift spills.
 
-  python tools/volume_cost.py kernels [--frames 10] [--extractions 3] [--json FILE]
-  python tools/volume_cost.py icp [--frames 10] [--runs 7] [--reps 50] [--photo]
+  python tools/volume_cost.py kernels [--frames 10] [--extractions 3] [--runs 7] [--reps 20] [--json FILE]
+  python tools/volume_cost.py icp [--frames 10] [--runs 7] [--reps 50] [--photo [--sampling nearest|trilinear|both]]
   python tools/volume_cost.py shift [--frames 10] [--runs 7] [--reps 20]
   python tools/volume_cost.py summary DIR [--json FILE]
   python tools/volume_cost.py track [--runs 3] [--steps 200] [--warmup 20] [--frames 100] [--modes none,pinned,large[,coloured][,follow]]
@@ -123,6 +128,15 @@ def kernels(args):
             for _ in range(args.extractions):
                 for k in (0, len(seq["poses"]) - 1):
                     hits.append(int((vol.raycast(seq["poses"][k], step=MU / 2, raw=True, colour=coloured)[0] > 0).sum()))
+            cast = {}
+            if coloured:                      # the ray-cast with its colour frame under both sampling modes, alternating, between events
+                for _ in range(args.runs):
+                    for k in (0, len(seq["poses"]) - 1):
+                        for m in api.TsdfVolume.COLOUR_SAMPLING:
+                            vol.set_colour_sampling(m)
+                            cast.setdefault(f"pose {k} {m}", []).append(vol.raycast_time(seq["poses"][k], step=MU / 2, colour=True, reps=args.reps))
+                vol.set_colour_sampling("nearest")
+                cast = {k: _med(v) for k, v in cast.items()}
             nx, ny, nz = GRIDS[grid]["dims"]
             row = dict(raycast_hits=hits[:2], voxels=nx * ny * nz, updated_per_frame=int(np.median(upd)), in_band_per_frame=int(np.median(band)), points=n,
                        vertices=nv, triangles=nt, pixels=synth.TUM_ROWS * synth.TUM_COLS, integrate_host_us_back_to_back=round(host_us, 1))
@@ -130,7 +144,7 @@ def kernels(args):
                 out[grid]["coloured_integrate_host_us_back_to_back"] = row["integrate_host_us_back_to_back"]
             else:
                 out[grid] = row
-            print(json.dumps(dict(grid=grid, coloured=coloured, **row)), flush=True)
+            print(json.dumps(dict(grid=grid, coloured=coloured, **row, **({"raycast_colour_us": cast} if cast else {}))), flush=True)
             vol.close()
     for d in dev + cdev:
         ctx.free(d)
@@ -308,16 +322,22 @@ def icp_photo(args):
         print(json.dumps(dict(stride=stride, lattice=lx * ly, pairs=int(acc[28]), photo_pairs=int(acc[29]), blocks=(-(-lx // 16)) * (-(-ly // 16)),
                               rows_us=_med(geo[:, 0]), photo_rows_us=_med(photo[:, 0]), step_fold_us=_med(geo[:, 1]),
                               photo_step_fold_us=_med(photo[:, 1]))), flush=True)
-    wall = dict(geo=[], photo=[])
+    modes = list(api.TsdfVolume.COLOUR_SAMPLING) if args.sampling == "both" else [args.sampling]
+    wall = dict(geo=[], **{m: [] for m in modes})
+    p_res = {}
     for _ in range(args.runs):
         t0 = time.perf_counter()
         _, g_res = vol.track(raw, P_m)
-        t1 = time.perf_counter()
-        _, p_res = vol.track(raw, P_m, grey=grey)
-        wall["geo"].append(1e3 * (t1 - t0))
-        wall["photo"].append(1e3 * (time.perf_counter() - t1))
-    print(json.dumps(dict(track_call_ms=_med(wall["geo"]), track_photo_call_ms=_med(wall["photo"]), status=[g_res["status"], p_res["status"]],
-                          iterations=[g_res["iterations"], p_res["iterations"]], pairs=p_res["pairs"], photo_pairs=p_res["photo_pairs"])), flush=True)
+        wall["geo"].append(1e3 * (time.perf_counter() - t0))
+        for m in modes:                   # the whole call under each sampling mode of the model's colour frame, alternating
+            vol.set_colour_sampling(m)
+            t1 = time.perf_counter()
+            _, p_res[m] = vol.track(raw, P_m, grey=grey)
+            wall[m].append(1e3 * (time.perf_counter() - t1))
+    for m in modes:
+        r = p_res[m]
+        print(json.dumps(dict(sampling=m, track_call_ms=_med(wall["geo"]), track_photo_call_ms=_med(wall[m]), status=[g_res["status"], r["status"]],
+                              iterations=[g_res["iterations"], r["iterations"]], pairs=r["pairs"], photo_pairs=r["photo_pairs"])), flush=True)
     vol.close()
     ctx.close()
 
@@ -360,6 +380,8 @@ def main():
     k.add_argument("--frames", type=int, default=10)
     k.add_argument("--extractions", type=int, default=3)
     k.add_argument("--json", default=None)
+    k.add_argument("--runs", type=int, default=7)
+    k.add_argument("--reps", type=int, default=20)
     s = sub.add_parser("summary")
     s.add_argument("dir")
     s.add_argument("--json", default=None)
@@ -374,6 +396,7 @@ def main():
     i.add_argument("--runs", type=int, default=7)
     i.add_argument("--reps", type=int, default=50)
     i.add_argument("--photo", action="store_true")
+    i.add_argument("--sampling", choices=("nearest", "trilinear", "both"), default="nearest")
     h = sub.add_parser("shift")
     h.add_argument("--frames", type=int, default=10)
     h.add_argument("--runs", type=int, default=7)
