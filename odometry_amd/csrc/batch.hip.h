@@ -169,6 +169,7 @@ struct odo_tracker_batch {
   bool with_lists;
   hipEvent_t ev_a;         // a point on stream A (the rebuild of next_img on stream C goes behind an abandoned early Solve)
   int depth_persist_bails, depth_persist_strikes, depth_persist_clean;   // chains run again after a give-up (lifetime) / strikes that count / clean chains since
+  bool depth_persist_env;  // ODO_BATCH_DEPTH_PERSIST as it stood at create (0: the inverse-depth LMs on a launch per iteration)
   int dead;                // 1: a wait timed out with work in flight — every later call fails fast
   double tm_frame_us, tm_head_us, tm_solve_us, tm_depth_wait_us; long tm_frames;  // host-clock averages (diagnostics)
 };
@@ -222,10 +223,17 @@ static int batch_depth_persist_max() {
   static const int n = getenv("ODO_BATCH_DEPTH_PERSIST_MAX") ? atoi(getenv("ODO_BATCH_DEPTH_PERSIST_MAX")) : 8;
   return n < 8 ? n : 8;
 }
+// ODO_BATCH_DEPTH_PERSIST=0: off. Read once per tracker, at create, like ODO_DEPTH_NO_PERSIST — the launch and the statistics both
+// go by that value (a value cached at the first chain of the PROCESS let the statistics, which read the variable at every call,
+// report "off" while the launch stayed on for every tracker made after the variable was set).
+static bool batch_depth_persist_env() {
+  const char* e = getenv("ODO_BATCH_DEPTH_PERSIST");
+  return !e || atoi(e) != 0;
+}
 extern "C" int odo_tracker_batch_depth_persistent_stats(const odo_tracker_batch* b, int* on, int* chains_redone) {
   if (!b) return fail("odo_tracker_batch_depth_persistent_stats: NULL tracker");
   if (on) *on = (b->S <= batch_depth_persist_max() && b->depth_persist_strikes < 3 && b->depth[0] && b->depth[0]->persist_cfg &&
-                 (!getenv("ODO_BATCH_DEPTH_PERSIST") || atoi(getenv("ODO_BATCH_DEPTH_PERSIST")) != 0)) ? 1 : 0;
+                 b->depth_persist_env) ? 1 : 0;
   if (chains_redone) *chains_redone = b->depth_persist_bails;
   return 0;
 }
@@ -248,6 +256,7 @@ extern "C" int odo_tracker_batch_create(int device, const odo_tracker_params* p,
     c->h_ptab = c->d_ptab = nullptr; c->persistent = c->no_persist_once = c->use_persistent = false;
   }
   b->depth_persist_bails = b->depth_persist_strikes = b->depth_persist_clean = 0;
+  b->depth_persist_env = batch_depth_persist_env();
   b->w_ring[0] = b->w_ring[1] = nullptr; b->w_posted.store(0); b->w_done.store(0); b->w_quit.store(0);
   b->tm_frame_us = b->tm_head_us = b->tm_solve_us = b->tm_depth_wait_us = 0.0; b->tm_frames = 0;
   b->overlap = (p->overlap_depth != 0) && !getenv("ODO_BATCH_NO_OVERLAP");
@@ -451,9 +460,8 @@ static int batch_chain_tail(odo_tracker_batch* b, BatchChain* c, hipStream_t s) 
 // ODO_BATCH_DEPTH_PERSIST=0: off. A sequence whose launch gives up (a wait ran out: its workgroups were not all resident) makes the
 // whole chain run again on the step launches (batch_chain_run); three such chains switch the launch off for this tracker.
 static bool batch_depth_persist_ok(const odo_tracker_batch* b, const BatchChain* c) {
-  static const bool on = !getenv("ODO_BATCH_DEPTH_PERSIST") || atoi(getenv("ODO_BATCH_DEPTH_PERSIST")) != 0;
   const odo_depth* d0 = b->depth[0];
-  return on && !c->no_persist_once && b->depth_persist_strikes < 3 && (int)c->ids.size() <= batch_depth_persist_max() && d0->persist_cfg && d0->max_iters <= kDpMaxIters &&
+  return b->depth_persist_env && !c->no_persist_once && b->depth_persist_strikes < 3 && (int)c->ids.size() <= batch_depth_persist_max() && d0->persist_cfg && d0->max_iters <= kDpMaxIters &&
          c->h_ptab && c->d_ptab;
 }
 static int batch_chain_persistent(odo_tracker_batch* b, BatchChain* c, hipStream_t s) {

@@ -3,10 +3,10 @@ tests/test_depth_cases_cpu.py, shows that each row reaches the branch it is in t
 
 Stage 1 (DisparityDepthEstimate) of every row against the oracle, bit for bit, and against the rows' closed forms. Stage 2 (the whole
 ComputeDepth) of every row with the persistent depth-LM launch against the same call on the step launches, bit for bit — an identity
-the project claims for any input, rows with no matched point or with all depths equal included. Stage 2 against the ORACLE is not asked
-of these rows: its accept / reject decisions depend on the summation order to within the 1e-7 / 1e-5 tolerances of
-tests/test_gpu_parity.py, and on tied inputs (costs of exactly 0, equal residuals everywhere) a decision may legitimately flip.
-The started-ahead and prepared entry points, and the batched kernels (TrackerBatch.init), on a few of the rows."""
+the project claims for any input, rows with no matched point or with all depths equal included. Stage 2 of these rows against an
+independent answer is tests/test_gpu_depth_lm_cases.py's: on every row each evaluation's error sum is one float whatever the order it is
+added in (tests/test_depth_lm_cases_cpu.py shows it), so no accept / reject decision can flip with the summation order, and both launches
+are held bit for bit to an exact-sum model that equals the oracle. The started-ahead and prepared entry points, and the batched kernels (TrackerBatch.init), on a few of the rows."""
 import ctypes as C
 import struct
 
