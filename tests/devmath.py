@@ -117,7 +117,9 @@ def mirror_layout():
 ENTRIES = ("dm_layout_count", "dm_layout", "dm_dense_fast_ok", "dm_level_k", "dm_sincos", "dm_se3_exp", "dm_se3_roundtrip", "dm_se3_left_update",
            "dm_solve_damped", "dm_robust_weight", "dm_apply_step", "dm_depth_schedule", "dm_lm_script", "dm_sincos_pair_wave",
            "dm_se3_exp_wave", "dm_solve_damped_wave", "dm_apply_step_wave", "dm_pixels", "dm_dense_pixels", "dm_div32", "dm_div64",
-           "dm_callsites", "dm_dense_runs", "dm_dense_eval", "dm_dense_eval_batch", "dm_tdist_scale")
+           "dm_callsites", "dm_dense_runs", "dm_dense_eval", "dm_dense_eval_batch", "dm_tdist_scale", "dm_make_points", "dm_kf_lists",
+           "dm_list_eval")
+MAX_LEVELS = 8                # ODO_MAX_LEVELS_K
 
 
 def _p(a):
@@ -138,7 +140,8 @@ def _f64(a):
 
 class Ops:
     """The cases of tests/devmath_ops.h on the host (device=False: tests/_build_hostemu.so) or on the GPU (device=True: one build of
-    the harness). Same methods, same array shapes."""
+    the harness). Same methods, same array shapes. Device only: the wave-wide and block-level forms, the dense scan, the scale
+    kernels, the keyframe point lists (kf_lists) and the kernels that read them (list_eval)."""
 
     def __init__(self, lib, device):
         self.lib, self.device = lib, device
@@ -247,7 +250,61 @@ class Ops:
             self.lib.emu_pixels(C.byref(L), int(mode), _p(hit), _p(r), _p(w), _p(J))
         return hit, r, w, J
 
+    def make_points(self, I1, D1, K, level):
+        """make_point of every pixel of a level, its intrinsics make_level_k(*K, level) with K = (f0, cx0, cy0): [rows, cols, 13] in the
+        order of a list entry (a: X Y Z i1, b: fx_z jw02 jw03 jw04, c: jw05 jw12 jw13 jw14, d: jw15)."""
+        I1, D1 = _f32(I1), _f32(D1)
+        rows, cols = I1.shape
+        out = np.zeros((rows, cols, 13), np.float32)
+        self._call("make_points", rows * cols, _p(I1), _p(D1), cols, C.c_float(K[0]), C.c_float(K[1]), C.c_float(K[2]), int(level), _p(out))
+        return out
+
     # -- device only --
+    def kf_lists(self, sets, K, dense_above=0, spare=3, by_ref=False):
+        """The keyframe point lists of `sets` = [[(I1, D1) of level 0, of level 1, ...], ...]: level shapes shared by the sets, contents
+        their own. by_ref False: kf_count_kernel + kf_fill_kernel as the product launches them, one pair per set; True: the by-reference
+        bodies over a table, one entry per set, in one pair of launches. Everything starts as 0xAB bytes and is built twice into the same
+        buffers. Per set: dict(rowcnt [2, rows_total + 1] int32, npts [2, 8] int32, lists = for each of the 8 levels [2, interior +
+        spare, 13] float32)."""
+        shapes = [np.shape(im) for im, _ in sets[0]]
+        assert all([np.shape(im) for im, _ in s] == shapes and all(np.shape(d) == np.shape(im) for im, d in s) for s in sets)
+        n_sets, n_levels = len(sets), len(shapes)
+        rows, cols = _i32([s[0] for s in shapes]), _i32([s[1] for s in shapes])
+        I1 = _f32(np.stack([np.concatenate([_f32(im).ravel() for im, _ in s]) for s in sets]))
+        D1 = _f32(np.stack([np.concatenate([_f32(d).ravel() for _, d in s]) for s in sets]))
+        inner = [(r - 8, c - 8) if r > 8 and c > 8 else (0, 0) for r, c in shapes] + [(0, 0)] * (MAX_LEVELS - n_levels)
+        cap = [ih * iw + spare for ih, iw in inner]
+        rt, ct = sum(ih for ih, _ in inner), sum(cap)
+        rowcnt, npts = np.zeros((2, n_sets, rt + 1), np.int32), np.zeros((2, n_sets, MAX_LEVELS), np.int32)
+        a, b, c = (np.zeros((2, n_sets, ct, 4), np.float32) for _ in range(3))
+        d = np.zeros((2, n_sets, ct, 1), np.float32)
+        rc = self.lib.dm_kf_lists(n_sets, int(bool(by_ref)), n_levels, _p(rows), _p(cols), _p(I1), _p(D1), C.c_float(K[0]), C.c_float(K[1]),
+                                  C.c_float(K[2]), int(dense_above), int(spare), _p(rowcnt), _p(npts), _p(a), _p(b), _p(c), _p(d))
+        assert rc == 0, "dm_kf_lists: HIP error %d" % rc
+        out = []
+        for i in range(n_sets):
+            lists, at = [], 0
+            for n in cap:
+                lists.append(np.concatenate([v[:, i, at:at + n] for v in (a, b, c, d)], axis=2))
+                at += n
+            out.append(dict(rowcnt=rowcnt[:, i], npts=npts[:, i], lists=lists))
+        return out
+
+    def list_eval(self, I1, I2, D1, k, T, nblk, n_cap, robust=1, huber_delta=28.0, scale_sqr=1.0, active=1, level_ok=1):
+        """The level's list built by kf_count_kernel / kf_fill_kernel, then lm_residual_only_list_kernel and lm_residual_list_kernel on
+        nblk blocks, twice, every launch into 0xAB bytes. Returns (n = the level's point count, partial rows [2, nblk + 1, 29], residuals
+        [2, n_cap]); n_cap >= n."""
+        I1, I2, D1 = _f32(I1), _f32(I2), _f32(D1)
+        rows, cols = I1.shape
+        L = PixLevel(I1.ctypes.data, I2.ctypes.data, D1.ctypes.data, rows, cols, LevelK(*k))
+        L.T[:] = [float(v) for v in _f32(np.asarray(T, np.float32).T).reshape(16)]
+        L.robust, L.huber_delta, L.scale_sqr = int(robust), float(huber_delta), float(scale_sqr)
+        found = np.full(1, -1, np.int32)
+        partials, res = np.zeros((2, nblk + 1, 29), np.float64), np.zeros((2, n_cap), np.float32)
+        rc = self.lib.dm_list_eval(C.byref(L), int(nblk), int(active), int(level_ok), int(n_cap), _p(found), _p(partials), _p(res))
+        assert rc == 0, "dm_list_eval: HIP error %d (the level's list holds %d points, room for %d)" % (rc, found[0], n_cap)
+        return int(found[0]), partials, res
+
     def _wave(self, name, n, *args):
         off = np.zeros(n, np.int32)
         self._call(name, n, *args, _p(off))

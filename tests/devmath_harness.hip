@@ -14,6 +14,11 @@
 // block by block with the grid cap chosen by the test, dense_block_run of every block, and the t-distribution scale kernels over a
 // residual vector (dm_tdist_scale). The only waiting among them is lm_tdist_scale_multi_kernel's own bounded exchange (4 ms a wait),
 // launched exactly as lm_launch_scale launches it, with its fall-back queued behind it.
+//
+// For tests/test_gpu_kf_list_cases.py: make_point per pixel (dm_make_points), kf_count_kernel + kf_fill_kernel over levels of any
+// shapes as lm_enqueue_lists launches them, and the by-reference instantiation of their bodies from a table (dm_kf_lists), and
+// lm_residual_only_list_kernel / lm_residual_list_kernel on a list those kernels built (dm_list_eval). Every output buffer starts as
+// 0xAB bytes and has spare room behind what may be written.
 #include <hip/hip_runtime.h>
 #define ODO_LM_CHAIN_TU 1
 #define ODO_DENSE_KERNELS 1
@@ -50,6 +55,14 @@ struct Pool {
   template <class T> T* zeros(size_t count) {
     T* p = (T*)raw(count * sizeof(T));
     if (p) err = hipMemset(p, 0, count ? count * sizeof(T) : 4);
+    return p;
+  }
+  template <class T> void fill(T* dev, size_t count) {   // every byte 0xAB: what a kernel did not write shows
+    if (dev && err == hipSuccess) err = hipMemset(dev, 0xAB, count ? count * sizeof(T) : 4);
+  }
+  template <class T> T* filled(size_t count) {
+    T* p = (T*)raw(count * sizeof(T));
+    fill(p, count);
     return p;
   }
   template <class T> void down(T* host, const T* dev, size_t count) {
@@ -259,6 +272,27 @@ __global__ void __launch_bounds__(64) dense_state_kernel(LmState* __restrict__ s
                                                          int level) {
   for (int i = (int)threadIdx.x; i < n * 16; i += 64) st[i / 16].T[i % 16] = T[i];
   for (int i = (int)threadIdx.x; i < n; i += 64) { st[i].active = active[i]; st[i].level = level; }
+}
+
+// ---- the keyframe point lists from a table in global memory ------------------------------------------------------------------------
+// The `const KfLevels&` instantiation of both bodies, shaped like kf_count_batch_kernel / kf_fill_batch_kernel (batch.hip.h): one table
+// entry per blockIdx.y. (The product's batch launch passes no dense_above; here it is an argument, so that every case can be compared
+// with its by-value launch.)
+struct KfTab {
+  KfLevels kl;
+  int* rowcnt;
+  int* npts;
+  PointList pl[ODO_MAX_LEVELS_K];
+};
+__global__ void __launch_bounds__(256) kf_count_ref_kernel(const KfTab* __restrict__ tab) {
+  const KfTab& q = tab[blockIdx.y];
+  if (blockIdx.x == 0 && threadIdx.x < ODO_MAX_LEVELS_K) q.npts[threadIdx.x] = 0;
+  kf_count_kernel_body<const KfLevels&>(q.kl, q.rowcnt);
+}
+__global__ void __launch_bounds__(256) kf_fill_ref_kernel(const KfTab* __restrict__ tab, float f0, float cx0, float cy0, int dense_above) {
+  const KfTab& q = tab[blockIdx.y];
+  const int l = kf_find_level(q.kl, blockIdx.x);
+  kf_fill_kernel_body<const KfLevels&>(q.kl, l, q.pl[l], f0, cx0, cy0, q.rowcnt, q.npts, dense_above);
 }
 
 // ---- the shared-reciprocal divisions against the plain `/` of the same unit -------------------------------------------------------
@@ -669,6 +703,149 @@ int dm_tdist_scale(const float* res, int n, int order, int reps, float* scale_sq
       o[2] = o[1] ? (plan.single_order ? 0 : 1) : 2;
     }
     P.down(scale_sqr + r, dscale, 1);
+  }
+  return P.done();
+}
+
+// ---- the keyframe point lists ----
+int dm_make_points(int n, const float* I1, const float* D1, int cols, float f0, float cx0, float cy0, int level, float* out13) {
+  if (cols < 1 || level < 0 || level >= ODO_MAX_LEVELS_K) return (int)hipErrorInvalidValue;
+  Pool P;
+  const float *dI = P.up(I1, n), *dD = P.up(D1, n);
+  float* dout = P.zeros<float>(13 * (size_t)n);
+  DM_EACH(P, n, [=] __device__(int i) { dm::op_make_point(i, dI, dD, cols, f0, cx0, cy0, level, dout); });
+  P.down(out13, dout, 13 * (size_t)n);
+  return P.done();
+}
+// The buffers of one list build, laid out as lm_lists_layout lays them out: levels[l] = rows x cols floats of I1 and of D1 at pixel
+// offset sum(rows cols) of the levels before it (levels need not be a pyramid). Every level 0 .. ODO_MAX_LEVELS_K - 1 gets a list
+// of (its interior + spare) entries, rowcnt has one spare entry; all of it, and npts, starts as 0xAB bytes.
+struct KfSet {
+  KfLevels kl;
+  int rows_total;
+  int *rowcnt, *npts;
+  PointList pl[ODO_MAX_LEVELS_K];
+  size_t cap[ODO_MAX_LEVELS_K], cap_total;
+};
+static bool kf_device_set(Pool& P, int n_levels, const int* rows, const int* cols, const float* I1, const float* D1, int spare, KfSet* S) {
+  if (n_levels < 1 || n_levels > ODO_MAX_LEVELS_K || spare < 0 || spare > 4096) return false;
+  memset(S, 0, sizeof(*S));
+  size_t npx = 0;
+  for (int l = 0; l < n_levels; l++) {
+    if (rows[l] < 1 || cols[l] < 1 || rows[l] > 65535 || cols[l] > 65535) return false;
+    npx += (size_t)rows[l] * cols[l];
+  }
+  const float *dI = P.up(I1, npx), *dD = P.up(D1, npx);
+  KfLevels& kl = S->kl;
+  kl.n_levels = n_levels;
+  size_t off = 0;
+  int rows_total = 0;
+  for (int l = 0; l < ODO_MAX_LEVELS_K; l++) {
+    size_t interior = 0;
+    if (l < n_levels) {
+      kl.I1[l] = dI + off; kl.D1[l] = dD + off;
+      kl.rows[l] = rows[l]; kl.cols[l] = cols[l];
+      kl.row_base[l] = rows_total;
+      const int ir = rows[l] - 8, ic = cols[l] - 8;
+      rows_total += (ir > 0 && ic > 0) ? ir : 0;
+      interior = (ir > 0 && ic > 0) ? (size_t)ir * ic : 0;
+      off += (size_t)rows[l] * cols[l];
+    }
+    S->cap[l] = interior + (size_t)spare;
+    S->cap_total += S->cap[l];
+    S->pl[l].a = P.filled<float4>(S->cap[l]); S->pl[l].b = P.filled<float4>(S->cap[l]);
+    S->pl[l].c = P.filled<float4>(S->cap[l]); S->pl[l].d = P.filled<float>(S->cap[l]);
+  }
+  for (int l = n_levels; l <= ODO_MAX_LEVELS_K; l++) kl.row_base[l] = rows_total;
+  S->rows_total = rows_total;
+  S->rowcnt = P.filled<int>((size_t)rows_total + 1);
+  S->npts = P.filled<int>(ODO_MAX_LEVELS_K);
+  return rows_total > 0;
+}
+static void kf_launch_by_value(Pool& P, const KfSet& S, float f0, float cx0, float cy0, int dense_above) {   // lm_enqueue_lists' pair
+  DM_LAUNCH(P, kf_count_kernel<0>, S.rows_total, 256, S.kl, S.rowcnt, S.npts);
+  DM_LAUNCH(P, kf_fill_kernel<0>, S.rows_total, 256, S.kl, f0, cx0, cy0, (const int*)S.rowcnt, S.npts, S.pl[0], S.pl[1], S.pl[2], S.pl[3],
+            S.pl[4], S.pl[5], S.pl[6], S.pl[7], dense_above);
+}
+// n_sets list builds of the same level shapes with contents of their own (I1 / D1: n_sets x sum(rows cols)), twice in a row into the
+// same buffers. form 0: kf_count_kernel + kf_fill_kernel as lm_enqueue_lists launches them (rows_total blocks of 256), one pair per
+// set; form 1: the by-reference bodies over a table of n_sets entries, grid (rows_total, n_sets). Outputs, [run 2][set n_sets][...]:
+// rowcnt rows_total + 1, npts ODO_MAX_LEVELS_K, a / b / c 4 x cap_total floats and d cap_total floats, level l's entries at offset
+// sum of (interior + spare) of the levels before it.
+int dm_kf_lists(int n_sets, int form, int n_levels, const int* rows, const int* cols, const float* I1, const float* D1, float f0, float cx0,
+                float cy0, int dense_above, int spare, int* rowcnt, int* npts, float* a, float* b, float* c, float* d) {
+  if (n_sets < 1 || n_sets > 4 || form < 0 || form > 1) return (int)hipErrorInvalidValue;
+  Pool P;
+  std::vector<KfSet> S((size_t)n_sets);
+  size_t npx = 0;
+  for (int l = 0; l < n_levels && l < ODO_MAX_LEVELS_K; l++) npx += (size_t)(rows[l] > 0 ? rows[l] : 0) * (cols[l] > 0 ? cols[l] : 0);
+  for (int i = 0; i < n_sets; i++)
+    if (!kf_device_set(P, n_levels, rows, cols, I1 + npx * i, D1 + npx * i, spare, &S[i])) return (int)hipErrorInvalidValue;
+  const KfTab* dtab = nullptr;
+  if (form == 1) {
+    std::vector<KfTab> tab((size_t)n_sets);
+    for (int i = 0; i < n_sets; i++) {
+      memset(&tab[i], 0, sizeof(KfTab));
+      tab[i].kl = S[i].kl; tab[i].rowcnt = S[i].rowcnt; tab[i].npts = S[i].npts;
+      for (int l = 0; l < ODO_MAX_LEVELS_K; l++) tab[i].pl[l] = S[i].pl[l];
+    }
+    dtab = P.up(tab.data(), (size_t)n_sets);
+  }
+  const int rt = S[0].rows_total;
+  const size_t ct = S[0].cap_total;
+  for (int run = 0; run < 2; run++) {
+    if (form == 1) {
+      DM_LAUNCH(P, kf_count_ref_kernel, dim3((unsigned)rt, (unsigned)n_sets), 256, dtab);
+      DM_LAUNCH(P, kf_fill_ref_kernel, dim3((unsigned)rt, (unsigned)n_sets), 256, dtab, f0, cx0, cy0, dense_above);
+    } else {
+      for (int i = 0; i < n_sets; i++) kf_launch_by_value(P, S[i], f0, cx0, cy0, dense_above);
+    }
+    for (int i = 0; i < n_sets; i++) {
+      const size_t s = (size_t)run * n_sets + i;
+      P.down(rowcnt + s * ((size_t)rt + 1), S[i].rowcnt, (size_t)rt + 1);
+      P.down(npts + s * ODO_MAX_LEVELS_K, S[i].npts, ODO_MAX_LEVELS_K);
+      size_t at = 0;
+      for (int l = 0; l < ODO_MAX_LEVELS_K; l++) {
+        const size_t n = S[i].cap[l];
+        P.down(a + 4 * (s * ct + at), (const float*)S[i].pl[l].a, 4 * n); P.down(b + 4 * (s * ct + at), (const float*)S[i].pl[l].b, 4 * n);
+        P.down(c + 4 * (s * ct + at), (const float*)S[i].pl[l].c, 4 * n); P.down(d + (s * ct + at), (const float*)S[i].pl[l].d, n);
+        at += n;
+      }
+    }
+  }
+  return P.done();
+}
+// What reads a list: the level's list built by the two kernels above (one level, level 0: its intrinsics are make_level_k(fl, cx, cy,
+// 0)), then lm_residual_only_list_kernel and lm_residual_list_kernel launched as lm_launch_eval launches them — nblk blocks of
+// kLmBlock over the n points kf_fill_kernel counted — on a state with `active` at pose L->T, twice. level_ok = 0: the launches'
+// expect_level is not the state's level. found[0] = n. partials: [2][nblk + 1][29], res: [2][n_cap]; both start every launch as 0xAB
+// bytes.
+int dm_list_eval(const dm::PixLevel* L, int nblk, int active, int level_ok, int n_cap, int* found, double* partials, float* res) {
+  const float f0 = (float)L->k.fl;
+  if ((double)f0 != L->k.fl || nblk < 1 || nblk > 4096 || n_cap < 1) return (int)hipErrorInvalidValue;
+  Pool P;
+  KfSet S;
+  if (!kf_device_set(P, 1, &L->rows, &L->cols, L->I1, L->D1, 1, &S)) return (int)hipErrorInvalidValue;
+  kf_launch_by_value(P, S, f0, L->k.cx, L->k.cy, 0);
+  int n = -1;
+  P.down(&n, S.npts, 1);
+  found[0] = n;
+  if (P.err != hipSuccess || n < 0 || n > n_cap || (size_t)n + 1 > S.cap[0]) { const int e = P.done(); return e ? e : (int)hipErrorInvalidValue; }
+  LevelK k = make_level_k(f0, L->k.cx, L->k.cy, 0);
+  k.bilinear = L->k.bilinear;
+  const float* dI2 = P.up(L->I2, (size_t)L->rows * L->cols);
+  const LmState* st = dense_device_states(P, 1, L->T, &active);
+  const float* dscale = P.up(&L->scale_sqr, 1);
+  const size_t np = ODO_NACC * ((size_t)nblk + 1);
+  double* dp = P.filled<double>(np);
+  float* dres = P.filled<float>((size_t)n_cap);
+  const int expect = level_ok ? kDmExpectLevel : kDmExpectLevel + 1;
+  for (int run = 0; run < 2; run++) {
+    P.fill(dp, np); P.fill(dres, (size_t)n_cap);
+    DM_LAUNCH(P, lm_residual_only_list_kernel<0>, nblk, kLmBlock, S.pl[0], n, dI2, L->rows, L->cols, k, st, expect, dres);
+    DM_LAUNCH(P, lm_residual_list_kernel<0>, nblk, kLmBlock, S.pl[0], n, dI2, L->rows, L->cols, k, st, expect, L->robust, L->huber_delta, dscale,
+              dp);
+    P.down(partials + run * np, dp, np); P.down(res + (size_t)run * n_cap, dres, (size_t)n_cap);
   }
   return P.done();
 }

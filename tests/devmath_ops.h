@@ -161,4 +161,17 @@ ODO_HD void op_pixel(const PixLevel& L, int mode, int x, int y, int* hit_out, fl
   pix_store(L, o, hit, r, J, hit_out, r_out, w_out, J_out);
 }
 
+// make_point of pixel i of a level (x = i % cols, y = i / cols; every pixel, whatever its depth), the level's intrinsics from
+// make_level_k as kf_fill_kernel_body derives them: the thirteen floats of a list entry in PointList's order — a = X, Y, Z, i1;
+// b = fx_z, jw02, jw03, jw04; c = jw05, jw12, jw13, jw14; d = jw15.
+ODO_HD void op_make_point(int i, const float* I1, const float* D1, int cols, float f0, float cx0, float cy0, int level, float* out13) {
+  const LevelK k = make_level_k(f0, cx0, cy0, level);
+  const PointK p = make_point(i % cols, i / cols, D1[i], I1[i], k);
+  float* o = out13 + (size_t)i * 13;
+  o[0] = p.X; o[1] = p.Y; o[2] = p.Z; o[3] = p.i1;
+  o[4] = p.fx_z; o[5] = p.jw02; o[6] = p.jw03; o[7] = p.jw04;
+  o[8] = p.jw05; o[9] = p.jw12; o[10] = p.jw13; o[11] = p.jw14;
+  o[12] = p.jw15;
+}
+
 }  // namespace dm

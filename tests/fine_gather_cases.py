@@ -8,6 +8,12 @@ test chooses the block count. ODO_COARSE_MAX and ODO_HOME_XCD are read once per 
 
 runs one Solve per N and weight mode (Huber 1, L2 0, t-distribution 2) on the persistent launch and one with ODO_LM_NO_FINE=1
 (step launches), and writes poses, statuses, evaluation counts, point counts and persistent-launch statistics to OUT.npz.
+
+    python tests/fine_gather_cases.py OUT.npz --under coarse:ODO_LM_NO_FINE=1 --base step:ODO_LM_NO_FINE=1,ODO_LM_NO_COARSE=1 --trace N ...
+
+chooses the two environments itself — the launch under test and its baseline, here the one-workgroup coarse launch (which, with
+ODO_COARSE_MAX unset and no persistent launch, takes levels of up to kCoarseMaxPoints points) against the step launches — and with
+--trace also writes every trace row of both (tests/test_gpu_coarse_rounds.py).
 """
 import os
 import sys
@@ -41,7 +47,20 @@ def frames(n_points):
     return img0, inv, img1
 
 
-def main(out, counts):
+PATHS = (("fine", {}), ("step", {"ODO_LM_NO_FINE": "1"}))     # (name, environment of the optimiser): the launch under test, the baseline
+TRACE_INT = ("level", "iter", "n_res", "accepted", "stop")
+
+
+def parse_path(arg):
+    """NAME:KEY=VALUE,KEY=VALUE -> (name, environment); the variables are set while that path's optimiser is created (the library
+    reads ODO_LM_NO_FINE and ODO_LM_NO_COARSE per optimiser)."""
+    name, _, rest = arg.partition(":")
+    return name, dict(kv.split("=", 1) for kv in rest.split(",") if kv)
+
+
+def main(out, counts, paths=PATHS, trace=False):
+    """trace: the optimisers record (set_record), and every trace row is written out as well: `_trace_i` [rows, 5] (TRACE_INT) and
+    `_trace_f` [rows, 8] float64 (err, lambda_after, delta[6]); `_launches`: the launches of the Solve."""
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from odometry_amd import api
     api.default_context()
@@ -50,21 +69,36 @@ def main(out, counts):
         img0, inv, img1 = frames(n)
         p0, d0, p1 = api.ImagePyramid(1, img0, False), api.DepthPyramid(1, inv, False), api.ImagePyramid(1, img1, False)
         for mode in MODES:
-            for path in ("fine", "step"):
-                if path == "step":
-                    os.environ["ODO_LM_NO_FINE"] = "1"
+            for path, env in paths:
+                os.environ.update(env)
                 lm = api.LevenbergMarquardtOptimizer(0.01, 0.995, ITERS, np.eye(4), None, mode, 28.0,
                                                      intrinsics=(K["f0"], K["cx0"], K["cy0"]))
+                if trace:
+                    lm.set_record(True)
                 T = lm.Solve(p0, d0, p1)
                 key = f"{n}_{mode}_{path}"
                 res[key + "_pose"] = np.asarray(T, np.float32)
                 res[key + "_meta"] = np.array([lm.last_status, lm.launch_stats()[0], lm.points()[0][0], *lm.persistent_stats()], np.int64)
+                res[key + "_launches"] = np.array([lm.launch_stats()[1]], np.int64)
+                if trace:
+                    rows = lm.trace()
+                    res[key + "_trace_i"] = np.array([[r[f] for f in TRACE_INT] for r in rows], np.int64).reshape(-1, len(TRACE_INT))
+                    res[key + "_trace_f"] = np.array([[r["err"], r["lambda_after"], *r["delta"]] for r in rows], np.float64).reshape(-1, 8)
                 lm.close()
-                os.environ.pop("ODO_LM_NO_FINE", None)
+                for k in env:
+                    os.environ.pop(k, None)
         for o in (p0, d0, p1):
             o.close()
     np.savez(out, **res)
 
 
 if __name__ == "__main__":
-    main(sys.argv[1], [int(a) for a in sys.argv[2:]])
+    args = sys.argv[2:]
+    opts = {"paths": list(PATHS), "trace": False}
+    while args and args[0].startswith("--"):
+        flag = args.pop(0)
+        if flag == "--trace":
+            opts["trace"] = True
+        else:
+            opts["paths"][{"--under": 0, "--base": 1}[flag]] = parse_path(args.pop(0))
+    main(sys.argv[1], [int(a) for a in args], tuple(opts["paths"]), opts["trace"])

@@ -152,6 +152,10 @@ void emu_pixels(const dm::PixLevel* L, int mode, int* hit, float* r, float* w, f
   for (int y = 4; y < L->rows - 4; y++)
     for (int x = 4; x < L->cols - 4; x++) dm::op_pixel(*L, mode, x, y, hit, r, w, J);
 }
+// make_point of every pixel of a level: what kf_fill_kernel_body stores for the valid interior ones (tests/kf_list_cases.py).
+void emu_make_points_n(int n, const float* I1, const float* D1, int cols, float f0, float cx0, float cy0, int level, float* out13) {
+  for (int i = 0; i < n; i++) dm::op_make_point(i, I1, D1, cols, f0, cx0, cy0, level, out13);
+}
 int emu_sizeof_lm_state() { return (int)sizeof(LmState); }
 int emu_sizeof_lm_script() { return (int)sizeof(dm::LmScript); }
 int emu_sizeof_pix_level() { return (int)sizeof(dm::PixLevel); }

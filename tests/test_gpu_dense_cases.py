@@ -184,12 +184,13 @@ def test_tdist_scale_equals_model(dev, n, kind):
 
 
 # ---- through the public API, with the product's own cap ---------------------------------------------------------------------------
-def _api_level_check(O, api, rows, cols, levels, mode, robusts, what):
+def _api_level_check(O, api, rows, cols, levels, mode, robusts, what, inputs=None, prime=None, after=None):
     """lm.accumulate on every level against the oracle's accumulation: status and N exact; for L2 and Huber weights every sum within
     the any-order bound of the exact sum of accumulate_row's products over the oracle's dumped r, w, J; for t-distribution weights
     (sigma enters every weight) rtol 1e-11, atol 1e-9 against the oracle's sums, which a 1-ulp error of sigma cannot pass.
-    Returns the largest error / bound."""
-    I1, I2, inv, K, T = Dc.api_inputs(rows, cols)
+    Returns the largest error / bound. inputs: (I1, I2, inverse depth, K, T) in place of Dc.api_inputs(rows, cols); prime(lm) /
+    after(lm): called on every optimiser before its first and after its last accumulation (tests/test_gpu_kf_list_cases.py)."""
+    I1, I2, inv, K, T = inputs or Dc.api_inputs(rows, cols)
     KD = dict(f0=K[0], cx0=K[1], cy0=K[2])
     p0, d0, p1 = api.ImagePyramid(levels, I1, False), api.DepthPyramid(levels, inv, False), api.ImagePyramid(levels, I2, False)
     i0, i1, dd = O.image_pyramid(I1, levels, False), O.image_pyramid(I2, levels, False), O.depth_pyramid(inv, levels)
@@ -198,6 +199,8 @@ def _api_level_check(O, api, rows, cols, levels, mode, robusts, what):
         for robust in robusts:
             lm = api.LevenbergMarquardtOptimizer(0.01, 0.995, [10] * levels, np.eye(4), None, robust, HUBER, intrinsics=K)
             lm.set_mode(mode)
+            if prime:
+                prime(lm)
             for level in range(levels):
                 w = "%s, level %d, robust %d" % (what, level, robust)
                 st, acc = lm.accumulate(p0, d0, p1, level, T)
@@ -217,6 +220,8 @@ def _api_level_check(O, api, rows, cols, levels, mode, robusts, what):
                     assert err <= bound, "%s, sum %d: %r against %r, bound %r" % (w, q, acc[q], exact, bound)
                     if bound > 0:
                         worst = max(worst, err / bound)
+            if after:
+                after(lm)
             lm.close()
     finally:
         for o in (p0, d0, p1):

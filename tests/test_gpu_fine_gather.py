@@ -32,11 +32,12 @@ S = _solo_rows()
 COUNTS = [n for n in sorted({1, 255, 256, 257, 1024, 1025, 2048, 2049, 256 * S, 256 * S + 1}) if n <= cases.INTERIOR]
 
 
-def _child(tmp, name, counts, env):
+def _child(tmp, name, counts, env, options=()):
     out = os.path.join(str(tmp), name + ".npz")
-    e = {k: v for k, v in os.environ.items() if k not in ("ODO_HOME_XCD", "ODO_NO_HOME_XCD", "ODO_LM_NO_FINE", "ODO_LM_FINE_K")}
+    e = {k: v for k, v in os.environ.items() if k not in ("ODO_HOME_XCD", "ODO_NO_HOME_XCD", "ODO_LM_NO_FINE", "ODO_LM_FINE_K",
+                                                          "ODO_LM_NO_COARSE", "ODO_COARSE_MAX")}
     e.update(env)
-    subprocess.run([sys.executable, os.path.join(ROOT, "tests", "fine_gather_cases.py"), out] + [str(n) for n in counts],
+    subprocess.run([sys.executable, os.path.join(ROOT, "tests", "fine_gather_cases.py"), out] + list(options) + [str(n) for n in counts],
                    check=True, env=e, timeout=300)
     return np.load(out)
 
