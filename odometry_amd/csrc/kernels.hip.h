@@ -583,10 +583,21 @@ __device__ __forceinline__ float ldg_f32(const float* base_uniform, unsigned byt
   typedef __attribute__((address_space(1))) const float GlobalFloat;
   return *(GlobalFloat*)((GlobalBytes*)base_uniform + byte_off);
 }
+// Branch-free: everything up to the taps is computed for every lane, ONE predicate (`have` = the lane holds a point at all, then the
+// tests of odo::warp_point in their comparisons, so that a NaN fails them) selects the sampled pixel to (0, 0) — every lane loads in
+// bounds, and no conversion of a NaN or of a coordinate beyond the int range ever feeds an address — and r and J to +0.0f: what
+// rows_store_z expects of a point without a residual. As nested returns this was a four-deep s_and_saveexec nest on the single
+// latency-bound wave: nine v_mov of dead zeros, an exec save / restore and a branch per level, and v's six dependent fp64 operations
+// not started before u's range test had been taken. A lane without a point computes on its zero-initialised registers.
 template <bool kMayBilinear>
 __device__ __forceinline__ bool point_residual_g(const PointK& p, const float* T, const LevelK& k, const float* I2_uniform, int rows,
-                                                 int cols, float* r, float J[6]) {
-  if (kMayBilinear && k.bilinear) return point_residual<true>(p, T, k, I2_uniform, rows, cols, r, J);
+                                                 int cols, float* r, float J[6], bool have = true) {
+  if (kMayBilinear && k.bilinear) {
+    *r = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 6; i++) J[i] = 0.0f;
+    return have && point_residual<true>(p, T, k, I2_uniform, rows, cols, r, J);
+  }
   // odo::warp_point (ref: include/image_processing_global.h:42-59) with ONE fp64 reciprocal for both image coordinates (dense.hip.h,
   // "Shared-reciprocal division": 13 fp64 operations instead of 22). u = float(fl * double(t0) / double(t2) + double(cx)): the
   // operands are floats, so as doubles they are normal, every quotient stays inside the double range, v_div_scale rescales nothing
@@ -595,13 +606,12 @@ __device__ __forceinline__ bool point_residual_g(const PointK& p, const float* T
   const float t0 = ((T[0] * p.X + T[4] * p.Y) + T[8] * p.Z) + T[12];
   const float t1 = ((T[1] * p.X + T[5] * p.Y) + T[9] * p.Z) + T[13];
   const float t2 = ((T[2] * p.X + T[6] * p.Y) + T[10] * p.Z) + T[14];
-  if (!(t2 > 0.0f)) return false;
   const double t2d = (double)t2, y = rcp_refined_d(t2d);
   const float u = (float)(div_shared_d(k.fl * (double)t0, t2d, y) + (double)k.cx);
   const float v = (float)(div_shared_d(k.fl * (double)t1, t2d, y) + (double)k.cy);
   const float fu = floorf(u), fv = floorf(v);
-  if (!(fu < (float)cols) || !(fv < (float)rows) || !(fu >= 0.0f) || !(fv >= 0.0f)) return false;
-  const int ui = (int)fu, vi = (int)fv;
+  const bool ok = have & (t2 > 0.0f) & (fu < (float)cols) & (fv < (float)rows) & (fu >= 0.0f) & (fv >= 0.0f);
+  const int ui = (int)(ok ? fu : 0.0f), vi = (int)(ok ? fv : 0.0f);
   // (ref: lm_optimizer.cpp:215-217, image_processing_global.h:62-69 — odo::residual_jacobian's taps)
   const int px = (ui - 1 >= 0) ? ui - 1 : 0, nx = (ui + 1 < cols) ? ui + 1 : cols - 1;
   const int py = (vi - 1 >= 0) ? vi - 1 : 0, ny = (vi + 1 < rows) ? vi + 1 : rows - 1;
@@ -613,14 +623,14 @@ __device__ __forceinline__ bool point_residual_g(const PointK& p, const float* T
   // lm_optimizer.cpp:235, jw(1,0) = jw(0,1) = 0): for finite gradients the sum with a signed zero can only turn a -0 into a +0, and a
   // zero entry of J reaches the sums as a zero addend of accumulators that start at +0 — every sum is the same bit pattern.
   const float gx = 0.5f * (tr - tl), gy = 0.5f * (td - tu);
-  *r = tc - p.i1;
-  J[0] = gx * p.fx_z;
-  J[1] = gy * p.fx_z;
-  J[2] = gx * p.jw02 + gy * p.jw12;
-  J[3] = gx * p.jw03 + gy * p.jw13;
-  J[4] = gx * p.jw04 + gy * p.jw14;
-  J[5] = gx * p.jw05 + gy * p.jw15;
-  return true;
+  *r = ok ? tc - p.i1 : 0.0f;
+  J[0] = ok ? gx * p.fx_z : 0.0f;
+  J[1] = ok ? gy * p.fx_z : 0.0f;
+  J[2] = ok ? gx * p.jw02 + gy * p.jw12 : 0.0f;
+  J[3] = ok ? gx * p.jw03 + gy * p.jw13 : 0.0f;
+  J[4] = ok ? gx * p.jw04 + gy * p.jw14 : 0.0f;
+  J[5] = ok ? gx * p.jw05 + gy * p.jw15 : 0.0f;
+  return ok;
 }
 
 // Residual / Jacobian / normal-equation pass over a keyframe point list (semi-dense levels): one point per thread
@@ -1901,7 +1911,7 @@ __device__ __forceinline__ void lm_coarse_body(const StepArgs& a, const StepLaun
   if (my_q < ODO_NACC) rows_of_quantity(my_q, &rowA, &rowB);
   // the keyframe points of the level stay in registers from iteration to iteration (as in lm_fine_body): one dependent trip to L2 / L1
   // less in every evaluation of a level that is a latency chain of ~200 points on four waves
-  PointK cpt[kCoarseRounds];
+  PointK cpt[kCoarseRounds] = {};   // (zero: a lane without a point computes on defined values, point_residual_g)
   bool cpt_ok[kCoarseRounds] = {false, false};
   int cpt_level = -1;
   for (int guard = 0; guard < 4096; guard++) {
@@ -1951,11 +1961,9 @@ __device__ __forceinline__ void lm_coarse_body(const StepArgs& a, const StepLaun
 #pragma unroll
         for (int i = 0; i < 6; i++) J[i] = td_J[vb0 / 2][i];
         if (valid) w = robust_weight(r, 2, a.huber_delta, td_scale_sqr);
-      } else if (cpt_ok[vb0 / 2]) {
-        if (point_residual_g<kFull>(cpt[vb0 / 2], T, L.k, I2u, L.rows, L.cols, &r, J)) {
-          w = robust_weight(r, kFull ? a.robust : (a.robust == 1 ? 1 : 0), a.huber_delta, 1.0f);
-          valid = true;
-        }
+      } else {
+        valid = point_residual_g<kFull>(cpt[vb0 / 2], T, L.k, I2u, L.rows, L.cols, &r, J, cpt_ok[vb0 / 2]);
+        w = valid ? robust_weight(r, kFull ? a.robust : (a.robust == 1 ? 1 : 0), a.huber_delta, 1.0f) : 0.0f;
       }
       if (vb0 > 0) __syncthreads();  // the previous round's rows have been consumed
       rows_store_z(rows_sh, RowBuf<kLmBlock>::W, tl, J, w, r, valid);
@@ -2012,7 +2020,11 @@ __device__ __forceinline__ void lm_coarse_body(const StepArgs& a, const StepLaun
   const unsigned long long w_loop_end = (unsigned long long)wall_clock64();
 #endif
   if (threadIdx.x == 0) lm_hot_store(hot, s_sh);   // (read back by wave 0 only, below: a wave's LDS accesses stay in order)
-  lm_fused_publish(s_sh, q.st_out, a.host_prog, q.seq, a.token, a.cost_stat, a.out, a.done_flag, a.final_state, chain_out_of(a));
+  // (the chain hand-over's fields through the pointer the level table came by, read HERE: as fields of `a` they were kernel-argument
+  //  loads issued at entry and merged with lm_chain_skip's word into one eight-dword load, which then lived across the whole loop and
+  //  was given a spill slot as a tuple — lm_coarse_kernel carried a 36-byte private segment that no instruction of it touched, and
+  //  every dispatch of it asked for the scratch set-up; the armed build, which does not look at the guard, had none)
+  lm_fused_publish(s_sh, q.st_out, a.host_prog, q.seq, a.token, a.cost_stat, a.out, a.done_flag, a.final_state, chain_out_of(*(const StepArgs*)lv_src));
 #if ODO_PHASE_STAMPS
   if (ODO_DBG(a) && threadIdx.x == 0) {
     const unsigned long long now = (unsigned long long)wall_clock64();
@@ -2432,7 +2444,7 @@ __device__ __forceinline__ void lm_fine_body(const StepArgs& a, const StepLaunch
   int rowA = 0, rowB = 0;
   if (my_q < ODO_NACC) rows_of_quantity(my_q, &rowA, &rowB);
   const int fq = t & 31, fseg = t >> 5;  // the fold's thread map (segments 0..7 fold: the first half of the workgroup)
-  PointK pt;
+  PointK pt = {};               // (zero: a lane without a point computes on defined values, point_residual_g)
   bool pt_ok = false;
   int pt_level = -1;
   unsigned long long c_eval = 0, c_xchg = 0, c_sm = 0, c_it = 0, c_last = ODO_DBG(a) ? __builtin_readcyclecounter() : 0;
@@ -2469,12 +2481,9 @@ __device__ __forceinline__ void lm_fine_body(const StepArgs& a, const StepLaunch
         pt_ok = vb < nblk && idx < L.n;
         if (pt_ok) pt = load_point(L.pl, idx);
       }
-      float r = 0.0f, wgt = 0.0f, J[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-      bool valid = false;
-      if (pt_ok && point_residual_g<kTdist || kTrace>(pt, T, L.k, I2u, L.rows, L.cols, &r, J)) {
-        wgt = robust_weight(r, (kTdist || kTrace) ? a.robust : (a.robust == 1 ? 1 : 0), a.huber_delta, 1.0f);
-        valid = true;
-      }
+      float r, J[6];
+      const bool valid = point_residual_g<kTdist || kTrace>(pt, T, L.k, I2u, L.rows, L.cols, &r, J, pt_ok);
+      float wgt = valid ? robust_weight(r, (kTdist || kTrace) ? a.robust : (a.robust == 1 ? 1 : 0), a.huber_delta, 1.0f) : 0.0f;
       if (kTdist && w < nblk) {   // (workgroup-uniform: the scale passes hold workgroup barriers; a half without a virtual block adds zeros)
         // t-distribution weights need the scale of ALL residuals of this evaluation first (ref: src/lm_optimizer.cpp:257-261)
         __shared__ double td_ws_sh[2][8];
