@@ -39,6 +39,16 @@ namespace odo {
 
 constexpr int kWave = 64;
 #define ODO_MAX_LEVELS_K 8
+// The chain kernels run one evaluation loop per launch on a lone wave: lane masks that depend on the lane id alone are hoisted out
+// of that loop into scalar pairs and, in lm_fine_kernel, spilled and read back lane by lane in every evaluation. Where this is
+// true such a mask is one compare on a per-lane register behind an empty asm (solve_damped_wave_regs, sincos_pair_lanes,
+// lm_fine_body). The main unit's builds of the same functions (the step launches, the batched kernels) keep the masks: measured,
+// the batched tracker at S = 4 and S = 8 is slower with the registers (profiles/state_machine_uniform_ab.md, section 6).
+#ifdef ODO_LM_CHAIN_TU
+constexpr bool kChainLaneRegs = true;
+#else
+constexpr bool kChainLaneRegs = false;
+#endif
 
 __device__ __forceinline__ int reflect101(int i, int n) {
   if (n == 1) return 0;
@@ -720,14 +730,35 @@ __device__ __forceinline__ double readlane_d(double v, int src_lane) {  // src_l
   return __hiloint2double(hi, lo);
 }
 
+__device__ __forceinline__ double bpermute_d(double v, int src_byte) {  // v of lane src_byte / 4 (0 .. 63), what __shfl(v, lane, 64) gives
+  const int lo = __builtin_amdgcn_ds_bpermute(src_byte, __double2loint(v));
+  const int hi = __builtin_amdgcn_ds_bpermute(src_byte, __double2hiint(v));
+  return __hiloint2double(hi, lo);
+}
+
 __device__ __forceinline__ void solve_damped_wave_regs(const double* acc, float lambda, float delta_out[6]) {
   const int lane = threadIdx.x & 63;
   const int i = lane >> 3, j = lane & 7;
   const bool in = (i < 6 && j < 7);
+  // What this lane holds — 0: nothing, 1: an off-diagonal entry, 2: a diagonal entry, 3: the right-hand side — in ONE register behind
+  // an empty asm, for the same reason as elim below: `in`, `j < 6`, `i == j` and `in && i == j` were four more lane masks hoisted
+  // out of a caller's evaluation loop and spilled; each is one compare on this register where it is used.
+  // (kChainLaneRegs: in the chain unit only, whose kernels have that loop; the batched kernels of the main unit keep the masks.)
+  int kind = in ? (j < 6 ? (i == j ? 2 : 1) : 3) : 0;
+  const int lo = i < j ? i : j, hi = i < j ? j : i;
   double a = 0.0;
-  if (in) {
+  if constexpr (kChainLaneRegs) {
+    asm volatile("" : "+v"(kind));
+    // One load in straight-line code, from one per-lane index (a lane that holds nothing reads sum 0 and drops it), and selects on
+    // kind: the same entry, damping and negation as under the three nested lane branches below, without their exec-mask nest.
+    const int at = in ? (j < 6 ? lo * 6 - (lo * (lo - 1)) / 2 + (hi - lo) : 21 + i) : 0;
+    const double v = acc[at];
+    const double damped = v + (double)lambda * v;
+    a = kind == 2 ? damped : v;
+    a = kind == 3 ? -v : a;
+    a = kind == 0 ? 0.0 : a;
+  } else if (in) {
     if (j < 6) {
-      const int lo = i < j ? i : j, hi = i < j ? j : i;
       a = acc[lo * 6 - (lo * (lo - 1)) / 2 + (hi - lo)];
       if (i == j) a = a + (double)lambda * a;
     } else {
@@ -737,15 +768,24 @@ __device__ __forceinline__ void solve_damped_wave_regs(const double* acc, float 
   // Elimination down the diagonal (no row exchanges: the system is symmetric positive semi-definite). The pivot is
   // wave-uniform (v_readlane -> SGPRs); the pivot row and this lane's column-c entry are two independent
   // ds_bpermute gathers per step.
+  // What a column takes from the lane id is ONE register each, computed here: the gathers' byte addresses are a lane's part plus
+  // the column's constant (the instruction's offset field), and "this lane eliminates in column c" — in && i > c && j >= c — is
+  // c <= elim. As written per column these were four address instructions and, in a caller with an evaluation loop, six lane
+  // masks hoisted out of the loop into scalar pairs that lm_fine_kernel spilled and read back lane by lane in every solve; the
+  // empty asm keeps the compares where they are used.
+  int elim = in ? (i - 1 < j ? i - 1 : j) : -1;
+  asm volatile("" : "+v"(elim));
+  const int prow_at = j * 4, mycol_at = (i < 6 ? i : 5) * 32;   // byte addresses of lanes j and (i < 6 ? i : 5) * 8
   unsigned okmask = 0u;
 #pragma unroll
   for (int c = 0; c < 6; c++) {
     const double piv = readlane_d(a, c * 8 + c);
     if (fabs(piv) > 0.0) {  // wave-uniform
       okmask |= 1u << c;
-      const double prow = __shfl(a, c * 8 + j, 64);
-      const double mycol = __shfl(a, (i < 6 ? i : 5) * 8 + c, 64);
-      if (in && i > c && j >= c) {
+      if (c == 5) break;   // no row below the last one (elim <= 4, which the compiler cannot see any more)
+      const double prow = bpermute_d(a, prow_at + c * 32);    // from lane c * 8 + j
+      const double mycol = bpermute_d(a, mycol_at + c * 4);   // from lane (i < 6 ? i : 5) * 8 + c
+      if (c <= elim) {
         // (Round 5, measured and dropped: the division spelled out as the compiler's own sequence — v_div_scale, v_rcp_f64, two
         //  Newton steps, v_div_fmas, v_div_fixup — with the pivot's refined reciprocal computed under the latency of the two
         //  gathers and used whenever v_div_scale scales nothing: bit-identical, five dependent fp64 operations off the chain per
@@ -756,7 +796,7 @@ __device__ __forceinline__ void solve_damped_wave_regs(const double* acc, float 
     }
   }
   // Reciprocal pivots: the diagonal lanes divide side by side (one divide latency for all six).
-  const double rdiag = (in && i == j && ((okmask >> i) & 1u)) ? 1.0 / a : 0.0;
+  const double rdiag = ((kChainLaneRegs ? kind == 2 : (in && i == j)) && ((okmask >> i) & 1u)) ? 1.0 / a : 0.0;
   // Back substitution on wave-uniform values (compile-time indices, xs[] stays in registers).
   double xs[6];
 #pragma unroll
@@ -791,7 +831,9 @@ __device__ __forceinline__ void solve_damped_wave(const double* acc, float lambd
 __device__ __forceinline__ void sincos_pair_lanes(float xa_f, float xb_f, float* sa, float* ca, float* sb, float* cb) {
   const int g = threadIdx.x & 3;
   const bool is_cos = (g & 1) != 0;
-  const double x = (double)((g & 2) ? xb_f : xa_f);
+  int second = g & 2;   // (behind an empty asm: as a lane mask it was hoisted out of a caller's evaluation loop and spilled)
+  if constexpr (kChainLaneRegs) asm volatile("" : "+v"(second));
+  const double x = (double)(second ? xb_f : xa_f);
   const double kf = floor(x * 6.36619772367581382433e-01 + 0.5);
   const double r = (x - kf * 1.57079632673412561417e+00) - kf * 6.07710050650619224932e-11;
   const double r2 = r * r;
@@ -1319,41 +1361,51 @@ __device__ __forceinline__ void lm_hot_store(const LmHot& h, LmState& s) {  // o
   s.pending = 0;
 }
 // All threads of the block call it (it ends with a block barrier); acc_sh holds the 29 sums of the evaluation at s_sh.T.
-__device__ __forceinline__ void lm_state_machine_hot(LmHot& h, const StepLevel* lv, int n_levels, float lambda0, float precision,
+// Wave 0's branch is taken on SCALAR conditions: `threadIdx.x < 64` is the same for a whole wave but divergent to the compiler, and
+// every field of LmHot carried across the join of such a branch became a divergent phi — the accept test, the lambda test, the
+// max_iters test and the level walk were exec-mask nests with register copies into and out of temporaries at every merge. With
+// the wave's first thread id (and have_sums, an __all's result) read through readfirstlane they are s_cbranch_vccz / scc branches
+// and a rejected step copies nothing. What is written only by some exits is written under those exits: the step and the new T
+// exist only behind need_step / a level's begin, the flags the other waves read are stored only when a level stops or begins.
+// Must be called in converged control flow (readfirstlane reads the wave's first ACTIVE lane).
+__device__ __forceinline__ void lm_state_machine_hot(LmHot& hot, const StepLevel* lv, int n_levels, float lambda0, float precision,
                                                      LmState& s_sh, const double* acc_sh, LmTraceRow* __restrict__ trace,
                                                      float* __restrict__ cost_stat, bool publisher,
                                                      unsigned long long* smdbg = nullptr, int stop_level = 0, bool have_sums = true) {
   const int t = threadIdx.x;
-  if (t < 64 && have_sums) {   // (have_sums: wave 0's own; false = its gather gave up, only the closing barrier is left to do)
+  const bool wave0 = __builtin_amdgcn_readfirstlane(t) < 64;
+  const bool sums = __builtin_amdgcn_readfirstlane(have_sums ? 1 : 0) != 0;
+  if (wave0 && sums) {   // (have_sums: wave 0's own; false = its gather gave up, only the closing barrier is left to do)
+    LmHot h = hot;   // (the function's own copy, written back at the end: updated through the reference, active / status / finished
+                     //  were left in scratch memory by the compiler — and a private load is divergent to it)
     unsigned long long c0 = smdbg ? __builtin_readcyclecounter() : 0, c1 = c0, c2 = c0, c3 = c0;
     const int iter0 = h.iter, lvl0 = h.level;
     const float err_last0 = h.err_last;
-    // the T of the evaluation being consumed = matrix(inc): cur's on accept (read ahead of the decision: one LDS trip beside the sums')
-    float Tprev[12];
-#pragma unroll
-    for (int c = 0; c < 4; c++)
-#pragma unroll
-      for (int r = 0; r < 3; r++) Tprev[c * 3 + r] = s_sh.T[c * 4 + r];
     // ---- lm_decide (odo_math.h; ref: src/lm_optimizer.cpp:123-143) ----
     h.n_evals++;
-    if (t == 0) s_sh.iters_level[lvl0 & 7] += 1;
+    // ONE trip to LDS in front of the decision instead of three in a row: sums 27 and 28 are read together (the second was read
+    // behind the branch on the first), and the evaluation count is an LDS add that returns nothing (read, wait, add, write before)
+    const double s27 = acc_sh[27], s28 = acc_sh[28];
+    if (t == 0) __hip_atomic_fetch_add(&s_sh.iters_level[lvl0 & 7], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     bool need_step = false;
-    float err_now = 0.0f;
-    bool have_err = false;
-    if (!(acc_sh[28] > 0.0)) {                           // :244-248 -> :123-126
+    if (!(s28 > 0.0)) {                                  // :244-248 -> :123-126
       h.status = -1;
       h.active = 0;
     } else {
-      err_now = (float)(acc_sh[27] / acc_sh[28]);        // :129
-      have_err = true;
+      const float err_now = (float)(s27 / s28);          // :129
+      if (t == 0) s_sh.err_now = err_now;
       if (err_now > h.err_last) {                        // :131
         h.lambda = h.lambda * 5.0f;
         if (h.lambda > 1e+5f) { h.active = 0; h.stop_reason = 2; }
         else need_step = true;                           // (cur = last: they are equal)
       } else {
         h.cur = h.inc;                                   // (and last = cur)
+        // the T of the evaluation being consumed = matrix(inc): cur's from here on. Read HERE, into Tc itself: the trip to LDS
+        // is in front of the solve's own for the sums (a wave's LDS reads return in order), so it costs its three instructions.
 #pragma unroll
-        for (int i = 0; i < 12; i++) h.Tc[i] = Tprev[i];
+        for (int c = 0; c < 4; c++)
+#pragma unroll
+          for (int r = 0; r < 3; r++) h.Tc[c * 3 + r] = s_sh.T[c * 4 + r];
         const float err_diff = err_now / h.err_last;
         if (err_diff > precision) { h.active = 0; h.stop_reason = 1; }
         else {
@@ -1364,12 +1416,9 @@ __device__ __forceinline__ void lm_state_machine_hot(LmHot& h, const StepLevel* 
       }
     }
     if (smdbg) { c1 = __builtin_readcyclecounter(); c2 = c1; c3 = c1; }
-    float d[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    bool new_T = false;
-    float Tn[16];
-#pragma unroll
-    for (int i = 0; i < 16; i++) Tn[i] = 0.0f;
+    float d_rec[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // the step for the trace row (recording builds; dead without a trace)
     if (need_step) {
+      float d[6];
       solve_damped_wave_regs(acc_sh, h.lambda, d);       // :145-151
       if (smdbg) { asm volatile("" ::"v"(d[0]), "v"(d[5])); c2 = __builtin_readcyclecounter(); }
       Se3 dd;
@@ -1377,20 +1426,23 @@ __device__ __forceinline__ void lm_state_machine_hot(LmHot& h, const StepLevel* 
       const float C[16] = {h.Tc[0], h.Tc[1], h.Tc[2], 0.0f, h.Tc[3], h.Tc[4], h.Tc[5], 0.0f,
                            h.Tc[6], h.Tc[7], h.Tc[8], 0.0f, h.Tc[9], h.Tc[10], h.Tc[11], 1.0f};
       se3_left_update_mat(dd, C, &h.inc);                // :153
+      float Tn[16];
       se3_to_colmajor(h.inc, Tn);
-      new_T = true;
       h.iter++;                                          // :154
       if (!(h.max_iters > h.iter)) { h.active = 0; h.stop_reason = 3; }
       if (smdbg) { asm volatile("" ::"v"(Tn[0]), "v"(Tn[14])); c3 = __builtin_readcyclecounter(); }
-    }
-    if (smdbg && t == 0) { smdbg[0] += c1 - c0; smdbg[1] += c2 - c1; smdbg[2] += c3 - c2; smdbg[3] += 1; }
-    if (t == 0) {
-      if (have_err) s_sh.err_now = err_now;
-      if (need_step) {
+      if (t == 0) {   // (a level that begins below writes its own T over this one)
 #pragma unroll
         for (int i = 0; i < 6; i++) s_sh.delta[i] = d[i];
+#pragma unroll
+        for (int i = 0; i < 16; i++) s_sh.T[i] = Tn[i];
+      }
+      if (trace) {
+#pragma unroll
+        for (int i = 0; i < 6; i++) d_rec[i] = d[i];
       }
     }
+    if (smdbg && t == 0) { smdbg[0] += c1 - c0; smdbg[1] += c2 - c1; smdbg[2] += c3 - c2; smdbg[3] += 1; }
     if (publisher && t == 0 && trace) {   // (see lm_state_machine)
       const int ev = h.n_evals - 1;
       const float e = s_sh.err_now;
@@ -1404,42 +1456,42 @@ __device__ __forceinline__ void lm_state_machine_hot(LmHot& h, const StepLevel* 
         r.stop = (h.stop_reason == 3 || h.active) ? 0 : h.stop_reason;
         r.lambda_after = h.lambda;
 #pragma unroll
-        for (int i = 0; i < 6; i++) r.delta[i] = (h.active || h.stop_reason == 3) ? d[i] : 0.0f;
+        for (int i = 0; i < 6; i++) r.delta[i] = (h.active || h.stop_reason == 3) ? d_rec[i] : 0.0f;
       }
       const int evals_this_level = s_sh.iters_level[lvl0 & 7];
       if (iter0 == 0 && evals_this_level == 1) cost_stat[lvl0 * 2 + 0] = e;
       cost_stat[lvl0 * 2 + 1] = e;
     }
-    if (lv) {
-      while (!h.active && h.status == 0 && !h.finished) {
-        const int next = (h.level < 0) ? n_levels - 1 : h.level - 1;
-        if (next < stop_level) { h.finished = 1; break; }
-        h.stop_reason = 0;
-        // lm_begin_level (ref: src/lm_optimizer.cpp:110-115)
-        h.level = next;
-        h.iter = 0;
-        h.err_last = 1e+10f;
-        h.lambda = lambda0;
-        h.inc = h.cur;
-        h.max_iters = lv[next].max_iters;
-        h.active = (h.status == 0 && h.max_iters > 0) ? 1 : 0;
+    // level, active, status and finished change only when the level stops (every evaluation starts active, with status 0 and not
+    // finished: the callers' loops run on exactly that), so only then is there a walk to do and anything to tell the other waves
+    if (!h.active) {
+      if (lv) {
+        while (!h.active && h.status == 0 && !h.finished) {
+          const int next = (h.level < 0) ? n_levels - 1 : h.level - 1;
+          if (next < stop_level) { h.finished = 1; break; }
+          h.stop_reason = 0;
+          // lm_begin_level (ref: src/lm_optimizer.cpp:110-115)
+          h.level = next;
+          h.iter = 0;
+          h.err_last = 1e+10f;
+          h.lambda = lambda0;
+          h.inc = h.cur;
+          h.max_iters = lv[next].max_iters;
+          h.active = (h.status == 0 && h.max_iters > 0) ? 1 : 0;
+          if (t == 0) {   // T = matrix(inc = cur)
 #pragma unroll
-        for (int c = 0; c < 4; c++) {
+            for (int c = 0; c < 4; c++) {
 #pragma unroll
-          for (int r = 0; r < 3; r++) Tn[c * 4 + r] = h.Tc[c * 3 + r];
-          Tn[c * 4 + 3] = (c == 3) ? 1.0f : 0.0f;
+              for (int r = 0; r < 3; r++) s_sh.T[c * 4 + r] = h.Tc[c * 3 + r];
+              s_sh.T[c * 4 + 3] = (c == 3) ? 1.0f : 0.0f;
+            }
+          }
         }
-        new_T = true;
+        if (h.status != 0) h.finished = 1;
       }
-      if (h.status != 0) h.finished = 1;
+      if (t == 0) { s_sh.level = h.level; s_sh.active = h.active; s_sh.status = h.status; s_sh.finished = h.finished; }   // what the other waves read
     }
-    if (t == 0) {   // what the other waves read
-      if (new_T) {
-#pragma unroll
-        for (int i = 0; i < 16; i++) s_sh.T[i] = Tn[i];
-      }
-      s_sh.level = h.level; s_sh.active = h.active; s_sh.status = h.status; s_sh.finished = h.finished;
-    }
+    hot = h;
   }
   __syncthreads();
 }
@@ -2500,7 +2552,10 @@ __device__ __forceinline__ void lm_fine_body(const StepArgs& a, const StepLaunch
         double accq = 0.0;
         if (my_q < ODO_NACC) accq = rows_accumulate<kLmBlock, kS>(rows_sh, rowA, rowB, my_s, accq);
         accq = rows_butterfly8(accq);
-        if (my_q < ODO_NACC && my_s == 0 && !(fault && vb == 0)) fine_publish(buf, vb, my_q, accq, tag, local);   // fault: row 0 never appears
+        // (who publishes, in one register behind an empty asm: as a lane mask it was hoisted out of this loop and spilled)
+        int pub = (my_q < ODO_NACC && my_s == 0 && !(fault && vb == 0)) ? 1 : 0;   // fault: row 0 never appears
+        if constexpr (kChainLaneRegs) asm volatile("" : "+v"(pub));
+        if (pub) fine_publish(buf, vb, my_q, accq, tag, local);
       }
     } else {
       // Levels of more virtual blocks than the 2 K the workgroups keep in registers (lm_plan_levels: up to 2 K x fine_passes, two
