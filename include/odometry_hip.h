@@ -255,6 +255,17 @@ int odo_lm_launch_stats(const odo_lm* lm, int* n_active_launches, int* n_total_l
  * launch gave up waiting for one of its workgroups and that were redone on the step launches (results unaffected): this
  * optimiser's own Solves plus the batched Solves (odo_lm_solve_batch, odo_tracker_batch) of its context. */
 int odo_lm_persistent_stats(const odo_lm* lm, int* workgroups, int* fallbacks);
+/* Which path the optimiser's last odo_lm_solve / odo_lm_solve_batch took (read-only, host values, no synchronisation):
+ * out[0] the number of sequences of the batched Solve it ran in — 0: a Solve of its own, which is also what every optimiser reports
+ *        after odo_lm_solve_batch fell back to one Solve after the other (more than 64 sequences, t-distribution weights, ...);
+ * out[1] min_level: the coarse launch took the levels >= min_level (n_levels: there was none);
+ * out[2] fine_lo: the persistent launch took the levels [fine_lo, min_level), step launches what lies below (fine_lo >= min_level:
+ *        the sequence took no part in a persistent launch);
+ * out[3] workgroups per sequence of the persistent launch that was issued for the Solve (0: none was issued) — in a batched Solve
+ *        the launch's number, the same for every sequence, also for one that only has its state carried by it;
+ * out[4] launches issued (of the whole batch; after a redo: of the redo);
+ * out[5] 1 if the persistent launch gave up and the Solve was redone on the step launches (out[1 .. 3] then describe the redo). */
+int odo_lm_last_plan(const odo_lm* lm, int out[6]);
 /* Its give-up policy. A wait inside the launch is bounded by the device wall clock (4 ms; ODO_LM_FINE_WAIT_US) — stretched while the
  * shader clock runs below nominal (process start, power cap), but never beyond 4 x the bound (16 ms) —, so a give-up costs that + one
  * redo of the Solve on the step launches. Three give-ups switch the launch off; it is tried again after *retry_after

@@ -162,6 +162,7 @@ SIGNATURES = {
     "odo_lm_points": (C.c_int, [_vp, _ip, _ip]),
     "odo_lm_launch_stats": (C.c_int, [_vp, _ip, _ip, _dp]),
     "odo_lm_persistent_stats": (C.c_int, [_vp, _ip, _ip]),
+    "odo_lm_last_plan": (C.c_int, [_vp, _ip]),
     "odo_lm_persistent_backoff": (C.c_int, [_vp, _ip, _ip, _ip]),
     "odo_lm_tdist_stats": (C.c_int, [_vp, C.POINTER(C.c_long), _ip]),
     "odo_debug_update_stamps": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _fp, C.POINTER(C.c_ulonglong)]),

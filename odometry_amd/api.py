@@ -265,6 +265,14 @@ class LevenbergMarquardtOptimizer:
         L.check(self.ctx.lib.odo_lm_persistent_stats(self.h, C.byref(k), C.byref(f)), "odo_lm_persistent_stats")
         return k.value, f.value
 
+    def last_plan(self):
+        """odo_lm_last_plan: which path the last Solve / solve_batch took, as a dict — n (sequences of the batched Solve, 0: a Solve of
+        its own or the sequential fall-back), min_level, fine_lo, workgroups (per sequence of the persistent launch, 0: none issued),
+        launches, redone."""
+        out = (C.c_int * 6)()
+        L.check(self.ctx.lib.odo_lm_last_plan(self.h, out), "odo_lm_last_plan")
+        return dict(zip(("n", "min_level", "fine_lo", "workgroups", "launches", "redone"), (int(v) for v in out)))
+
     def tdist_stats(self):
         """(scale iterations issued on the multi-workgroup kernel, those redone by its single-workgroup fall-back)"""
         a, b = C.c_long(0), C.c_int(0)

@@ -818,6 +818,9 @@ struct odo_lm {
   float* h_cost;
   // stats of the last solve
   int last_evals, last_launches;
+  // odo_lm_last_plan: {n of the batch (0: a Solve of its own), min_level, fine_lo, workgroups per sequence of the persistent launch
+  // (0: none issued), launches issued, 1 if redone on the step launches} of the last odo_lm_solve / odo_lm_solve_batch
+  int last_plan[6];
   double last_bytes;
   int iters[ODO_MAX_LEVELS];
   int launches_level[ODO_MAX_LEVELS];
@@ -1884,6 +1887,7 @@ extern "C" int odo_lm_solve(odo_lm* m, const odo_pyr* kf_img, const odo_pyr* kf_
   int seq = 0;
   bool started = resumed;
   const int fine_k_asked = m->fine_k;
+  int redone = 0;
 fused_again:
   if (fused) {
     // ---- fused pipeline: the coarse launch + one persistent launch (or identical generic step launches); the device walks
@@ -1947,6 +1951,7 @@ fused_again:
       m->fine_bails++;
       (void)fine_note_giveup(&m->fine_strikes, &m->fine_clean, &m->fine_offs);
       m->fine_k = 0;
+      redone = 1;
       started = false;
       launches = 0;
       m->chained.active = 0;   // (a Solve chained behind this one sees a guard without its token and returns at once)
@@ -1990,6 +1995,13 @@ fused_again:
   m->last_slot = fused ? m->job.slot : 0;
   m->last_evals = (int)m->h_out[17];
   m->last_launches = launches;
+  {
+    const int ml = fused ? m->job.min_level : m->n_levels, fl = fused ? m->job.fine_lo : m->n_levels;
+    int fine_budget = 0;   // (lm_job_launch_fine issues the launch only when its levels have evaluations)
+    for (int l = fl; l < ml; l++) fine_budget += m->max_iters[l] > 0 ? m->max_iters[l] : 0;
+    const int plan[6] = {0, ml, fl, (fl < ml && fine_budget > 0) ? m->fine_k_last : 0, launches, redone};
+    memcpy(m->last_plan, plan, sizeof(plan));
+  }
   m->last_bytes = 0.0;
   for (int l = 0; l < ODO_MAX_LEVELS; l++) {
     m->iters[l] = (int)m->h_out[18 + l];
@@ -2179,7 +2191,9 @@ static int lm_batch_begin(int n, odo_lm* const* lms, const odo_pyr* const* kf_im
     if (ml < m->n_levels) any_coarse = 1;
     if (fl < ml) any_fine = 1;
     m->last_coarse = (ml < m->n_levels) ? 1 : 0;
+    m->last_plan[0] = n; m->last_plan[1] = ml; m->last_plan[2] = fl;
   }
+  for (int i = 0; i < n; i++) { lms[i]->last_plan[3] = any_fine ? fine_k : 0; lms[i]->last_plan[4] = 0; lms[i]->last_plan[5] = 0; }
   // the table of the previous batched Solve may still be read by its draining launches: order the upload behind them
   HIP_OK(hipMemcpyAsync(d_table, h_table, sizeof(StepArgs) * (size_t)n, hipMemcpyHostToDevice, s));
   jb.grid = grid; jb.budget = budget; jb.seq = 0; jb.launches = 0; jb.it = 0; jb.poll_ok = true; jb.issued_all = false;
@@ -2359,7 +2373,12 @@ static int lm_solve_batch(int n, odo_lm* const* lms, const odo_pyr* const* kf_im
           m->ust = m->d_state; m->upo = 0;
         }
         if (lm_unfused_levels_batch(n, lms, kf_img, kf_dep, cur_img, lms[0]->n_levels - 1, &launches, bytes, idle, idle_arg)) return -1;
-        for (int i = 0; i < n; i++) { take_result(i); if (status[i]) any_fail = 1; }
+        for (int i = 0; i < n; i++) {
+          take_result(i);
+          if (status[i]) any_fail = 1;
+          const int plan[6] = {n, lms[i]->n_levels, lms[i]->n_levels, 0, launches, 0};   // batched, no fused part at all
+          memcpy(lms[i]->last_plan, plan, sizeof(plan));
+        }
         if (any_fail) fail("Optimize failed! ");
         return 0;
       }
@@ -2446,7 +2465,11 @@ collect_again:
       if (rc) return -1;
     }
   }
-  for (int i = 0; i < n; i++) { take_result(i); if (status[i]) any_fail = 1; }
+  for (int i = 0; i < n; i++) {
+    take_result(i);
+    if (status[i]) any_fail = 1;
+    lms[i]->last_plan[4] = launches; lms[i]->last_plan[5] = redone;   // (the rest of the report: lm_batch_begin)
+  }
   // (forgiveness and retry as in odo_lm_solve: lm_batch_begin uses the launch whenever batch_fine_strikes < 3)
   (void)fine_note_clean(jb.fine_used && !redone, &cx->batch_fine_strikes, &cx->batch_fine_clean, &cx->batch_fine_offs);
   if (lms[0]->ev_on) {   // launch statistics of the batched Solve, kept with the first optimiser (odo_lm_event_stats_ex)
@@ -2578,6 +2601,12 @@ extern "C" int odo_lm_persistent_stats(const odo_lm* m, int* workgroups, int* fa
   if (!m) return fail("odo_lm_persistent_stats: NULL lm");
   if (workgroups) *workgroups = (m->fine_k > 0 && m->fine_k_last > 0) ? m->fine_k_last : m->fine_k;
   if (fallbacks) *fallbacks = m->fine_bails + m->ctx->batch_fine_bails;   // its own Solves + its context's batched Solves
+  return 0;
+}
+// Which path the last Solve took (host values only: written by odo_lm_solve, lm_batch_begin and lm_solve_batch).
+extern "C" int odo_lm_last_plan(const odo_lm* m, int out[6]) {
+  if (!m || !out) return fail("odo_lm_last_plan: NULL arg");
+  memcpy(out, m->last_plan, sizeof(m->last_plan));
   return 0;
 }
 // Back-off state of the persistent launch: give-ups that count (3 = switched off), the interval after which a switched-off launch

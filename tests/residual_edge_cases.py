@@ -29,13 +29,18 @@ def _texture(x, y):
     return 128.0 + 50.0 * np.sin(0.23 * x + 0.11 * y) + 40.0 * np.cos(0.17 * y - 0.05 * x) + 25.0 * np.sin(0.31 * x) * np.cos(0.27 * y)
 
 
-def frames():
+def frames(rows=ROWS, cols=COLS, valid=None):
     """(keyframe image, inverse depth — valid everywhere, two values in a checkerboard of 2 x 2 cells so that a translation moves
-    neighbouring points by different amounts —, current image), float32."""
-    y, x = np.mgrid[0:ROWS, 0:COLS].astype(np.float64)
+    neighbouring points by different amounts —, current image), float32. Other sizes and `valid` = (row0, row1, col0, col1), the
+    only window that keeps its inverse depth, are for tests/batch_chain_cases.py."""
+    y, x = np.mgrid[0:rows, 0:cols].astype(np.float64)
     img0 = _texture(x, y).astype(np.float32)
     img1 = _texture(x + 1.0, y + 1.0).astype(np.float32)
     inv = np.where(((x // 2) + (y // 2)) % 2 == 0, 0.125, 0.25).astype(np.float32)
+    if valid is not None:
+        keep = np.zeros((rows, cols), bool)
+        keep[valid[0]:valid[1], valid[2]:valid[3]] = True
+        inv[~keep] = 0.0
     return img0, inv, img1
 
 

@@ -57,6 +57,63 @@ CASES = {
 }
 
 
+COARSEST, FINEST = LEVELS - 1, 0
+
+
+def check_exits(trace_i, trace_f):
+    """Every row of CASES takes the exit it is named for. trace_i[case]: the recorded (level, iter, n_res, accepted, stop) rows of the
+    row's Solve, trace_f[case]: their (err, lambda after, delta[6]) — of a single Solve or of one sequence of a batched one."""
+    def _rows(case):
+        return [tuple(int(x) for x in r) for r in trace_i[case]], [float(x) for x in trace_f[case][:, 1]]
+
+    def _of_level(rows, level):
+        return [r for r in rows if r[0] == level]
+
+    # identical frames: err == 0 on the coarsest level, every step accepted (0 / 0 > precision is false), the level ends at max_iters
+    # on an ACCEPTED step and the walk goes on
+    rows, lam = _rows("identical")
+    co = _of_level(rows, COARSEST)
+    assert len(co) == 6 and all(r[3] == 1 and r[4] == 0 for r in co) and rows[6][:2] == (FINEST, 0)
+    assert (trace_f["identical"][:6, 0] == 0).all()
+    # accept, then the precision stop — on the coarsest level (the level changes on an accepted step) and on the finest (the Solve ends)
+    rows, lam = _rows("precision")
+    for level in (COARSEST, FINEST):
+        lv = _of_level(rows, level)
+        assert lv[0][3:] == (1, 0) and lv[-1][3:] == (1, 1) and len(lv) < 6
+    assert rows[-1][0] == FINEST and rows[len(_of_level(rows, COARSEST))][:2] == (FINEST, 0)
+    # reject with lambda x 5 and a step from the unchanged estimate; the coarsest level ends at max_iters on a REJECTED step
+    rows, lam = _rows("reject_x5")
+    rej = [i for i, r in enumerate(rows) if r[3:] == (0, 0)]
+    assert rej and all(np.float32(lam[i]) == np.float32(lam[i - 1]) * np.float32(5.0) for i in rej if rows[i][1] > 0)
+    co = _of_level(rows, COARSEST)
+    assert len(co) == 6 and co[-1][3] == 0 and rows[6][:2] == (FINEST, 0)
+    # lambda over 1e5: the level stops on a rejected step, the next level begins
+    rows, lam = _rows("lambda_stop")
+    stops = [i for i, r in enumerate(rows) if r[4] == 2]
+    assert len(stops) == 1 and rows[stops[0]][3] == 0 and lam[stops[0]] > 1e5 and rows[stops[0]][0] == COARSEST
+    assert rows[stops[0] + 1][:2] == (FINEST, 0) and rows[stops[0] - 1][3:] == (0, 0)
+    # max_iters 1 and 2
+    for case, n_fine, n_coarse in (("iters_1_2", 1, 2), ("iters_2_1", 2, 1)):
+        rows, lam = _rows(case)
+        assert [r[:2] for r in rows] == [(COARSEST, i) for i in range(n_coarse)] + [(FINEST, i) for i in range(n_fine)]
+        assert all(r[4] == 0 for r in rows)
+    # a level with max_iters 0: walked over, at the end and at the start of the pyramid
+    rows, lam = _rows("no_finest")
+    assert len(rows) == 6 and all(r[0] == COARSEST for r in rows)
+    rows, lam = _rows("no_coarsest")
+    assert len(rows) == 6 and all(r[0] == FINEST for r in rows)
+    # a reject as the first evaluation of a level (the step starts from the level's initial estimate)
+    rows, lam = _rows("reject_first")
+    assert len(rows) == 12 and all(r[3:] == (0, 0) for r in rows)
+    # ... and lambda over 1e5 there: one evaluation per level, no step
+    rows, lam = _rows("reject_first_stop")
+    assert [r[:2] + r[3:] for r in rows] == [(COARSEST, 0, 0, 2), (FINEST, 0, 0, 2)]
+    assert (trace_f["reject_first_stop"][:, 2:] == 0).all()
+    # ... and after two rejected steps
+    rows, lam = _rows("reject_stop_3rd")
+    assert [r[:2] + r[3:] for r in rows] == [(l, i, 0, 2 if i == 2 else 0) for l in (COARSEST, FINEST) for i in range(3)]
+
+
 def main(out, routes):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from odometry_amd import api

@@ -26,6 +26,18 @@ def test_header_symbols_are_exported_and_bound():
     assert lib.odo_version() >= 100
 
 
+def test_the_plan_report_is_declared_bound_and_refuses_null():
+    """odo_lm_last_plan: which path an optimiser's last Solve took (tests/test_gpu_batch_chain_cases.py reads every route from it)."""
+    from odometry_amd import _lib, api
+    lib = _lib.load()
+    assert "odo_lm_last_plan" in declared_symbols() and hasattr(api.LevenbergMarquardtOptimizer, "last_plan")
+    restype, argtypes = _lib.SIGNATURES["odo_lm_last_plan"]
+    assert restype is C.c_int and len(argtypes) == 2
+    out = (C.c_int * 6)(*[7] * 6)
+    assert lib.odo_lm_last_plan(None, out) == -1 and "odo_lm_last_plan" in _lib.last_error()
+    assert list(out) == [7] * 6
+
+
 def test_library_is_in_tree_and_has_gfx950_code():
     from odometry_amd import _lib
     assert _lib.LIB_PATH.startswith(ROOT)

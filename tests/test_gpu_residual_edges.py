@@ -1,7 +1,9 @@
 """The residual of the LM chain kernels at the edges of its validity test (point_residual_g, kernels.hip.h): ONE predicate — the lane
 holds a point, t2 > 0, 0 <= floor(u) < cols, 0 <= floor(v) < rows, a NaN failing every comparison — selects the taps' pixel and the
-row's r and J instead of a nest of early returns, in the coarse launch, the persistent launch and their batched / recording /
-t-distribution builds. The step launches keep the branching point_residual: they are the in-library reference here.
+row's r and J instead of a nest of early returns, in the coarse launch and the persistent launch. This module runs their recording and
+their lean builds on single Solves with Huber weights; the batched builds run the same poses as sequences of one batched Solve in
+tests/test_gpu_batch_chain_cases.py, and no test issues these poses with t-distribution weights. The step launches keep the branching
+point_residual: they are the in-library reference here.
 
 A two-level pyramid of a 32 x 40 image with a valid inverse depth everywhere, so every interior pixel is a keyframe point (the
 library's interior keeps 4 pixels from each border: 24 x 32 = 768 and 8 x 12 = 96 points, three virtual blocks and one), solved from

@@ -29,7 +29,7 @@ from test_gpu_residual_edges import ROUTES, _KNOBS
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COARSEST, FINEST = cases.LEVELS - 1, 0
+COARSEST, FINEST = cases.COARSEST, cases.FINEST
 
 
 @pytest.fixture(scope="module")
@@ -56,36 +56,39 @@ def runs(tmp_path_factory):
     return out
 
 
+def oracle_reference(O, pyr, c, robust=cases.ROBUST):
+    """(the oracle's Solve of the row c, per recorded evaluation the condition number of the damped system it solved). pyr: a cache of
+    the oracle's pyramids per kind of frames."""
+    flat = lambda levels: np.concatenate([l.ravel() for l in levels])
+    if c["kind"] not in pyr:
+        img0, inv, img1 = cases.frames(c["kind"])
+        pyr[c["kind"]] = (O.image_pyramid(img0, cases.LEVELS, True), O.depth_pyramid(inv, cases.LEVELS),
+                          O.image_pyramid(img1, cases.LEVELS, True))
+    r0, rd, r1 = pyr[c["kind"]]
+    params = O.lm_params(lam=c["lam"], precision=cases.PRECISION, max_iters=tuple(c["iters"]), robust=robust,
+                         huber_delta=cases.HUBER, K=cases.K)
+    solve = O.lm_solve(flat(r0), flat(rd), flat(r1), cases.ROWS, cases.COLS, params, init=c["T"])
+    conds = []
+    for row in solve["trace"]:
+        cond = 0.0
+        if np.any(row["delta"] != 0):
+            l = row["level"]
+            acc = O.lm_accumulate(r0[l], r1[l], rd[l], l, row["pose"], robust=robust, huber_delta=cases.HUBER, K=cases.K)["acc"]
+            A = np.zeros((6, 6))
+            for i in range(6):
+                for j in range(i, 6):
+                    A[i, j] = A[j, i] = acc[i * 6 - (i * (i - 1)) // 2 + (j - i)]
+            A[np.diag_indices(6)] += np.float64(np.float32(row["lambda_after"])) * np.diag(A)
+            cond = float(np.linalg.cond(A))
+        conds.append(cond)
+    return solve, conds
+
+
 @pytest.fixture(scope="module")
 def refs(O):
     """The oracle's Solve of every row, and per recorded evaluation the condition number of the damped system it solved."""
-    out = {}
-    flat = lambda levels: np.concatenate([l.ravel() for l in levels])
     pyr = {}
-    for name, c in cases.CASES.items():
-        if c["kind"] not in pyr:
-            img0, inv, img1 = cases.frames(c["kind"])
-            pyr[c["kind"]] = (O.image_pyramid(img0, cases.LEVELS, True), O.depth_pyramid(inv, cases.LEVELS),
-                              O.image_pyramid(img1, cases.LEVELS, True))
-        r0, rd, r1 = pyr[c["kind"]]
-        params = O.lm_params(lam=c["lam"], precision=cases.PRECISION, max_iters=tuple(c["iters"]), robust=cases.ROBUST,
-                             huber_delta=cases.HUBER, K=cases.K)
-        solve = O.lm_solve(flat(r0), flat(rd), flat(r1), cases.ROWS, cases.COLS, params, init=c["T"])
-        conds = []
-        for row in solve["trace"]:
-            cond = 0.0
-            if np.any(row["delta"] != 0):
-                l = row["level"]
-                acc = O.lm_accumulate(r0[l], r1[l], rd[l], l, row["pose"], robust=cases.ROBUST, huber_delta=cases.HUBER, K=cases.K)["acc"]
-                A = np.zeros((6, 6))
-                for i in range(6):
-                    for j in range(i, 6):
-                        A[i, j] = A[j, i] = acc[i * 6 - (i * (i - 1)) // 2 + (j - i)]
-                A[np.diag_indices(6)] += np.float64(np.float32(row["lambda_after"])) * np.diag(A)
-                cond = float(np.linalg.cond(A))
-            conds.append(cond)
-        out[name] = (solve, conds)
-    return out
+    return {name: oracle_reference(O, pyr, c) for name, c in cases.CASES.items()}
 
 
 def _bits(a):
@@ -130,71 +133,28 @@ def test_the_recorded_rows_are_the_oracles(runs, refs, case):
             assert solve["n_evals"] == 0 and len(ti) <= 1 and (ti[:, 2] == 0).all(), key
             continue
         assert n_evals == solve["n_evals"] == len(ti), key
-        for row, f, b, cond in zip(ti, tf, solve["trace"], conds):
-            d_dev, d_ref = f[2:].astype(np.float64), b["delta"].astype(np.float64)
-            bound = (cond + 1.0) * 2.0 ** -22 * np.linalg.norm(d_ref)
-            print(key, "level", row[0], "iter", row[1], "N", row[2], "accepted", row[3], "stop", row[4], "err", f[0], "oracle", b["err"],
-                  "lambda", f[1], "oracle", b["lambda_after"], "|d - oracle's|", np.linalg.norm(d_dev - d_ref), "bound", bound)
-            assert tuple(int(x) for x in row) == (b["level"], b["iter"], b["n_res"], b["accepted"], b["stop"]), key
-            assert abs(np.float64(f[0]) - b["err"]) <= 2.0 ** -23 * abs(b["err"]), key
-            assert np.float32(f[1]) == np.float32(b["lambda_after"]), key
-            assert np.linalg.norm(d_dev - d_ref) <= bound, key
+        assert_rows_are_the_oracles(key, ti, tf, solve, conds)
 
 
-def _rows(runs, case):
-    """[(level, iter, n_res, accepted, stop)], [lambda after] of the in-library reference's recording run (every route equals it)."""
-    return [tuple(int(x) for x in r) for r in runs[f"step_{case}_rec_trace_i"]], [float(x) for x in runs[f"step_{case}_rec_trace_f"][:, 1]]
-
-
-def _of_level(rows, level):
-    return [r for r in rows if r[0] == level]
+def assert_rows_are_the_oracles(key, ti, tf, solve, conds):
+    """Recorded rows against the oracle's: integer fields and lambda exact, err one fp32 rounding, the step within the perturbation
+    bound of the module's docstring."""
+    for row, f, b, cond in zip(ti, tf, solve["trace"], conds):
+        d_dev, d_ref = f[2:].astype(np.float64), b["delta"].astype(np.float64)
+        bound = (cond + 1.0) * 2.0 ** -22 * np.linalg.norm(d_ref)
+        print(key, "level", row[0], "iter", row[1], "N", row[2], "accepted", row[3], "stop", row[4], "err", f[0], "oracle", b["err"],
+              "lambda", f[1], "oracle", b["lambda_after"], "|d - oracle's|", np.linalg.norm(d_dev - d_ref), "bound", bound)
+        assert tuple(int(x) for x in row) == (b["level"], b["iter"], b["n_res"], b["accepted"], b["stop"]), key
+        assert abs(np.float64(f[0]) - b["err"]) <= 2.0 ** -23 * abs(b["err"]), key
+        assert np.float32(f[1]) == np.float32(b["lambda_after"]), key
+        assert np.linalg.norm(d_dev - d_ref) <= bound, key
 
 
 def test_each_row_of_the_table_takes_its_exit(runs):
-    # identical frames: err == 0 on the coarsest level, every step accepted (0 / 0 > precision is false), the level ends at max_iters
-    # on an ACCEPTED step and the walk goes on
-    rows, lam = _rows(runs, "identical")
-    co = _of_level(rows, COARSEST)
-    assert len(co) == 6 and all(r[3] == 1 and r[4] == 0 for r in co) and rows[6][:2] == (FINEST, 0)
-    assert (runs["step_identical_rec_trace_f"][:6, 0] == 0).all()
-    # accept, then the precision stop — on the coarsest level (the level changes on an accepted step) and on the finest (the Solve ends)
-    rows, lam = _rows(runs, "precision")
-    for level in (COARSEST, FINEST):
-        lv = _of_level(rows, level)
-        assert lv[0][3:] == (1, 0) and lv[-1][3:] == (1, 1) and len(lv) < 6
-    assert rows[-1][0] == FINEST and rows[len(_of_level(rows, COARSEST))][:2] == (FINEST, 0)
-    # reject with lambda x 5 and a step from the unchanged estimate; the coarsest level ends at max_iters on a REJECTED step
-    rows, lam = _rows(runs, "reject_x5")
-    rej = [i for i, r in enumerate(rows) if r[3:] == (0, 0)]
-    assert rej and all(np.float32(lam[i]) == np.float32(lam[i - 1]) * np.float32(5.0) for i in rej if rows[i][1] > 0)
-    co = _of_level(rows, COARSEST)
-    assert len(co) == 6 and co[-1][3] == 0 and rows[6][:2] == (FINEST, 0)
-    # lambda over 1e5: the level stops on a rejected step, the next level begins
-    rows, lam = _rows(runs, "lambda_stop")
-    stops = [i for i, r in enumerate(rows) if r[4] == 2]
-    assert len(stops) == 1 and rows[stops[0]][3] == 0 and lam[stops[0]] > 1e5 and rows[stops[0]][0] == COARSEST
-    assert rows[stops[0] + 1][:2] == (FINEST, 0) and rows[stops[0] - 1][3:] == (0, 0)
-    # max_iters 1 and 2
-    for case, n_fine, n_coarse in (("iters_1_2", 1, 2), ("iters_2_1", 2, 1)):
-        rows, lam = _rows(runs, case)
-        assert [r[:2] for r in rows] == [(COARSEST, i) for i in range(n_coarse)] + [(FINEST, i) for i in range(n_fine)]
-        assert all(r[4] == 0 for r in rows)
-    # a level with max_iters 0: walked over, at the end and at the start of the pyramid
-    rows, lam = _rows(runs, "no_finest")
-    assert len(rows) == 6 and all(r[0] == COARSEST for r in rows)
-    rows, lam = _rows(runs, "no_coarsest")
-    assert len(rows) == 6 and all(r[0] == FINEST for r in rows)
+    # the checks themselves: state_machine_cases.check_exits (shared with tests/test_gpu_batch_chain_cases.py), on the in-library
+    # reference's recording run (every route equals it)
+    cases.check_exits({c: runs[f"step_{c}_rec_trace_i"] for c in cases.CASES}, {c: runs[f"step_{c}_rec_trace_f"] for c in cases.CASES})
     # no residual at all
     for route in ROUTES:
         for kind in ("rec", "lean"):
             assert int(runs[f"{route}_no_residual_{kind}_meta"][0]) == -1
-    # a reject as the first evaluation of a level (the step starts from the level's initial estimate)
-    rows, lam = _rows(runs, "reject_first")
-    assert len(rows) == 12 and all(r[3:] == (0, 0) for r in rows)
-    # ... and lambda over 1e5 there: one evaluation per level, no step
-    rows, lam = _rows(runs, "reject_first_stop")
-    assert [r[:2] + r[3:] for r in rows] == [(COARSEST, 0, 0, 2), (FINEST, 0, 0, 2)]
-    assert (runs["step_reject_first_stop_rec_trace_f"][:, 2:] == 0).all()
-    # ... and after two rejected steps
-    rows, lam = _rows(runs, "reject_stop_3rd")
-    assert [r[:2] + r[3:] for r in rows] == [(l, i, 0, 2 if i == 2 else 0) for l in (COARSEST, FINEST) for i in range(3)]
