@@ -1030,6 +1030,45 @@ int odo_rgbd_frontend_stats(odo_rgbd_frontend* f, const float* gray_out, long ou
 /* Frames in flight are completed first. */
 int odo_rgbd_frontend_destroy(odo_rgbd_frontend* f);
 
+/* ---- Bilateral depth filter: an edge-preserving denoiser for uint16 sensor depth, exact to the last bit ------------------------
+ * Integers only, no floating point and no exp on the device: the weights are small tables that the caller passes in (Python:
+ * api.depth_filter_tables makes Gaussian ones that follow a sensor's noise model), and the sums do not depend on their order.
+ * Frame rows x cols uint16, dense rows, 0 = no reading; radius R in 1 .. 4, the window is (2R + 1)^2;
+ *   ws[(2R + 1)^2]  spatial weights, row-major, each 0 .. 16, the centre's >= 1 (the rest of ws[81] is ignored);
+ *   wr[256]         range weights 0 .. 255, wr[0] >= 1;
+ *   shift[256]      0 .. 4, indexed by the centre's high byte.
+ * Per pixel with centre c = raw[y][x]: c == 0 gives 0 (nothing is filled in). Otherwise s = shift[c >> 8], and every tap t of the
+ * window that lies inside the frame and has t != 0 gives delta = (int)t - (int)c, k = |delta| >> s; the tap counts iff k < 256, with
+ * weight w = ws[tap] * wr[k]. S = sum of w * delta and W = sum of w over the counted taps, both int32 (|S| <= 4080 * 4095 * 80 =
+ * 1 336 608 000; W >= ws[centre] * wr[0] >= 1). With C's truncating division q = S >= 0 ? (S + W / 2) / W : -((-S + W / 2) / W), and
+ * out = c + q. It follows that out == 0 exactly where raw == 0; that out lies between the smallest and the largest counted tap; that
+ * a tap further than 256 << s raw units from the centre contributes nothing (a depth edge is never averaged across); and that ws
+ * with only its centre non-zero gives out == raw. shift lets the range kernel widen with the sensor's noise, which grows with z^2. */
+typedef struct odo_depth_filter odo_depth_filter;
+typedef struct {
+  int rows, cols, radius;
+  uint8_t ws[81], wr[256], shift[256];
+} odo_depth_filter_params;
+/* Validates every bound above (and rows, cols in 1 .. 8192) before it touches the device: -1 with a message and *out untouched on
+ * any violation. Device memory: 512 B + 16 B per tile of 64 x 16 pixels. ctx must outlive the filter. One host thread at a time. */
+int odo_depth_filter_create(odo_ctx* ctx, const odo_depth_filter_params* p, odo_depth_filter** out);
+/* One launch on ctx's stream, returns at once: out_dev = the filter of in_dev (both rows x cols uint16 on the device, dense; 8-byte
+ * alignment and cols % 4 == 0 take the wide loads and stores). -1 and nothing enqueued for a NULL, for in_dev == out_dev and for any
+ * other overlap of the two frames. Ordered behind it without a host wait: whatever is enqueued on ctx's stream afterwards
+ * (odo_dev_download, odo_ctx_synchronize, and of a volume created on ctx the calls that read a depth frame: odo_volume_integrate_dev /
+ * _colour_dev run on ctx's stream, odo_volume_icp_*_dev and odo_volume_track*_dev order the volume's stream behind it). NOT ordered behind it:
+ * a tracker, which reads its depth frame on a stream of its own (odo_ctx_synchronize(ctx) before odo_tracker_init_rgbd / _track_rgbd /
+ * _hint_next_rgbd receive out_dev), and an RGB-D front end's submit_dev, which runs on the front end's stream. */
+int odo_depth_filter_run_dev(odo_depth_filter* f, const uint16_t* in_dev, uint16_t* out_dev);
+/* Of the last run, exact: n_valid (pixels with a reading), n_changed (out != raw), sum_abs_change (sum of |out - raw|). Waits for
+ * ctx's stream. Zeros before the first run. */
+int odo_depth_filter_stats(odo_depth_filter* f, long out[3]);
+/* Diagnostic, like odo_volume_raycast_time: one launch to warm, `reps` (1 .. 10000) between two events on ctx's stream; *us = the mean
+ * time of one launch in microseconds. Waits. out_dev and the statistics are those of one run afterwards. */
+int odo_depth_filter_time_dev(odo_depth_filter* f, const uint16_t* in_dev, uint16_t* out_dev, int reps, float* us);
+/* Safe with a run in flight: waits for ctx's stream first. */
+int odo_depth_filter_destroy(odo_depth_filter* f);
+
 /* ---- S sequences in lock step on one GPU (the data-parallel axis of SURVEY section 8e inside one device) -----------------
  * One odo_tracker tracks one sequence as a serial chain of ~70 short launches per frame, which leaves most of the chip
  * idle. odo_tracker_batch runs the same frame loop (ref: run_odometry_kitti_offline.cpp:198-271) for n_sequences independent

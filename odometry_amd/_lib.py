@@ -43,6 +43,11 @@ class RgbdFrontendParams(C.Structure):
                 ("colour_from_depth", C.c_float * 12), ("colour_channels", C.c_int), ("colour_bgr", C.c_int), ("slots", C.c_int)]
 
 
+class DepthFilterParams(C.Structure):
+    _fields_ = [("rows", C.c_int), ("cols", C.c_int), ("radius", C.c_int), ("ws", C.c_uint8 * 81), ("wr", C.c_uint8 * 256),
+                ("shift", C.c_uint8 * 256)]
+
+
 class VolumeParams(C.Structure):
     _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("voxel_size", C.c_float), ("origin", C.c_float * 3),
                 ("mu", C.c_float), ("max_depth", C.c_float), ("max_weight", C.c_int), ("rows", C.c_int), ("cols", C.c_int),
@@ -301,6 +306,11 @@ SIGNATURES = {
     "odo_debug_volume_spill_guard": (C.c_int, [_vp, C.POINTER(C.c_long)]),   # test only: not for integrators (include/odometry_hip.h)
     "odo_volume_set_follow": (C.c_int, [_vp, C.POINTER(VolumeFollowParams)]),
     "odo_volume_follow": (C.c_int, [_vp, _fp, _ip]),
+    "odo_depth_filter_create": (C.c_int, [_vp, C.POINTER(DepthFilterParams), C.POINTER(_vp)]),
+    "odo_depth_filter_run_dev": (C.c_int, [_vp, _vp, _vp]),
+    "odo_depth_filter_stats": (C.c_int, [_vp, C.POINTER(C.c_long)]),
+    "odo_depth_filter_time_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, _fp]),
+    "odo_depth_filter_destroy": (C.c_int, [_vp]),
 }
 
 _lib = None

@@ -1549,6 +1549,117 @@ class RgbdFrontend:
             pass
 
 
+KINECT_AXIAL_NOISE = (0.0012, 0.0019, 0.4)   # sigma(z) = a + b (z - z0)^2 metres: the published Kinect axial model (synth.sensor_noise)
+
+
+def depth_filter_tables(radius=2, sigma_s=1.5, sigma0=8.0, gain=3.0, depth_scale=1000.0, noise=KINECT_AXIAL_NOISE):
+    """The three tables of the bilateral depth filter (include/odometry_hip.h, odo_depth_filter_create) as Gaussians that follow a
+    sensor's axial noise sigma(z) = a + b (z - z0)^2 metres, noise = (a, b, z0):
+      ws[dy][dx] = rint(16 exp(-(dx^2 + dy^2) / (2 sigma_s^2))), (2 radius + 1)^2 uint8;
+      wr[k]      = rint(255 exp(-k^2 / (2 sigma0^2))), sigma0 in raw units, 256 uint8;
+      shift[j]   = clip(rint(log2(gain sigma(z_j) depth_scale / sigma0)), 0, 4) with z_j = (256 j + 128) / depth_scale: the range
+                   kernel's width sigma0 << shift follows gain sigma(z) in raw units.
+    Returns (ws, wr, shift)."""
+    a, b, z0 = noise
+    d = np.arange(-radius, radius + 1, dtype=np.float64)
+    ws = np.rint(16.0 * np.exp(-(d[None, :] ** 2 + d[:, None] ** 2) / (2.0 * sigma_s * sigma_s))).astype(np.uint8)
+    k = np.arange(256, dtype=np.float64)
+    wr = np.rint(255.0 * np.exp(-k * k / (2.0 * sigma0 * sigma0))).astype(np.uint8)
+    z = (256.0 * k + 128.0) / depth_scale
+    sig = a + b * (z - z0) ** 2
+    shift = np.clip(np.rint(np.log2(gain * sig * depth_scale / sigma0)), 0, 4).astype(np.uint8)
+    return ws, wr, shift
+
+
+class DepthFilter:
+    """The bilateral depth filter on the device (odo_depth_filter_*): a uint16 sensor depth frame in, the denoised frame out, one
+    launch on the context's stream, exact integers (include/odometry_hip.h). ctx_or_tracker: a Context, or a Tracker (its context).
+    size = (rows, cols); tables = (ws, wr, shift), default depth_filter_tables(**table_kwargs)."""
+
+    STATS = ("n_valid", "n_changed", "sum_abs_change")
+
+    def __init__(self, ctx_or_tracker, size, tables=None, **table_kwargs):
+        self.lib = L.load()
+        self._owner = ctx_or_tracker   # keeps the stream's owner alive as long as the filter
+        self._ctx = ctx_or_tracker._ctx if isinstance(ctx_or_tracker, Tracker) else ctx_or_tracker.h
+        if tables is not None and table_kwargs:
+            raise TypeError("tables and table keywords exclude each other")
+        ws, wr, shift = depth_filter_tables(**table_kwargs) if tables is None else tables
+        ws = np.asarray(ws)
+        if ws.ndim != 2 or ws.shape[0] != ws.shape[1] or ws.shape[0] % 2 != 1:
+            raise ValueError(f"ws {ws.shape}: a (2R + 1) x (2R + 1) array")
+        wr, shift = np.asarray(wr).reshape(-1), np.asarray(shift).reshape(-1)
+        if wr.shape != (256,) or shift.shape != (256,):
+            raise ValueError("wr and shift have 256 entries each")
+        for name, t in (("ws", ws), ("wr", wr), ("shift", shift)):
+            if t.min() < 0 or t.max() > 255:
+                raise ValueError(f"{name} does not fit uint8")
+        p = L.DepthFilterParams()
+        p.rows, p.cols = size
+        p.radius = (ws.shape[0] - 1) // 2
+        flat = ws.reshape(-1)
+        if flat.size > 81:
+            raise ValueError(f"radius {p.radius} (1 .. 4)")
+        for i, v in enumerate(flat):
+            p.ws[i] = int(v)
+        for i in range(256):
+            p.wr[i], p.shift[i] = int(wr[i]), int(shift[i])
+        self.params = p
+        self.rows, self.cols, self.radius = p.rows, p.cols, p.radius
+        self._out = None
+        self.h = None
+        h = C.c_void_p()
+        L.check(self.lib.odo_depth_filter_create(self._ctx, C.byref(p), C.byref(h)), "odo_depth_filter_create")
+        self.h = h
+
+    def run(self, depth_dev, out_dev=None):
+        """Enqueues the filter of the device frame depth_dev and returns the handle of the output at once: out_dev, or a buffer of
+        the filter's own (overwritten by the next such run; `close` frees it)."""
+        if out_dev is None:
+            if self._out is None:
+                p = C.c_void_p()
+                L.check(self.lib.odo_dev_alloc(self._ctx, 2 * self.rows * self.cols, C.byref(p)), "odo_dev_alloc")
+                self._out = p
+            out_dev = self._out
+        L.check(self.lib.odo_depth_filter_run_dev(self.h, depth_dev, out_dev), "odo_depth_filter_run_dev")
+        return out_dev
+
+    def stats(self):
+        """The last run's exact counts (waits for it)."""
+        o = (C.c_long * 3)()
+        L.check(self.lib.odo_depth_filter_stats(self.h, o), "odo_depth_filter_stats")
+        return dict(zip(self.STATS, list(o)))
+
+    def time(self, depth_dev, out_dev=None, reps=50):
+        """Mean microseconds of one launch, `reps` between two events (a diagnostic: tools/depth_filter_cost.py)."""
+        if out_dev is None:
+            out_dev = self.run(depth_dev)
+        us = C.c_float(0)
+        L.check(self.lib.odo_depth_filter_time_dev(self.h, depth_dev, out_dev, reps, C.byref(us)), "odo_depth_filter_time_dev")
+        return us.value
+
+    def download(self, out_dev=None):
+        """An output frame on the host (ordered behind the run on the context's stream): rows x cols uint16."""
+        out = np.empty((self.rows, self.cols), np.uint16)
+        L.check(self.lib.odo_dev_download(self._ctx, out.ctypes.data_as(C.c_void_p), self._out if out_dev is None else out_dev,
+                                          out.nbytes), "odo_dev_download")
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.odo_depth_filter_destroy(self.h)
+            self.h = None
+            if self._out is not None:
+                self.lib.odo_dev_free(self._ctx, self._out)
+                self._out = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def write_ply(path, xyzi):
     """(N, 4) float32 x, y, z, intensity -> binary little-endian PLY with float x y z and uchar red green blue (grey)."""
     xyzi = np.asarray(xyzi, np.float32).reshape(-1, 4)

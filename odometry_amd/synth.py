@@ -245,17 +245,43 @@ def sensor_depth(Z, depth_scale=1000.0, max_range=30.0):
     return np.where(ok, raw, 0).astype(np.uint16)
 
 
+KINECT_AXIAL_NOISE = (0.0012, 0.0019, 0.4)   # sigma(z) = 1.2 mm + 1.9 mm (z - 0.4 m)^2: the published Kinect axial noise model
+
+
+def sensor_noise(Z, rng, noise=KINECT_AXIAL_NOISE, max_range=30.0):
+    """Z (metres) with a depth sensor's axial noise added, in front of sensor_depth: Gaussian, zero mean, standard deviation
+    sigma(z) = a + b (z - z0)^2 metres with noise = (a, b, z0). rng: a numpy Generator (one standard normal per pixel is drawn,
+    whatever Z holds). Pixels beyond max_range (where sensor_depth has no reading, and the model's sigma would be tens of metres)
+    and pixels that are not finite stay as they are; a noisy depth below 0 is 0, which sensor_depth turns into "no reading"."""
+    Z = np.asarray(Z, np.float64)
+    a, b, z0 = noise
+    n = rng.standard_normal(Z.shape)
+    keep = ~np.isfinite(Z) | (Z > max_range)
+    Zs = np.where(keep, 0.0, Z)
+    return np.where(keep, Z, np.maximum(Zs + (a + b * (Zs - z0) ** 2) * n, 0.0))
+
+
+def depth_noise_rng(depth_noise, k):
+    """The generator of frame k's noise: depth_noise = seed, or (seed, (a, b, z0)). One generator per frame, so that a frame's
+    noise does not depend on which other frames were rendered."""
+    seed, noise = depth_noise if isinstance(depth_noise, tuple) else (depth_noise, KINECT_AXIAL_NOISE)
+    return np.random.default_rng([0x0D0E77E7, int(seed), int(k)]), noise
+
+
 def make_rgbd_sequence(n_frames, seed=0, drive="natural", fwd_range=(0.1, 0.2), depth_scale=1000.0, max_range=30.0, rows=TUM_ROWS,
-                       cols=TUM_COLS, f=TUM_F, cx=TUM_CX, cy=TUM_CY):
+                       cols=TUM_COLS, f=TUM_F, cx=TUM_CX, cy=TUM_CY, depth_noise=None):
     """An RGB-D drive: grey frames of the named drive's scene (Scene.render) and the sensor's depth frames (sensor_depth), along the
-    drive's trajectory with fwd_range metres per frame. TUM-shaped by default. Returns dict(gray=[...], depth=[uint16 ...],
+    drive's trajectory with fwd_range metres per frame. TUM-shaped by default. depth_noise: None, a noise seed, or (seed, (a, b,
+    z0)): sensor_noise on every frame's Z in front of sensor_depth. Returns dict(gray=[...], depth=[uint16 ...],
     poses=[c2w ...], K=dict(f0, cx0, cy0), depth_scale, max_range)."""
     scene = drive_scene(drive, seed)
     kw = {k: v for k, v in DRIVES[drive].items() if k not in ("scene", "fwd_range")}
     poses = trajectory(n_frames, seed, fwd_range=fwd_range, **kw)
     out = dict(gray=[], depth=[], poses=poses, K=dict(f0=f, cx0=cx, cy0=cy), depth_scale=depth_scale, max_range=max_range)
-    for T in poses:
+    for k, T in enumerate(poses):
         img, Z = scene.render(T, rows, cols, f, cx, cy, 0.0)
+        if depth_noise is not None:
+            Z = sensor_noise(Z, *depth_noise_rng(depth_noise, k), max_range=max_range)
         out["gray"].append(img)
         out["depth"].append(sensor_depth(Z, depth_scale, max_range))
     return out
@@ -292,12 +318,13 @@ def colour_from_gray(gray, channels=3, bgr=False, tint_seed=None):
 
 def make_raw_rgbd_sequence(n_frames, seed=0, drive="natural", fwd_range=(0.1, 0.2), depth_scale=1000.0, max_range=30.0, rows=TUM_ROWS,
                            cols=TUM_COLS, f=TUM_F, cx=TUM_CX, cy=TUM_CY, depth_size=None, depth_f=None, depth_c=None,
-                           colour_from_depth=None, channels=3, bgr=False, tint_seed=None, frames=None):
+                           colour_from_depth=None, channels=3, bgr=False, tint_seed=None, frames=None, depth_noise=None):
     """What an RGB-D sensor delivers along the drive of make_rgbd_sequence: per frame an interleaved uint8 colour frame rendered at
     the colour camera (rows x cols, f, cx, cy; colour_from_gray of the grey rendering) and a uint16 depth frame rendered AT THE DEPTH
     IMAGER: depth_size = (rows, cols), focal length depth_f, principal point depth_c = (cx, cy) (default: the image centre), pose
     T @ colour_from_depth (4x4, P_c = R P_d + t; default identity). Defaults make the depth imager the colour camera.
-    frames: the frame indices to render (default all). Returns dict(colour=[...], raw_depth=[...], gray=[fp32 grey renderings],
+    frames: the frame indices to render (default all). depth_noise: as make_rgbd_sequence, on the depth imager's Z (depth_gt stays
+    clean). Returns dict(colour=[...], raw_depth=[...], gray=[fp32 grey renderings],
     depth_gt=[the registered ground truth: sensor_depth of the colour camera's Z], frames=[indices], poses (all n_frames), K,
     depth_K=(fx, fy, cx, cy), colour_from_depth, depth_scale, max_range)."""
     scene = drive_scene(drive, seed)
@@ -319,6 +346,8 @@ def make_raw_rgbd_sequence(n_frames, seed=0, drive="natural", fwd_range=(0.1, 0.
         T = poses[k]
         img, Z = scene.render(T, rows, cols, f, cx, cy, 0.0)
         _, Zd = scene.render(T @ E, drows, dcols, fd, cxd, cyd, 0.0)
+        if depth_noise is not None:
+            Zd = sensor_noise(Zd, *depth_noise_rng(depth_noise, k), max_range=max_range)
         out["gray"].append(img)
         out["colour"].append(colour_from_gray(img, channels, bgr, tint_seed))
         out["raw_depth"].append(sensor_depth(Zd, depth_scale, max_range))
