@@ -947,6 +947,42 @@ int odo_volume_shift_time(odo_volume* v, const int d[3], int reps, float us[6]);
  * else. *n_changed = bytes behind the store's last point, guard included, that no longer hold 0xAB (waits): 0 until the store is
  * first emptied, unless a spill wrote where it must not. */
 int odo_debug_volume_spill_guard(odo_volume* v, long* n_changed);
+/* Mesh store: the leaving slab as triangles, so that the store and the window's mesh together are a mesh of
+ * the whole drive. The staying voxels form a box [lo_c, hi_c] on every axis (empty when |d_c| >= n_c on one). The cell with low
+ * corner c, all eight corners inside the grid, is spilled iff at least one corner leaves: on some axis c < lo or c + 1 > hi. An edge
+ * (a, e), b = a + d_e, e one of odo_volume_mesh's seven directions, is spilled iff it is an edge of at least one spilled cell of the
+ * grid, whatever the data: per axis the candidate low corners are {a} where d_e has a 1, else {a - 1, a} within [0, n - 2], and the
+ * edge is spilled iff some axis has a candidate with c < lo or c + 1 > hi. With a mesh store a shift first appends, from the PRE-shift
+ * grid, every vertex of odo_volume_mesh whose edge is spilled and every triangle of odo_volume_mesh whose cell is spilled: positions,
+ * normals, weights and colours bit for bit the mesh's, vertices in (voxel in raster order, e) order, triangles in (cell, tetrahedron,
+ * triangle) order with the mesh's winding and smallest-index-first rotation. A triangle's three indices are the STORE's: vertices
+ * already in the store + rank of the vertex among this spill's. As multisets of triangles, mesh before = spill + mesh after; the
+ * vertices of the seam between them are in both, and they are not welded: later integrations move the window's copy, so the seam
+ * can open by the TSDF's later updates.
+ * A spill is appended whole or not at all: if its vertices or its triangles do not fit what is left of either capacity, nothing of it
+ * is written and both of its counts go to the dropped totals; later, smaller spills are still appended. The store is therefore a
+ * complete mesh of every spill it holds at any time. (odo_volume_mesh differs: it never remaps indices, and with a vertex capacity
+ * below the total its triangles name vertices that were not written.)
+ * Five launches in front of the shift's (six with colour), no atomics, no host wait; only the slab is walked: a thread whose voxel is
+ * more than one voxel from every leaving voxel loads nothing. The mesh's scratch (5 B per voxel) is shared with odo_volume_mesh. */
+/* Allocates the mesh store: float4 xyz0 and nrmw (and uint8[4] rgba when the volume has colour: enable it first) per vertex, three
+ * int32 per triangle; each capacity 1 .. 2^28. Also allocates the mesh's scratch if no mesh was asked for yet, so that no shift
+ * allocates. Once, and not while attached to a tracker. Independent of odo_volume_enable_spill: a volume may have either or both. */
+int odo_volume_enable_spill_mesh(odo_volume* v, long vertex_capacity, long triangle_capacity);
+/* The store's mesh (waits for everything pending). *n_vertices, *n_triangles and dropped[2] (may be NULL: vertices, triangles that
+ * qualified since the store was last emptied and were not written) are set first, in every case below. Both capacities 0: nothing
+ * else. Otherwise the whole store is copied, or the call is refused: -1 and nothing copied or cleared when either capacity is below
+ * the store's count, because a cut would leave triangles without their vertices. rgba may be NULL (non-NULL is refused on a store
+ * without colours). clear != 0 empties the store afterwards. Legal while attached. */
+int odo_volume_spill_mesh(odo_volume* v, long vertex_capacity, long triangle_capacity, float* xyz0, float* nrmw, uint8_t* rgba,
+                          int32_t* tri, long* n_vertices, long* n_triangles, long dropped[2], int clear);
+/* Event timing (diagnostic, tools/volume_cost.py shift --mesh; waits; refused while attached or without a mesh store): as
+ * odo_volume_shift_time, us[0 .. 4] = the mesh spill's count, scan, vertices, triangles and colour (0 without colour) for d. The
+ * counters do not move, so the store's contents and counts read the same afterwards. */
+int odo_volume_spill_mesh_time(odo_volume* v, const int d[3], int reps, float us[5]);
+/* TEST ONLY, as odo_debug_volume_spill_guard: 64 guard items behind each of the mesh store's buffers, 0xAB fill; *n_changed = bytes
+ * behind the store's last vertex and last triangle, guards included, that no longer hold 0xAB (waits). */
+int odo_debug_volume_spill_mesh_guard(odo_volume* v, long* n_changed);
 /* Following a camera. The host works in fp64 from the fp32 entries of the camera-to-world pose [R | t]: p = t + focus * R[:, 2] (the
  * point `focus` metres along the optical axis); e_c = (p_c - (origin_c + 0.5 * n_c * vs)) / vs, its distance from the window's centre
  * in voxels; if max |e_c| < threshold then d = 0, else d_c = nearbyint(e_c) (ties to even) clamped to +-n_c. */

@@ -304,6 +304,11 @@ SIGNATURES = {
     "odo_volume_spill_points": (C.c_int, [_vp, C.c_long, _fp, _fp, _u8p, C.POINTER(C.c_long), C.POINTER(C.c_long), C.c_int]),
     "odo_volume_shift_time": (C.c_int, [_vp, _ip, C.c_int, _fp]),
     "odo_debug_volume_spill_guard": (C.c_int, [_vp, C.POINTER(C.c_long)]),   # test only: not for integrators (include/odometry_hip.h)
+    "odo_volume_enable_spill_mesh": (C.c_int, [_vp, C.c_long, C.c_long]),
+    "odo_volume_spill_mesh": (C.c_int, [_vp, C.c_long, C.c_long, _fp, _fp, _u8p, C.POINTER(C.c_int32), C.POINTER(C.c_long),
+                                        C.POINTER(C.c_long), C.POINTER(C.c_long), C.c_int]),
+    "odo_volume_spill_mesh_time": (C.c_int, [_vp, _ip, C.c_int, _fp]),
+    "odo_debug_volume_spill_mesh_guard": (C.c_int, [_vp, C.POINTER(C.c_long)]),   # test only, as odo_debug_volume_spill_guard
     "odo_volume_set_follow": (C.c_int, [_vp, C.POINTER(VolumeFollowParams)]),
     "odo_volume_follow": (C.c_int, [_vp, _fp, _ip]),
     "odo_depth_filter_create": (C.c_int, [_vp, C.POINTER(DepthFilterParams), C.POINTER(_vp)]),

@@ -915,6 +915,7 @@ class TsdfVolume:
         self._follow = None           # (focus, threshold) while set_follow is on
         self._spill_capacity = 0
         self._spill_colour = False
+        self._spill_mesh_colour = False
         p = L.VolumeParams()
         p.nx, p.ny, p.nz = dims
         p.voxel_size = voxel_size
@@ -1420,15 +1421,53 @@ class TsdfVolume:
         else:
             write_ply_normals(path, cols[0], cols[1])
 
-    def save_mesh_ply(self, path):
+    def enable_spill_mesh(self, vertex_capacity, triangle_capacity):
+        """Adds the mesh store: room for the vertices and triangles (1 .. 2^28 each) of the mesh of every slab that shifts destroy (32 B
+        per vertex, 36 B with colour: enable_colour first; 12 B per triangle). Once, and not while attached to a tracker. It does
+        not need enable_spill, and a volume may have both stores."""
+        L.check(self.lib.odo_volume_enable_spill_mesh(self.h, int(vertex_capacity), int(triangle_capacity)), "odo_volume_enable_spill_mesh")
+        self._spill_mesh_colour = self.has_colour   # (a store made before enable_colour has no colours)
+
+    def spilled_mesh(self, clear=False, colour=False, with_dropped=False):
+        """The mesh store as mesh() returns a mesh: (n, 4) float32 x, y, z, e; (n, 4) float32 nx, ny, nz, weight; (m, 3) int32 indices
+        into these vertices (colour: also (n, 4) uint8 R, G, B, A; with_dropped: also (vertices, triangles) of the spills that did
+        not fit and were left out whole). clear=True empties the store afterwards. Waits for everything pending."""
+        n, m, d = C.c_long(0), C.c_long(0), (C.c_long * 2)()
+        L.check(self.lib.odo_volume_spill_mesh(self.h, 0, 0, None, None, None, None, C.byref(n), C.byref(m), d, 0), "odo_volume_spill_mesh")
+        nv, nt = max(n.value, 1), max(m.value, 1)   # (exact buffers: this thread enqueues nothing between the two calls)
+        xyz0, nrmw, tri = np.zeros((nv, 4), np.float32), np.zeros((nv, 4), np.float32), np.zeros((nt, 3), np.int32)
+        rgba = np.zeros((nv, 4), np.uint8) if colour else None
+        L.check(self.lib.odo_volume_spill_mesh(self.h, nv, nt, _fp(xyz0), _fp(nrmw), rgba.ctypes.data_as(L._u8p) if colour else None,
+                                               tri.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n), C.byref(m), d, int(bool(clear))),
+                "odo_volume_spill_mesh")
+        out = (xyz0[:n.value].copy(), nrmw[:n.value].copy(), tri[:m.value].copy()) + ((rgba[:n.value].copy(),) if colour else ())
+        return out + ((d[0], d[1]),) if with_dropped else out
+
+    def spill_mesh_time(self, d, reps=50):
+        """Event timing of the mesh spill for a shift by d that is not applied: microseconds per launch, means over reps, of (count,
+        scan, vertices, triangles, colour); the last is 0 without colour. The store's contents and counts stay as they are."""
+        d = (C.c_int * 3)(*[int(x) for x in d])
+        us = np.zeros(5, np.float32)
+        L.check(self.lib.odo_volume_spill_mesh_time(self.h, d, int(reps), _fp(us)), "odo_volume_spill_mesh_time")
+        return tuple(float(x) for x in us)
+
+    def save_mesh_ply(self, path, spill=False):
         """Binary little-endian PLY of the mesh: float x y z nx ny nz per vertex (and uchar red green blue when the volume has
-        colour), three int indices per face."""
-        if self.has_colour:
-            xyz0, nrmw, tri, rgba = self.mesh(colour=True)
-            write_ply_mesh(path, xyz0, nrmw, tri, rgb=rgba)
+        colour), three int indices per face. spill=True: the mesh store's mesh in front of the window's, whose indices are offset
+        by the store's vertices (the whole surface of a volume that moved; the seam's vertices are in both and are not welded)."""
+        colour = self.has_colour
+        if spill and colour and not self._spill_mesh_colour:
+            raise ValueError("save_mesh_ply(spill=True): the mesh store was enabled before enable_colour and holds no colours, the "
+                             "mesh has them; call enable_colour before enable_spill_mesh")
+        parts = self.mesh(colour=True) if colour else self.mesh()
+        if spill:
+            store = self.spilled_mesh(colour=colour)
+            parts = tuple(np.concatenate([a, b + len(store[0])]) if i == 2 else np.concatenate([a, b])
+                          for i, (a, b) in enumerate(zip(store, parts)))
+        if colour:
+            write_ply_mesh(path, parts[0], parts[1], parts[2], rgb=parts[3])
         else:
-            xyz0, nrmw, tri = self.mesh()
-            write_ply_mesh(path, xyz0, nrmw, tri)
+            write_ply_mesh(path, parts[0], parts[1], parts[2])
 
     def close(self):
         if getattr(self, "h", None):

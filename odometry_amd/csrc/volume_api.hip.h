@@ -59,6 +59,12 @@ struct odo_volume {
   float4 *d_spill_xyz0, *d_spill_nrmw;
   uint32_t* d_spill_rgba;       // with colour
   VolSpillCounters* d_spill_ctr;
+  // the mesh store (odo_volume_enable_spill_mesh, volume_shift_api.hip.h; nothing below is allocated without it)
+  long smesh_vertex_capacity, smesh_triangle_capacity;   // 0: no store
+  float4 *d_smesh_xyz0, *d_smesh_nrmw;
+  uint32_t* d_smesh_rgba;       // with colour
+  int* d_smesh_tri;
+  VolSpillMeshCounters* d_smesh_ctr;
   int follow;                   // 1: odo_volume_set_follow's parameters are set
   odo_volume_follow_params fp;
 };
@@ -67,7 +73,8 @@ static int volume_release(odo_volume* v) {
   void* ps[] = {v->d_vox, v->d_blk, v->d_ctr, v->d_wave, v->d_off, v->d_cnt, v->d_xyz0, v->d_nrmw,
                 v->d_mesh_mask, v->d_mesh_base, v->d_mesh_cnt, v->d_mesh_off, v->d_mesh_ctr, v->d_mesh_xyz0, v->d_mesh_nrmw, v->d_mesh_tri,
                 v->d_col, v->d_rgba, v->d_mesh_rgba, v->d_ray_depth, v->d_ray_raw, v->d_ray_nrmw, v->d_ray_rgba,
-                v->d_vox2, v->d_col2, v->d_spill_xyz0, v->d_spill_nrmw, v->d_spill_rgba, v->d_spill_ctr};
+                v->d_vox2, v->d_col2, v->d_spill_xyz0, v->d_spill_nrmw, v->d_spill_rgba, v->d_spill_ctr,
+                v->d_smesh_xyz0, v->d_smesh_nrmw, v->d_smesh_rgba, v->d_smesh_tri, v->d_smesh_ctr};
   for (void* p : ps) if (p) (void)hipFree(p);
   if (v->ev_last) (void)hipEventDestroy(v->ev_last);
   if (v->own) (void)hipStreamDestroy(v->own);
@@ -98,6 +105,7 @@ static int volume_reset(odo_volume* v) {
   if (v->colour) HIP_OK(hipMemsetAsync(v->d_col, 0, sizeof(uint32_t) * (size_t)v->n_vox, v->own));
   HIP_OK(hipMemsetAsync(v->d_ctr, 0, sizeof(VolCounters), v->own));
   if (v->d_spill_ctr) HIP_OK(hipMemsetAsync(v->d_spill_ctr, 0, sizeof(VolSpillCounters), v->own));   // (the window stays where it is)
+  if (v->d_smesh_ctr) HIP_OK(hipMemsetAsync(v->d_smesh_ctr, 0, sizeof(VolSpillMeshCounters), v->own));
   v->n_frames = 0;
   return volume_mark(v, v->own);
 }
@@ -374,6 +382,26 @@ extern "C" int odo_volume_upload(odo_volume* v, const int16_t* q, const uint16_t
   return 0;
 }
 
+// The mesh's scratch (5 B per voxel and the per-block counts): allocated by the first of odo_volume_mesh and
+// odo_volume_enable_spill_mesh, which share it on the volume's own stream; kept until destroy.
+static int volume_mesh_scratch(const char* who, odo_volume* v) {
+  if (v->d_mesh_ctr) return 0;
+  const int nblk = (int)((v->n_vox + kMeshBlock - 1) / kMeshBlock);
+  bool ok = hipMalloc((void**)&v->d_mesh_mask, (size_t)v->n_vox) == hipSuccess &&
+            hipMalloc((void**)&v->d_mesh_base, sizeof(uint32_t) * (size_t)v->n_vox) == hipSuccess &&
+            hipMalloc((void**)&v->d_mesh_cnt, sizeof(unsigned) * 2 * (size_t)nblk) == hipSuccess &&
+            hipMalloc((void**)&v->d_mesh_off, sizeof(unsigned long long) * 2 * (size_t)nblk) == hipSuccess &&
+            hipMalloc((void**)&v->d_mesh_ctr, sizeof(MeshCounters)) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    void* ps[] = {v->d_mesh_mask, v->d_mesh_base, v->d_mesh_cnt, v->d_mesh_off, v->d_mesh_ctr};
+    for (void* p : ps) if (p) (void)hipFree(p);
+    v->d_mesh_mask = nullptr; v->d_mesh_base = nullptr; v->d_mesh_cnt = nullptr; v->d_mesh_off = nullptr; v->d_mesh_ctr = nullptr;
+    return fail("%s: device allocation failed (scratch for %ld voxels)", who, v->n_vox);
+  }
+  return 0;
+}
+
 // odo_volume_mesh and, with_colour, odo_volume_mesh_colour (one launch more: the vertices' colours, skipped when no vertex is written).
 static int volume_mesh(const char* who, odo_volume* v, long vertex_capacity, long triangle_capacity, float* xyz0, float* nrmw, uint8_t* rgba,
                        int32_t* tri, long counts[4], bool with_colour) {
@@ -383,20 +411,7 @@ static int volume_mesh(const char* who, odo_volume* v, long vertex_capacity, lon
   if (with_colour && !v->colour) return fail("%s: the volume has no colour grid (odo_volume_enable_colour first)", who);
   if (volume_sync(v)) return -1;
   const int nblk = (int)((v->n_vox + kMeshBlock - 1) / kMeshBlock);
-  if (!v->d_mesh_ctr) {
-    bool ok = hipMalloc((void**)&v->d_mesh_mask, (size_t)v->n_vox) == hipSuccess &&
-              hipMalloc((void**)&v->d_mesh_base, sizeof(uint32_t) * (size_t)v->n_vox) == hipSuccess &&
-              hipMalloc((void**)&v->d_mesh_cnt, sizeof(unsigned) * 2 * (size_t)nblk) == hipSuccess &&
-              hipMalloc((void**)&v->d_mesh_off, sizeof(unsigned long long) * 2 * (size_t)nblk) == hipSuccess &&
-              hipMalloc((void**)&v->d_mesh_ctr, sizeof(MeshCounters)) == hipSuccess;
-    if (!ok) {
-      (void)hipGetLastError();
-      void* ps[] = {v->d_mesh_mask, v->d_mesh_base, v->d_mesh_cnt, v->d_mesh_off, v->d_mesh_ctr};
-      for (void* p : ps) if (p) (void)hipFree(p);
-      v->d_mesh_mask = nullptr; v->d_mesh_base = nullptr; v->d_mesh_cnt = nullptr; v->d_mesh_off = nullptr; v->d_mesh_ctr = nullptr;
-      return fail("%s: device allocation failed (scratch for %ld voxels)", who, v->n_vox);
-    }
-  }
+  if (volume_mesh_scratch(who, v)) return -1;
   if (volume_grow((void**)&v->d_mesh_xyz0, &v->mesh_xyz0_capacity, vertex_capacity, sizeof(float4), who, "vertices") ||
       volume_grow((void**)&v->d_mesh_nrmw, &v->mesh_nrmw_capacity, vertex_capacity, sizeof(float4), who, "vertices") ||
       volume_grow((void**)&v->d_mesh_tri, &v->mesh_triangle_capacity, triangle_capacity, 3 * sizeof(int32_t), who, "triangles") ||

@@ -12,7 +12,8 @@
 //   triangles  per live cell block offset + rank in the block; per triangle vertex the owner voxel's base + rank of the edge in
 //              the owner's mask; wound by the table, rotated to the smallest index first, three int32 stored.
 // Output order = (voxel in raster order, e) and (cell in raster order, tetrahedron, triangle); nothing depends on timing.
-// Scratch: 5 B per voxel (base + mask), 31 MB for a 240 x 128 x 200 grid, allocated by the first mesh call, released with the volume.
+// Scratch: 5 B per voxel (base + mask), 31 MB for a 240 x 128 x 200 grid, allocated by the first mesh call or by
+// odo_volume_enable_spill_mesh (the mesh of the leaving slab, volume_shift.hip.h, uses it on the same stream), released with the volume.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -5,42 +5,12 @@
 // table of volume_mesh_table.h. Nothing is combined across threads but counts.
 #include <hip/hip_runtime.h>
 #include "volume_mesh.hip.h"
-#include "volume_mesh_table.h"
+#include "volume_mesh_emit.hip.h"   // mesh_voxel: shared with the mesh of the leaving slab
 #include "volume_scan.hip.h"
 
 namespace odo {
 
 __constant__ MtetTable c_mtet = make_mtet_table();   // 672 bytes, derived at compile time
-
-// What the count and the triangle pass both need of voxel v (< n): the 7-bit mask of its edges that carry a vertex, and of its cell
-// whether it is live (all eight corners observed) and which corners are positive. A neighbour outside the grid is never loaded.
-__device__ __forceinline__ void mesh_voxel(const VolGrid& g, int v, unsigned* edge_mask, bool* live, unsigned* pos8) {
-  *edge_mask = 0;
-  *live = false;
-  *pos8 = 0;
-  const uint32_t va = g.vox[v];
-  if (vox_w(va) == 0) return;   // no edge of an unobserved voxel carries a vertex, and its cell is not live
-  int i, j, k;
-  vox_ijk(g, v, &i, &j, &k);
-  const bool in_x = i + 1 < g.nx, in_y = j + 1 < g.ny, in_z = k + 1 < g.nz;
-  const bool pa = vox_q(va) > 0;
-  unsigned mask = 0, pos = pa ? 1u : 0u, observed = 1u;
-#pragma unroll
-  for (int e = 0; e < 7; e++) {
-    const int c = mtet_dir_offset(e);
-    const bool inside = (!(c & 1) || in_x) && (!(c & 2) || in_y) && (!(c & 4) || in_z);
-    if (!inside) continue;
-    const uint32_t vb = g.vox[vox_corner_word(g, v, c)];
-    if (vox_w(vb) == 0) continue;
-    const bool pb = vox_q(vb) > 0;
-    observed |= 1u << c;
-    pos |= (pb ? 1u : 0u) << c;
-    mask |= (pa != pb ? 1u : 0u) << e;
-  }
-  *edge_mask = mask;
-  *live = observed == 0xffu;
-  *pos8 = pos;
-}
 
 __global__ void __launch_bounds__(kMeshBlock) volume_mesh_count_kernel(VolMeshArgs a) {
   __shared__ unsigned sh[2][kMeshBlock / 64];

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "volume.hip.h"
+#include "volume_mesh.hip.h"
 
 namespace odo {
 
@@ -45,6 +46,33 @@ struct VolSpillArgs {
   uint32_t* rgba;            // [capacity], nullptr: no colour
   VolSpillCounters* sc;
 };
+
+// ---- the mesh of the leaving slab -----------------------------------------------------------------------------
+// One mesh spill, in front of the shift when the volume has a mesh store = five launches (six with colour), the mesh's shape over the
+// PRE-shift grid with volume_shift_math.h's two predicates ANDed in: count (edge mask & "edge spilled", triangle count * "cell spilled"),
+// scan (both block sums; the spill's two counts are left in the store's counters), vertices and triangles (both take their base from
+// the store's `written` counters, so a triangle's indices are the store's), colour, advance (one thread). No host wait.
+// Work follows the slab: a thread whose voxel is more than one voxel from every leaving voxel (shift_near) loads nothing, and a block
+// without such a voxel returns after writing its two zero counts; block order and output order stay the mesh's.
+// A spill is appended whole or not at all: every emitting block reads the same four counters and writes nothing unless both of the
+// spill's counts fit what is left, so the store is a complete mesh of every spill it holds. (odo_volume_mesh differs: it never remaps
+// indices and its triangles may name vertices beyond the vertex capacity.)
+struct VolSpillMeshCounters {
+  unsigned long long v_written, t_written;   // vertices / triangles in the store (<= the capacities)
+  unsigned long long v_total, t_total;       // those that qualified since enable / clear; total - written were dropped
+  unsigned long long v_pending, t_pending;   // the counts of the last spill enqueued (scan -> emit, advance)
+};
+
+struct VolSpillMeshArgs {
+  VolMeshArgs a;             // the pre-shift grid and the mesh's scratch; capacities, xyz0, nrmw, tri = the store's; ctr unused
+  int dx, dy, dz;
+  const uint32_t* col;       // the pre-shift colour grid, nullptr: no colour
+  uint32_t* rgba;            // [vertex_capacity], nullptr: no colour
+  VolSpillMeshCounters* sc;
+};
+
+void launch_volume_spill_mesh(const VolSpillMeshArgs& a, hipStream_t s);   // count, scan, vertices, triangles, colour, advance
+void launch_volume_spill_mesh_stage(const VolSpillMeshArgs& a, int stage, hipStream_t s);   // count (0) .. colour (4): timing
 
 void launch_volume_shift(const VolShiftArgs& a, hipStream_t s);
 void launch_volume_spill(const VolSpillArgs& a, hipStream_t s);   // count, scan, scatter, advance

@@ -3,8 +3,9 @@
 // the surface points a shift would destroy are first appended to a device-resident store. Included by odometry_hip.hip behind
 // volume_api.hip.h (the volume's object) and before tracker.hip.h (an attached tracker follows before it integrates).
 //
-// Nothing here waits for the device but odo_volume_spill_points (and the two diagnostics, odo_volume_shift_time and
-// odo_debug_volume_spill_guard): a spill and a shift are five launches on the volume's own stream.
+// Nothing here waits for the device but odo_volume_spill_points and odo_volume_spill_mesh (and the diagnostics, odo_volume_shift_time,
+// odo_volume_spill_mesh_time and the two guard hooks): a spill and a shift are five launches on the volume's own stream, a mesh spill
+// (odo_volume_enable_spill_mesh) five or six more in front of the shift's.
 // The shift writes into the grids' second buffers and the host swaps the pointers when it enqueues: launches enqueued earlier hold
 // the old pointers by value and are ordered in front by volume_order_on / volume_mark, and every later launcher reads v->d_vox,
 // v->d_col and v->p.origin when it is called.
@@ -50,6 +51,21 @@ static VolSpillArgs volume_spill_args(odo_volume* v, const int d[3]) {
   return sa;
 }
 
+static VolSpillMeshArgs volume_spill_mesh_args(odo_volume* v, const int d[3]) {
+  VolSpillMeshArgs sa;
+  memset(&sa, 0, sizeof(sa));
+  sa.a.g = volume_grid(v);
+  sa.a.n = (int)v->n_vox; sa.a.nblk = (int)((v->n_vox + kMeshBlock - 1) / kMeshBlock);
+  sa.a.vertex_capacity = v->smesh_vertex_capacity; sa.a.triangle_capacity = v->smesh_triangle_capacity;
+  sa.a.edge_mask = v->d_mesh_mask; sa.a.vertex_base = v->d_mesh_base; sa.a.blk = v->d_mesh_cnt; sa.a.blk_off = v->d_mesh_off;
+  sa.a.xyz0 = v->d_smesh_xyz0; sa.a.nrmw = v->d_smesh_nrmw; sa.a.tri = v->d_smesh_tri;
+  sa.dx = d[0]; sa.dy = d[1]; sa.dz = d[2];
+  // (a store made before odo_volume_enable_colour has no colours: its vertices are spilled without them)
+  sa.col = v->d_smesh_rgba ? v->d_col : nullptr; sa.rgba = v->d_smesh_rgba;
+  sa.sc = v->d_smesh_ctr;
+  return sa;
+}
+
 static VolShiftArgs volume_shift_args(odo_volume* v, const int d[3]) {
   VolShiftArgs a;
   memset(&a, 0, sizeof(a));
@@ -71,6 +87,10 @@ static int volume_shift(const char* who, odo_volume* v, const int d[3]) {
   if (volume_order_on(v, v->own)) return -1;
   if (v->spill_capacity > 0) {
     launch_volume_spill(volume_spill_args(v, d), v->own);
+    HIP_OK(hipGetLastError());
+  }
+  if (v->smesh_vertex_capacity > 0) {
+    launch_volume_spill_mesh(volume_spill_mesh_args(v, d), v->own);
     HIP_OK(hipGetLastError());
   }
   launch_volume_shift(volume_shift_args(v, d), v->own);
@@ -232,6 +252,151 @@ extern "C" int odo_debug_volume_spill_guard(odo_volume* v, long* n_changed) {
   const size_t bytes[3] = {sizeof(float4) * points, sizeof(float4) * points, sizeof(uint32_t) * points};
   long bad = 0;
   for (int b = 0; b < 3; b++) {
+    if (!at[b]) continue;
+    HIP_OK(hipMemcpyAsync(host.data(), at[b], bytes[b], hipMemcpyDeviceToHost, v->own));
+    HIP_OK(hipStreamSynchronize(v->own));
+    for (size_t i = 0; i < bytes[b]; i++) bad += host[i] != 0xAB;
+  }
+  *n_changed = bad;
+  return 0;
+}
+
+// ---- the mesh store ---------------------------------------------------------------------------------------
+// As the point store: every buffer has a guard of kSpillGuard items behind its capacity and is filled with 0xAB once. The mesh's
+// scratch is allocated here when no mesh was asked for yet, so that no shift (no frame call of an attached tracker) allocates.
+extern "C" int odo_volume_enable_spill_mesh(odo_volume* v, long vertex_capacity, long triangle_capacity) {
+  const char* who = "odo_volume_enable_spill_mesh";
+  if (!v) return fail("%s: NULL volume", who);
+  if (vertex_capacity < 1 || vertex_capacity > (1L << 28) || triangle_capacity < 1 || triangle_capacity > (1L << 28))
+    return fail("%s: capacities %ld, %ld out of range (1 .. 2^28 each)", who, vertex_capacity, triangle_capacity);
+  if (v->smesh_vertex_capacity > 0) return fail("%s: the volume has a mesh store already", who);
+  if (v->attached) return fail("%s: the volume is attached to a tracker (odo_tracker_attach_volume(t, NULL) first)", who);
+  HIP_OK(hipSetDevice(v->device));
+  if (volume_mesh_scratch(who, v)) return -1;
+  const size_t nv = (size_t)(vertex_capacity + kSpillGuard), nt = (size_t)(triangle_capacity + kSpillGuard);
+  float4 *xyz0 = nullptr, *nrmw = nullptr;
+  uint32_t* rgba = nullptr;
+  int* tri = nullptr;
+  VolSpillMeshCounters* ctr = nullptr;
+  bool ok = hipMalloc((void**)&xyz0, sizeof(float4) * nv) == hipSuccess && hipMalloc((void**)&nrmw, sizeof(float4) * nv) == hipSuccess &&
+            (!v->colour || hipMalloc((void**)&rgba, sizeof(uint32_t) * nv) == hipSuccess) &&
+            hipMalloc((void**)&tri, 3 * sizeof(int) * nt) == hipSuccess && hipMalloc((void**)&ctr, sizeof(VolSpillMeshCounters)) == hipSuccess;
+  ok = ok && volume_order_on(v, v->own) == 0 && hipMemsetAsync(ctr, 0, sizeof(VolSpillMeshCounters), v->own) == hipSuccess &&
+       hipMemsetAsync(xyz0, 0xAB, sizeof(float4) * nv, v->own) == hipSuccess &&
+       hipMemsetAsync(nrmw, 0xAB, sizeof(float4) * nv, v->own) == hipSuccess &&
+       (!rgba || hipMemsetAsync(rgba, 0xAB, sizeof(uint32_t) * nv, v->own) == hipSuccess) &&
+       hipMemsetAsync(tri, 0xAB, 3 * sizeof(int) * nt, v->own) == hipSuccess && volume_mark(v, v->own) == 0;
+  if (!ok) {
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(v->own);
+    void* ps[] = {xyz0, nrmw, rgba, tri, ctr};
+    for (void* p : ps) if (p) (void)hipFree(p);
+    return fail("%s: device allocation failed (%ld vertices, %ld triangles)", who, vertex_capacity, triangle_capacity);
+  }
+  v->d_smesh_xyz0 = xyz0; v->d_smesh_nrmw = nrmw; v->d_smesh_rgba = rgba; v->d_smesh_tri = tri; v->d_smesh_ctr = ctr;
+  v->smesh_vertex_capacity = vertex_capacity; v->smesh_triangle_capacity = triangle_capacity;
+  return 0;
+}
+
+// Waits, then reads the store's counters.
+static int volume_spill_mesh_counters(odo_volume* v, VolSpillMeshCounters* c) {
+  if (volume_sync(v)) return -1;
+  HIP_OK(hipMemcpyAsync(c, v->d_smesh_ctr, sizeof(*c), hipMemcpyDeviceToHost, v->own));
+  HIP_OK(hipStreamSynchronize(v->own));
+  return 0;
+}
+
+extern "C" int odo_volume_spill_mesh(odo_volume* v, long vertex_capacity, long triangle_capacity, float* xyz0, float* nrmw, uint8_t* rgba,
+                                     int32_t* tri, long* n_vertices, long* n_triangles, long dropped[2], int clear) {
+  const char* who = "odo_volume_spill_mesh";
+  if (!v || !n_vertices || !n_triangles || vertex_capacity < 0 || vertex_capacity > (1L << 28) || triangle_capacity < 0 ||
+      triangle_capacity > (1L << 28) || (vertex_capacity > 0 && (!xyz0 || !nrmw)) || (triangle_capacity > 0 && !tri))
+    return fail("%s: bad arg (capacities 0 .. 2^28, buffers for `vertex_capacity` vertices and `triangle_capacity` triangles)", who);
+  if (v->smesh_vertex_capacity <= 0) return fail("%s: the volume has no mesh store (odo_volume_enable_spill_mesh first)", who);
+  if (rgba && !v->d_smesh_rgba)
+    return fail("%s: the store has no colours (odo_volume_enable_colour before odo_volume_enable_spill_mesh)", who);
+  VolSpillMeshCounters c;
+  if (volume_spill_mesh_counters(v, &c)) return -1;
+  *n_vertices = (long)c.v_written;
+  *n_triangles = (long)c.t_written;
+  if (dropped) { dropped[0] = (long)(c.v_total - c.v_written); dropped[1] = (long)(c.t_total - c.t_written); }
+  const bool query = vertex_capacity == 0 && triangle_capacity == 0;
+  if (!query && (c.v_written > (unsigned long long)vertex_capacity || c.t_written > (unsigned long long)triangle_capacity))
+    return fail("%s: the store holds %llu vertices and %llu triangles, the buffers %ld and %ld: a cut would leave triangles without "
+                "their vertices (nothing copied, nothing cleared; the counts are returned)", who, c.v_written, c.t_written,
+                vertex_capacity, triangle_capacity);
+  if (!query) {
+    const size_t nv = (size_t)c.v_written, nt = (size_t)c.t_written;
+    if (nv > 0) {
+      HIP_OK(hipMemcpyAsync(xyz0, v->d_smesh_xyz0, sizeof(float4) * nv, hipMemcpyDeviceToHost, v->own));
+      HIP_OK(hipMemcpyAsync(nrmw, v->d_smesh_nrmw, sizeof(float4) * nv, hipMemcpyDeviceToHost, v->own));
+      if (rgba) HIP_OK(hipMemcpyAsync(rgba, v->d_smesh_rgba, sizeof(uint32_t) * nv, hipMemcpyDeviceToHost, v->own));
+    }
+    if (nt > 0) HIP_OK(hipMemcpyAsync(tri, v->d_smesh_tri, 3 * sizeof(int32_t) * nt, hipMemcpyDeviceToHost, v->own));
+    HIP_OK(hipStreamSynchronize(v->own));
+  }
+  if (clear) {
+    HIP_OK(hipMemsetAsync(v->d_smesh_ctr, 0, sizeof(VolSpillMeshCounters), v->own));
+    if (volume_mark(v, v->own)) return -1;
+  }
+  return 0;
+}
+
+// Event timing of the mesh spill's five stages for d, as odo_volume_shift_time times the point spill's: batches of `reps` launches
+// between events. The advance kernel is not run, so the counters do not move: the emitting stages write the store behind its
+// counted items (or nothing, when the spill would not fit), and its contents and counts read the same afterwards.
+extern "C" int odo_volume_spill_mesh_time(odo_volume* v, const int d[3], int reps, float us[5]) {
+  const char* who = "odo_volume_spill_mesh_time";
+  if (!v || !d || !us) return fail("%s: NULL arg", who);
+  if (reps < 1 || reps > 10000) return fail("%s: reps 1 .. 10000", who);
+  if (v->smesh_vertex_capacity <= 0) return fail("%s: the volume has no mesh store (odo_volume_enable_spill_mesh first)", who);
+  if (v->attached) return fail("%s: the volume is attached to a tracker (odo_tracker_attach_volume(t, NULL) first)", who);
+  HIP_OK(hipSetDevice(v->device));
+  if (volume_order_on(v, v->own)) return -1;
+  const VolSpillMeshArgs sa = volume_spill_mesh_args(v, d);
+  hipStream_t s = v->own;
+  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool ok = true;
+  for (auto& e : ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+  if (ok) {
+    for (int st = 0; st < 5; st++) launch_volume_spill_mesh_stage(sa, st, s);   // (warm)
+    ok = hipEventRecord(ev[0], s) == hipSuccess;
+    for (int st = 0; st < 5; st++) {
+      for (int i = 0; i < reps; i++) launch_volume_spill_mesh_stage(sa, st, s);
+      ok = ok && hipEventRecord(ev[1 + st], s) == hipSuccess;
+    }
+    ok = ok && hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+    for (int q = 0; q < 5 && ok; q++) {
+      float ms = 0.0f;
+      ok = hipEventElapsedTime(&ms, ev[q], ev[q + 1]) == hipSuccess;
+      us[q] = q == 4 && !sa.col ? 0.0f : 1e3f * ms / (float)reps;
+    }
+  }
+  for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+  if (!ok) {
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(s);
+    return fail("%s: timing failed", who);
+  }
+  return volume_mark(v, s);
+}
+
+extern "C" int odo_debug_volume_spill_mesh_guard(odo_volume* v, long* n_changed) {
+  const char* who = "odo_debug_volume_spill_mesh_guard";
+  if (!v || !n_changed) return fail("%s: NULL arg", who);
+  if (v->smesh_vertex_capacity <= 0) return fail("%s: the volume has no mesh store (odo_volume_enable_spill_mesh first)", who);
+  VolSpillMeshCounters c;
+  if (volume_spill_mesh_counters(v, &c)) return -1;
+  const size_t vfrom = (size_t)std::min<unsigned long long>(c.v_written, (unsigned long long)v->smesh_vertex_capacity);
+  const size_t tfrom = (size_t)std::min<unsigned long long>(c.t_written, (unsigned long long)v->smesh_triangle_capacity);
+  const size_t nv = (size_t)(v->smesh_vertex_capacity + kSpillGuard) - vfrom, nt = (size_t)(v->smesh_triangle_capacity + kSpillGuard) - tfrom;
+  const void* at[4] = {v->d_smesh_xyz0 + vfrom, v->d_smesh_nrmw + vfrom, v->d_smesh_rgba ? v->d_smesh_rgba + vfrom : nullptr,
+                       v->d_smesh_tri + 3 * tfrom};
+  const size_t bytes[4] = {sizeof(float4) * nv, sizeof(float4) * nv, sizeof(uint32_t) * nv, 3 * sizeof(int32_t) * nt};
+  std::vector<uint8_t> host;
+  try { host.resize(std::max(bytes[0], bytes[3])); } catch (...) { return fail("out of memory"); }
+  long bad = 0;
+  for (int b = 0; b < 4; b++) {
     if (!at[b]) continue;
     HIP_OK(hipMemcpyAsync(host.data(), at[b], bytes[b], hipMemcpyDeviceToHost, v->own));
     HIP_OK(hipStreamSynchronize(v->own));

@@ -3,11 +3,12 @@
 // volume's store. The rules are volume_shift_math.h's, the points volume_math.h's and volume_colour_math.h's (fp32, one rounding per
 // operation: the unit is built with -ffp-contract=off and correctly rounded divide / sqrt), so a spilled point is bit for bit the
 // point odo_volume_extract / _extract_colour gives for the same edge of the pre-shift grid. include/odometry_hip.h, odo_volume_shift;
-// DESIGN.md section 9.9.
+// DESIGN.md section 9.9. Behind them the spill of the leaving slab's MESH into the volume's mesh store.
 #include <hip/hip_runtime.h>
 #include "volume_shift.hip.h"
 #include "volume_shift_math.h"
 #include "volume_colour_math.h"
+#include "volume_mesh_emit.hip.h"
 #include "volume_scan.hip.h"
 
 namespace odo {
@@ -190,6 +191,174 @@ void launch_volume_spill_stage(const VolSpillArgs& a, int stage, hipStream_t s) 
   if (stage == 0) hipLaunchKernelGGL(volume_spill_count_kernel, grid, block, 0, s, a);
   else if (stage == 1) hipLaunchKernelGGL(volume_spill_scan_kernel, dim3(1), dim3(kVolScanThreads), 0, s, a);
   else hipLaunchKernelGGL(volume_spill_scatter_kernel, grid, block, 0, s, a);
+}
+
+// ---- the mesh of the leaving slab ----------------------------------------------------------------------------------------------------
+// volume_mesh_kernels.hip's four passes (the device code is volume_mesh_emit.hip.h's, compiled by both units) over the pre-shift grid,
+// with the predicates of volume_shift_math.h ANDed in; see volume_shift.hip.h.
+__constant__ MtetTable c_spill_mtet = make_mtet_table();
+
+// Voxel v's coordinates and whether it is within one voxel of a leaving voxel. Arithmetic only: nothing is loaded.
+__device__ __forceinline__ bool spill_mesh_near(const VolSpillMeshArgs& sa, int v, int* i, int* j, int* k) {
+  const VolGrid& g = sa.a.g;
+  if (v >= sa.a.n) return false;
+  vox_ijk(g, v, i, j, k);
+  return shift_near(*i, *j, *k, sa.dx, sa.dy, sa.dz, g.nx, g.ny, g.nz);
+}
+
+// Whether the spill that the scan counted fits what is left of both capacities, and the store's fill in front of it. Every block of
+// every emitting kernel reads the same four counters (the advance kernel moves them behind the last of those kernels).
+__device__ __forceinline__ bool spill_mesh_fits(const VolSpillMeshArgs& sa, unsigned long long* v_written, unsigned long long* t_written) {
+  const VolSpillMeshCounters* sc = sa.sc;
+  *v_written = sc->v_written;
+  *t_written = sc->t_written;
+  return *v_written + sc->v_pending <= (unsigned long long)sa.a.vertex_capacity &&
+         *t_written + sc->t_pending <= (unsigned long long)sa.a.triangle_capacity;
+}
+
+__global__ void __launch_bounds__(kMeshBlock) volume_spill_mesh_count_kernel(VolSpillMeshArgs sa) {
+  const VolMeshArgs& a = sa.a;
+  __shared__ unsigned sh[2][kMeshBlock / 64];
+  const int v = blockIdx.x * kMeshBlock + threadIdx.x;
+  int i = 0, j = 0, k = 0;
+  const bool near = spill_mesh_near(sa, v, &i, &j, &k);
+  if (!__syncthreads_or(near)) {   // no voxel of this block is near the slab: its two zero counts, nothing loaded
+    if (threadIdx.x < 2) a.blk[2 * blockIdx.x + threadIdx.x] = 0u;
+    return;
+  }
+  unsigned nv = 0, nt = 0;
+  if (near) {
+    unsigned mask, pos8;
+    bool live;
+    mesh_voxel(a.g, v, &mask, &live, &pos8);
+    unsigned spilled = 0;
+#pragma unroll
+    for (int e = 0; e < 7; e++)
+      spilled |= (shift_edge_spilled(i, j, k, mtet_dir_offset(e), sa.dx, sa.dy, sa.dz, a.g.nx, a.g.ny, a.g.nz) ? 1u : 0u) << e;
+    mask &= spilled;
+    a.edge_mask[v] = (uint8_t)mask;
+    nv = (unsigned)__popc(mask);
+    // (a live cell has all eight corners inside the grid: i + 1 < nx, j + 1 < ny, k + 1 < nz)
+    nt = live && shift_cell_spilled(i, j, k, sa.dx, sa.dy, sa.dz, a.g.nx, a.g.ny, a.g.nz) ? (unsigned)mtet_cell_count(pos8) : 0u;
+  }
+  for (int o = 32; o > 0; o >>= 1) { nv += __shfl_xor(nv, o, 64); nt += __shfl_xor(nt, o, 64); }
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { sh[0][w] = nv; sh[1][w] = nt; }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    unsigned t = 0;
+    for (int q = 0; q < kMeshBlock / 64; q++) t += sh[threadIdx.x][q];
+    a.blk[2 * blockIdx.x + threadIdx.x] = t;
+  }
+}
+
+// One block: volume_mesh_scan_kernel's walk over both per-block counts; the two sums are left for the emitting kernels and advance.
+__global__ void __launch_bounds__(kMeshScanThreads) volume_spill_mesh_scan_kernel(VolSpillMeshArgs sa) {
+  const VolMeshArgs& a = sa.a;
+  __shared__ unsigned wsum[2][kMeshScanThreads / 64];
+  const int t = threadIdx.x;
+  unsigned long long base[2] = {0, 0};
+  for (int c0 = 0; c0 < a.nblk; c0 += kMeshScanThreads) {
+    const int b = c0 + t;
+    unsigned s[2], inc[2];
+#pragma unroll
+    for (int x = 0; x < 2; x++) {
+      s[x] = b < a.nblk ? a.blk[2 * b + x] : 0u;   // (a chunk's sum is at most 1024 * 12 288: far below 2^32)
+      inc[x] = scan_wave(s[x], wsum[x]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int x = 0; x < 2; x++) {
+      const ScanRank r = scan_rank<kMeshScanThreads>(s[x], inc[x], wsum[x]);
+      if (b < a.nblk) a.blk_off[2 * b + x] = base[x] + (unsigned long long)r.rank;
+      base[x] += r.total;
+    }
+    __syncthreads();   // wsum is written again
+  }
+  if (t == 0) { sa.sc->v_pending = base[0]; sa.sc->t_pending = base[1]; }
+}
+
+// volume_mesh_vertex_kernel behind the store's earlier vertices: index = v_written + block offset + rank, left per voxel as the
+// store's index of the voxel's first vertex (what the triangles and the colours look up). A block without a vertex, and every block
+// of a spill that does not fit, writes nothing.
+__global__ void __launch_bounds__(kMeshBlock) volume_spill_mesh_vertex_kernel(VolSpillMeshArgs sa) {
+  const VolMeshArgs& a = sa.a;
+  __shared__ unsigned wsum[kMeshBlock / 64];
+  unsigned long long v_written, t_written;
+  if (a.blk[2 * blockIdx.x] == 0u || !spill_mesh_fits(sa, &v_written, &t_written)) return;   // (block-uniform)
+  const int v = blockIdx.x * kMeshBlock + threadIdx.x;
+  int i, j, k;
+  const unsigned mask = spill_mesh_near(sa, v, &i, &j, &k) ? (unsigned)a.edge_mask[v] : 0u;   // (count wrote it for near voxels only)
+  const unsigned rank = scan_block<kMeshBlock>((unsigned)__popc(mask), wsum).rank;
+  const unsigned long long idx = v_written + a.blk_off[2 * blockIdx.x] + rank;
+  if (!mask) return;
+  a.vertex_base[v] = (uint32_t)idx;   // (< 2^28: the spill fits the store)
+  mesh_vertices(a.g, v, mask, idx, (unsigned long long)a.vertex_capacity, a.xyz0, a.nrmw);
+}
+
+// volume_mesh_triangle_kernel for the spilled cells. Every vertex a spilled cell's triangle names lies on an edge of that cell, which
+// is a spilled edge by definition: its owner was near, and the vertex kernel left the owner's first index.
+__global__ void __launch_bounds__(kMeshBlock) volume_spill_mesh_triangle_kernel(VolSpillMeshArgs sa) {
+  const VolMeshArgs& a = sa.a;
+  __shared__ unsigned wsum[kMeshBlock / 64];
+  unsigned long long v_written, t_written;
+  if (a.blk[2 * blockIdx.x + 1] == 0u || !spill_mesh_fits(sa, &v_written, &t_written)) return;   // (block-uniform)
+  const int v = blockIdx.x * kMeshBlock + threadIdx.x;
+  int i, j, k;
+  unsigned nt = 0, pos8 = 0;
+  if (spill_mesh_near(sa, v, &i, &j, &k)) {
+    unsigned mask;
+    bool live;
+    mesh_voxel(a.g, v, &mask, &live, &pos8);
+    nt = live && shift_cell_spilled(i, j, k, sa.dx, sa.dy, sa.dz, a.g.nx, a.g.ny, a.g.nz) ? (unsigned)mtet_cell_count(pos8) : 0u;
+  }
+  const unsigned rank = scan_block<kMeshBlock>(nt, wsum).rank;
+  const unsigned long long idx = t_written + a.blk_off[2 * blockIdx.x + 1] + rank;
+  if (!nt) return;
+  mesh_triangles(a.g, c_spill_mtet, v, pos8, idx, (unsigned long long)a.triangle_capacity, a.vertex_base, a.edge_mask, a.tri);
+}
+
+// volume_mesh_colour_kernel for the spilled vertices, at the indices the vertex kernel left.
+__global__ void __launch_bounds__(kMeshBlock) volume_spill_mesh_colour_kernel(VolSpillMeshArgs sa) {
+  const VolMeshArgs& a = sa.a;
+  unsigned long long v_written, t_written;
+  if (a.blk[2 * blockIdx.x] == 0u || !spill_mesh_fits(sa, &v_written, &t_written)) return;   // (block-uniform)
+  const int v = blockIdx.x * kMeshBlock + threadIdx.x;
+  int i, j, k;
+  if (!spill_mesh_near(sa, v, &i, &j, &k)) return;
+  const unsigned mask = (unsigned)a.edge_mask[v];
+  if (!mask) return;
+  mesh_vertex_colours(a.g, sa.col, v, mask, a.vertex_base[v], (unsigned long long)a.vertex_capacity, sa.rgba);
+}
+
+// One thread, behind the kernels that read the counters: they move on, by the whole spill or not at all.
+__global__ void volume_spill_mesh_advance_kernel(VolSpillMeshArgs sa) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  // As volume_spill_advance_kernel: the counters are read through a volatile pointer (vector loads, each waited for), and every
+  // store carries a value computed from those loads, so none can be issued before its loads have returned. The pending counts stay:
+  // the next spill's scan writes them before anything reads them.
+  volatile VolSpillMeshCounters* sc = sa.sc;
+  const unsigned long long vw = sc->v_written, tw = sc->t_written, vt = sc->v_total, tt = sc->t_total;
+  const unsigned long long vp = sc->v_pending, tp = sc->t_pending;
+  const bool fits = vw + vp <= (unsigned long long)sa.a.vertex_capacity && tw + tp <= (unsigned long long)sa.a.triangle_capacity;
+  sc->v_total = vt + vp;
+  sc->t_total = tt + tp;
+  sc->v_written = vw + (fits ? vp : 0ull);
+  sc->t_written = tw + (fits ? tp : 0ull);
+}
+
+void launch_volume_spill_mesh_stage(const VolSpillMeshArgs& a, int stage, hipStream_t s) {
+  const dim3 grid(a.a.nblk), block(kMeshBlock);
+  if (stage == 0) hipLaunchKernelGGL(volume_spill_mesh_count_kernel, grid, block, 0, s, a);
+  else if (stage == 1) hipLaunchKernelGGL(volume_spill_mesh_scan_kernel, dim3(1), dim3(kMeshScanThreads), 0, s, a);
+  else if (stage == 2) hipLaunchKernelGGL(volume_spill_mesh_vertex_kernel, grid, block, 0, s, a);
+  else if (stage == 3) hipLaunchKernelGGL(volume_spill_mesh_triangle_kernel, grid, block, 0, s, a);
+  else if (a.col) hipLaunchKernelGGL(volume_spill_mesh_colour_kernel, grid, block, 0, s, a);
+}
+
+void launch_volume_spill_mesh(const VolSpillMeshArgs& a, hipStream_t s) {
+  for (int stage = 0; stage < 5; stage++) launch_volume_spill_mesh_stage(a, stage, s);
+  hipLaunchKernelGGL(volume_spill_mesh_advance_kernel, dim3(1), dim3(64), 0, s, a);
 }
 
 }  // namespace odo

@@ -1,8 +1,9 @@
 // volume_shift_math.h — the rules of the moving TSDF volume (include/odometry_hip.h, odo_volume_shift / odo_volume_follow; DESIGN.md
 // section 9.9), host + device like volume_math.h: the kernels of volume_shift_kernels.hip, the host object (volume_shift_api.hip.h)
 // and the g++ harness of tests/volume_shift_harness.cpp compile these same lines. Where a shifted voxel comes from, which voxels a
-// shift destroys, how far the window may travel and the shift that follows a pose are each written once, here. The window's origin
-// is host_fp.h's (hostfp::window_origin).
+// shift destroys, how far the window may travel, the shift that follows a pose, and which cells and edges of the mesh a shift spills
+// (tests/volume_spill_mesh_harness.cpp) are each written once, here. The window's origin is host_fp.h's
+// (hostfp::window_origin).
 #pragma once
 #include <stdint.h>
 
@@ -28,6 +29,50 @@ ODO_SHIFT_HD bool shift_source(int i, int d, int n, int* src) {
 ODO_SHIFT_HD bool shift_leaves(int i, int d, int n) {
   const long long t = (long long)i - d;
   return t < 0 || t >= n;
+}
+
+// ---- the mesh spill ---------------------------------------------------------------------------------------
+// The old voxels that stay under d form the box [lo, hi] on every axis, empty (lo > hi) when |d| >= n. (64-bit: every int d is legal.)
+ODO_SHIFT_HD void shift_stay_box(int d, int n, long long* lo, long long* hi) {
+  *lo = d > 0 ? (long long)d : 0;
+  *hi = d < 0 ? (long long)n - 1 + d : (long long)n - 1;
+}
+
+// On one axis: the cell with low corner c (0 <= c <= n - 2) has a corner that leaves, c < lo or c + 1 > hi.
+ODO_SHIFT_HD bool shift_cell_axis(int c, int d, int n) {
+  long long lo, hi;
+  shift_stay_box(d, n, &lo, &hi);
+  return c < lo || (long long)c + 1 > hi;
+}
+
+// The cell with low corner (i, j, k), all eight corners inside the grid, is spilled iff at least one of its corners leaves.
+ODO_SHIFT_HD bool shift_cell_spilled(int i, int j, int k, int dx, int dy, int dz, int nx, int ny, int nz) {
+  return shift_cell_axis(i, dx, nx) || shift_cell_axis(j, dy, ny) || shift_cell_axis(k, dz, nz);
+}
+
+// On one axis: the edge from a to a + step (step 0 or 1, both inside the grid, n >= 2) is an edge of cells whose low corner is a when
+// step = 1, else one of {a - 1, a} within [0, n - 2]; true iff one of those has a leaving corner on this axis.
+ODO_SHIFT_HD bool shift_edge_axis(int a, int step, int d, int n) {
+  if (step) return shift_cell_axis(a, d, n);
+  return (a >= 1 && shift_cell_axis(a - 1, d, n)) || (a <= n - 2 && shift_cell_axis(a, d, n));
+}
+
+// The edge from voxel (i, j, k) in direction c (= dx + 2 dy + 4 dz, 1 .. 7, the far end inside the grid) is spilled iff it is an edge of
+// at least one spilled cell of the grid. The candidate cells are a product over the axes, so one axis with a spilling candidate is enough.
+ODO_SHIFT_HD bool shift_edge_spilled(int i, int j, int k, int c, int dx, int dy, int dz, int nx, int ny, int nz) {
+  return shift_edge_axis(i, c & 1, dx, nx) || shift_edge_axis(j, (c >> 1) & 1, dy, ny) || shift_edge_axis(k, (c >> 2) & 1, dz, nz);
+}
+
+// On one axis: voxel v is within one voxel of a leaving one, so one of its edges or its cell may be spilled. A voxel for which this is
+// false on every axis owns no spilled edge and no spilled cell: the mesh spill's threads load nothing for it.
+ODO_SHIFT_HD bool shift_near_axis(int v, int d, int n) {
+  long long lo, hi;
+  shift_stay_box(d, n, &lo, &hi);
+  return (lo > 0 && v <= lo) || (hi < (long long)n - 1 && v >= hi);
+}
+
+ODO_SHIFT_HD bool shift_near(int i, int j, int k, int dx, int dy, int dz, int nx, int ny, int nz) {
+  return shift_near_axis(i, dx, nx) || shift_near_axis(j, dy, ny) || shift_near_axis(k, dz, nz);
 }
 
 // The cumulative shift off + d on one axis, refused (false) beyond +-kShiftMaxOff.

@@ -33,7 +33,8 @@
             --modes coloured,pinned,none alternating in one call). Mode `follow` is the pinned grid with a spill store of 2^22 points
             and api.TsdfVolume.set_follow's defaults (focus max_depth / 2, threshold min(dims) // 8): the window moves with the
             camera; its lines carry `shifts`, the times the window moved during the timed frames (the window is read after every
-            frame, a host call without a wait, in this mode only).
+            frame, a host call without a wait, in this mode only). `follow_none` is the same without a store and `follow_mesh`
+            the same with a mesh store (2^22 vertices, 2^23 triangles) in place of the point store.
 
   icp       the frame-to-model alignment's two kernels timed with events (api.TsdfVolume.icp_time: `reps` launches of
             volume_icp_rows_kernel<29>, then of volume_icp_step_kernel<29>'s fold, each batch between two events on the volume's stream):
@@ -54,12 +55,17 @@
             d = (0, 0, nz / 4). One JSON line per case with the medians over `runs` batches of the shift, of a device-to-device
             hipMemcpyAsync of the same bytes, of a hipMemsetAsync of the same bytes, and of the spill's count, scan and scatter,
             with the bytes moved and the points that shift spills.
+            --mesh: each volume has both stores; a one-layer shift on each axis, the quarter-grid shift and a whole-grid shift
+            (d = (0, 0, nz): every voxel is near the slab, the mesh's whole work through the spill's kernels); one line per case with
+            the mesh spill's five stages (api.TsdfVolume.spill_mesh_time) beside the shift and the point spill's three stages from
+            alternating batches, then the counts each shift really spills.
 
   python tools/volume_cost.py kernels [--frames 10] [--extractions 3] [--runs 7] [--reps 20] [--json FILE]
   python tools/volume_cost.py icp [--frames 10] [--runs 7] [--reps 50] [--photo [--sampling nearest|trilinear|both]]
-  python tools/volume_cost.py shift [--frames 10] [--runs 7] [--reps 20]
+  python tools/volume_cost.py shift [--frames 10] [--runs 7] [--reps 20] [--mesh]
   python tools/volume_cost.py summary DIR [--json FILE]
-  python tools/volume_cost.py track [--runs 3] [--steps 200] [--warmup 20] [--frames 100] [--modes none,pinned,large[,coloured][,follow]]
+  python tools/volume_cost.py track [--runs 3] [--steps 200] [--warmup 20] [--frames 100]
+                                    [--modes none,pinned,large[,coloured][,follow][,follow_none][,follow_mesh]]
 
 A build without the volume is measured with tools/rgbd_cost.py --modes tum (the same drive and loop as `track`'s mode `none`).
 """
@@ -85,12 +91,15 @@ GRIDS = dict(pinned=dict(dims=(240, 128, 200), origin=(-4.8, -3.3, 0.4)),
 
 def make_volume(owner, grid, size, K, colour=False):
     from odometry_amd import api
-    g = GRIDS["pinned" if grid in ("coloured", "follow") else grid]
+    g = GRIDS["pinned" if grid == "coloured" or grid.startswith("follow") else grid]
     vol = api.TsdfVolume(owner, g["dims"], VS, g["origin"], MU, MAX_DEPTH, 65535, size, K, 1000.0)
     if colour or grid == "coloured":
         vol.enable_colour(3, False, 255)
     if grid == "follow":
         vol.enable_spill(1 << 22)
+    if grid == "follow_mesh":
+        vol.enable_spill_mesh(1 << 22, 1 << 23)
+    if grid.startswith("follow"):
         vol.set_follow(MAX_DEPTH / 2, min(g["dims"]) // 8)
     return vol
 
@@ -228,7 +237,7 @@ def track(args):
             trk.init(*dev[order[0]])
             kf = shifts = 0
             t0 = None
-            win = vol.window()[0] if mode == "follow" else None
+            win = vol.window()[0] if mode.startswith("follow") else None
             for k in range(1, last + 1):
                 if k == args.warmup + 1:
                     trk._sync()
@@ -250,12 +259,17 @@ def track(args):
             groups, redo1 = trk.persistent_stats()
             res[mode].append(fps)
             st = vol.stats() if vol is not None else {}
+            if mode.startswith("follow"):
+                st = dict(st, shifts=int(shifts), window=list(win))
             if mode == "follow":
-                st = dict(st, shifts=int(shifts), window=list(win), spilled=len(vol.spilled(clear=True)[0]))
+                st = dict(st, spilled=len(vol.spilled(clear=True)[0]))
+            if mode == "follow_mesh":
+                got = vol.spilled_mesh(clear=True, with_dropped=True)
+                st = dict(st, spilled_vertices=len(got[0]), spilled_triangles=len(got[2]), spilled_dropped=list(got[3]))
             print(json.dumps(dict(run=run, mode=mode, fps=round(fps, 1), keyframes=kf + 1, lm_persistent_groups=groups,
                                   solves_redone=redo1 - redo0, depth_jobs_redone=djob1 - djob0, frames_integrated=st.get("frames"),
                                   updated_last=st.get("updated"), in_band_last=st.get("in_band"),
-                                  **{k_: st[k_] for k_ in ("shifts", "window", "spilled") if k_ in st}, **{k_: round(v, 1) for k_, v in tm.items()})), flush=True)
+                                  **{k_: st[k_] for k_ in ("shifts", "window", "spilled", "spilled_vertices", "spilled_triangles", "spilled_dropped") if k_ in st}, **{k_: round(v, 1) for k_, v in tm.items()})), flush=True)
     trk.attach_volume(None)
     print(json.dumps(dict(summary=True, **{m: dict(median_fps=round(float(np.median(res[m])), 1),
                                                    spread=[round(min(res[m]), 1), round(max(res[m]), 1)]) for m in modes})))
@@ -373,6 +387,45 @@ def shift(args):
     ctx.close()
 
 
+def shift_mesh(args):
+    """`shift --mesh`: the mesh spill's five stages beside the point spill's three and the shift, one visit."""
+    from odometry_amd import api, synth
+    seq = synth.make_rgbd_sequence(args.frames, seed=0)
+    K = (seq["K"]["f0"], seq["K"]["cx0"], seq["K"]["cy0"])
+    ctx = api.Context(0)
+    names = ("count", "scan", "vertices", "triangles", "colour")
+    for grid in ("pinned", "large"):
+        nx, ny, nz = GRIDS[grid]["dims"]
+        for coloured in (False, True):
+            vol = make_volume(ctx, grid, (synth.TUM_ROWS, synth.TUM_COLS), K, colour=coloured)
+            cdev = [synth.colour_from_gray(g, 3, False, tint_seed=1) for g in seq["gray"]]
+            for d, c, A in zip(seq["depth"], cdev, seq["poses"]):
+                vol.integrate(d, A, colour=c if coloured else None)
+            vol.enable_spill(1 << 22)
+            vol.enable_spill_mesh(1 << 23, 1 << 24)
+            nv, nt = vol.mesh_counts()
+            shifts = (("one layer x", (1, 0, 0)), ("one layer y", (0, 1, 0)), ("one layer z", (0, 0, 1)), ("quarter grid", (0, 0, nz // 4)),
+                      ("whole grid", (0, 0, nz)))
+            for tag, d in shifts:
+                us = np.array([vol.spill_mesh_time(d, reps=args.reps) for _ in range(args.runs)])
+                pt = np.array([vol.shift_time(d, reps=args.reps) for _ in range(args.runs)])
+                row = dict(grid=grid, coloured=coloured, shift=tag, d=list(d), voxels=nx * ny * nz, mesh_vertices=nv, mesh_triangles=nt)
+                for k, n in enumerate(names):
+                    row["mesh_" + n + "_us_median"] = round(float(np.median(us[:, k])), 2)
+                    row["mesh_" + n + "_us_min_max"] = [round(float(us[:, k].min()), 2), round(float(us[:, k].max()), 2)]
+                row["mesh_stages_us_median_sum"] = round(float(np.median(us, 0).sum()), 2)
+                for k, n in ((0, "shift"), (3, "spill_count"), (4, "spill_scan"), (5, "spill_scatter")):
+                    row[n + "_us_median"] = round(float(np.median(pt[:, k])), 2)
+                print(json.dumps(row), flush=True)
+            for tag, d in shifts[:4]:   # what each really spills, applied in turn
+                vol.shift(d)
+                got = vol.spilled_mesh(clear=True, with_dropped=True)
+                print(json.dumps(dict(grid=grid, coloured=coloured, shift=tag, applied=True, spilled_vertices=len(got[0]),
+                                      spilled_triangles=len(got[2]), dropped=list(got[3]), spilled_points=len(vol.spilled(clear=True)[0]))), flush=True)
+            vol.close()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -401,9 +454,12 @@ def main():
     h.add_argument("--frames", type=int, default=10)
     h.add_argument("--runs", type=int, default=7)
     h.add_argument("--reps", type=int, default=20)
+    h.add_argument("--mesh", action="store_true")
     args = ap.parse_args()
     if args.cmd == "icp" and args.photo:
         return icp_photo(args)
+    if args.cmd == "shift" and args.mesh:
+        return shift_mesh(args)
     dict(kernels=kernels, summary=summary, track=track, icp=icp, shift=shift)[args.cmd](args)
 
 
