@@ -462,6 +462,13 @@ int odo_map_stats(odo_map* m, long out[6]);
 int odo_map_keyframe_pose(const odo_map* m, int keyframe, float abs_pose_colmajor[16]);
 /* Empty map: points, voxels, counters and the insertion counter start from nothing. */
 int odo_map_clear(odo_map* m);
+/* TEST ONLY, for the project's own suite; not part of the interface an integrator uses and free to change. The voxel filter's hash
+ * table as it stands (waits for pending insertions): *n_slots = its slot count, stored whenever m and the pointers are not NULL; with
+ * n_slots_cap >= that count, keys[slot] and payload[slot] of every slot (an unclaimed slot holds all ones in both; a claimed one
+ * its 63-bit voxel key and the least (insertion << 32 | pixel) of its claimants). -1, nothing copied: a NULL argument, a map without
+ * a filter (voxel_size == 0), n_slots_cap too small. */
+int odo_debug_map_table(odo_map* m, unsigned long long n_slots_cap, unsigned long long* keys, unsigned long long* payload,
+                        unsigned long long* n_slots);
 /* -1 while the map is attached to a tracker. */
 int odo_map_destroy(odo_map* m);
 /* The tracker inserts every keyframe into m (GlobalMap::InsertKeyFrame where the runner keeps its keyframes, ref:

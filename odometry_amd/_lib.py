@@ -249,6 +249,8 @@ SIGNATURES = {
     "odo_map_stats": (C.c_int, [_vp, C.POINTER(C.c_long)]),
     "odo_map_keyframe_pose": (C.c_int, [_vp, C.c_int, _fp]),
     "odo_map_clear": (C.c_int, [_vp]),
+    "odo_debug_map_table": (C.c_int, [_vp, C.c_ulonglong, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong),
+                                      C.POINTER(C.c_ulonglong)]),   # test only: not for integrators (include/odometry_hip.h)
     "odo_map_destroy": (C.c_int, [_vp]),
     "odo_tracker_attach_map": (C.c_int, [_vp, _vp]),
     "odo_tracker_create_rgbd": (C.c_int, [C.c_int, C.POINTER(TrackerParams), C.c_float, C.c_float, C.POINTER(_vp)]),

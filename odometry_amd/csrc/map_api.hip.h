@@ -165,6 +165,21 @@ extern "C" int odo_map_stats(odo_map* m, long out[6]) {
   return 0;
 }
 
+// Test only (include/odometry_hip.h): the hash table as it stands, held slot by slot by tests/test_gpu_map_hash_cases.py.
+extern "C" int odo_debug_map_table(odo_map* m, unsigned long long n_slots_cap, unsigned long long* keys, unsigned long long* payload,
+                                   unsigned long long* n_slots) {
+  if (!m || !keys || !payload || !n_slots) return fail("odo_debug_map_table: NULL arg");
+  *n_slots = m->slots;
+  if (!(m->voxel > 0.0f)) return fail("odo_debug_map_table: the map has no voxel filter (voxel_size == 0)");
+  if (n_slots_cap < m->slots) return fail("odo_debug_map_table: room for %llu slots, the table has %llu", n_slots_cap, m->slots);
+  if (map_sync(m)) return -1;
+  const size_t bytes = sizeof(unsigned long long) * (size_t)m->slots;
+  HIP_OK(hipMemcpyAsync(keys, m->d_keys, bytes, hipMemcpyDeviceToHost, m->own));
+  HIP_OK(hipMemcpyAsync(payload, m->d_payload, bytes, hipMemcpyDeviceToHost, m->own));
+  HIP_OK(hipStreamSynchronize(m->own));
+  return 0;
+}
+
 extern "C" int odo_map_keyframe_pose(const odo_map* m, int keyframe, float abs_pose_colmajor[16]) {
   if (!m || !abs_pose_colmajor) return fail("odo_map_keyframe_pose: NULL arg");
   if (keyframe < 0 || keyframe >= m->n_ins) return fail("odo_map_keyframe_pose: keyframe %d of %ld", keyframe, m->n_ins);
