@@ -990,6 +990,42 @@ int odo_volume_spill_mesh_time(odo_volume* v, const int d[3], int reps, float us
 /* TEST ONLY, as odo_debug_volume_spill_guard: 64 guard items behind each of the mesh store's buffers, 0xAB fill; *n_changed = bytes
  * behind the store's last vertex and last triangle, guards included, that no longer hold 0xAB (waits). */
 int odo_debug_volume_spill_mesh_guard(odo_volume* v, long* n_changed);
+/* Re-entry store: the leaving VOXELS, put back when the window returns to them. A voxel's global index is
+ * g_c = off_c + i_c (off the window's cumulative shift, i its index in the window): the same physical voxel has the same g whenever
+ * it is in the window. The store is an ordered list of entries (g[3], voxel word, colour word). With a store, a shift by d != 0 that
+ * odo_volume_shift accepts does three things, in this order:
+ *   restore  every entry whose g - off_new lies in [0, n) on all three axes is removed from the store and its voxel word (and its colour
+ *            word, when the store has colours) written to that voxel of the shifted grid. Entering voxels are 0 there, so this
+ *            overwrites zeros only;
+ *   keep     the other entries stay, in their order;
+ *   save     every voxel of the PRE-shift grid that leaves under d (above) and has a non-zero bit in its voxel word, or in its colour
+ *            word on a volume with colour, is appended behind them in raster order (i fastest, then j, then k).
+ * Entries beyond the capacity are counted and dropped: the kept entries always fit, so only the tail of the newly saved ones is cut.
+ * Between shifts every stored g lies outside the window and no g occurs twice. With enough capacity a shift by d followed by -d, or
+ * any closed walk of shifts, restores grid, colour grid and window bit for bit and leaves the store empty. Integers only, no atomics,
+ * no host wait; eight launches round the shift's. odo_volume_clear empties the store. The point and mesh stores stay logs of the
+ * surfaces that left: geometry that leaves, returns and leaves again appears in them twice. */
+/* Allocates the store: capacity (1 .. 2^28) entries in two sets of buffers, 16 B per entry and set (20 B when the volume has colour:
+ * enable it first; a store without colours gives its voxels back with colour word 0), and the scratch of its passes, so that no shift
+ * allocates. Once, and not while attached to a tracker. */
+int odo_volume_enable_reentry(odo_volume* v, long capacity);
+/* The store's live entries in store order (waits for everything pending). *n = the live count, in every case below. capacity 0:
+ * nothing else. Otherwise -1 and nothing copied or cleared when capacity is below the live count; else g (three int32 per entry), vox
+ * and, unless NULL, col (refused on a store without colours) receive them. clear != 0 empties the store and zeroes its counters
+ * afterwards. Legal while attached. */
+int odo_volume_reentry_voxels(odo_volume* v, long capacity, int32_t (*g)[3], uint32_t* vox, uint32_t* col, long* n, int clear);
+/* stats[4] = entries in the store, and since enable / clear: entries appended, entries put back into the grid, leaving voxels that
+ * found the store full (waits). live = saved - restored. */
+int odo_volume_reentry_stats(odo_volume* v, long stats[4]);
+/* Event timing (diagnostic, tools/volume_cost.py shift --reentry; waits; refused while attached or without a store): as
+ * odo_volume_shift_time, us[0 .. 4] = save count, save scan, save scatter, the store pass (count, scan and compaction: three launches)
+ * and the advance for a shift by d that is not applied. The passes write the grids' and the store's second buffers and a copy of the
+ * counters, none of which is swapped in: the volume and the store read the same afterwards. */
+int odo_volume_reentry_time(odo_volume* v, const int d[3], int reps, float us[5]);
+/* TEST ONLY, as odo_debug_volume_spill_guard: 64 guard entries behind each buffer of both sets, 0xAB fill. *n_changed = bytes of the
+ * live set behind its last live entry, guard included, that no longer hold 0xAB (0 while the live count has never gone down);
+ * *n_guard = bytes of the guards of both sets that no longer hold it (always 0). Waits. */
+int odo_debug_volume_reentry_guard(odo_volume* v, long* n_changed, long* n_guard);
 /* Following a camera. The host works in fp64 from the fp32 entries of the camera-to-world pose [R | t]: p = t + focus * R[:, 2] (the
  * point `focus` metres along the optical axis); e_c = (p_c - (origin_c + 0.5 * n_c * vs)) / vs, its distance from the window's centre
  * in voxels; if max |e_c| < threshold then d = 0, else d_c = nearbyint(e_c) (ties to even) clamped to +-n_c. */

@@ -311,6 +311,12 @@ SIGNATURES = {
                                         C.POINTER(C.c_long), C.POINTER(C.c_long), C.c_int]),
     "odo_volume_spill_mesh_time": (C.c_int, [_vp, _ip, C.c_int, _fp]),
     "odo_debug_volume_spill_mesh_guard": (C.c_int, [_vp, C.POINTER(C.c_long)]),   # test only, as odo_debug_volume_spill_guard
+    "odo_volume_enable_reentry": (C.c_int, [_vp, C.c_long]),
+    "odo_volume_reentry_voxels": (C.c_int, [_vp, C.c_long, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                            C.POINTER(C.c_long), C.c_int]),
+    "odo_volume_reentry_stats": (C.c_int, [_vp, C.POINTER(C.c_long)]),
+    "odo_volume_reentry_time": (C.c_int, [_vp, _ip, C.c_int, _fp]),
+    "odo_debug_volume_reentry_guard": (C.c_int, [_vp, C.POINTER(C.c_long), C.POINTER(C.c_long)]),   # test only, as ..._spill_guard
     "odo_volume_set_follow": (C.c_int, [_vp, C.POINTER(VolumeFollowParams)]),
     "odo_volume_follow": (C.c_int, [_vp, _fp, _ip]),
     "odo_depth_filter_create": (C.c_int, [_vp, C.POINTER(DepthFilterParams), C.POINTER(_vp)]),

@@ -1451,6 +1451,46 @@ class TsdfVolume:
         L.check(self.lib.odo_volume_spill_mesh_time(self.h, d, int(reps), _fp(us)), "odo_volume_spill_mesh_time")
         return tuple(float(x) for x in us)
 
+    # ---- the re-entry store (odo_volume_enable_reentry: the leaving voxels, put back when the window returns) ----
+    def enable_reentry(self, capacity):
+        """Adds the re-entry store: room for `capacity` (1 .. 2^28) voxels that shifts push out of the window, each kept with its
+        integer position in the world and put back by the first shift that brings the window over it again (two sets of buffers: 32 B
+        per entry, 40 B with colour: enable_colour first). Once, and not while attached to a tracker. shift, follow, track(...,
+        integrate=True) and an attached RgbdTracker use it with no further arguments."""
+        L.check(self.lib.odo_volume_enable_reentry(self.h, int(capacity)), "odo_volume_enable_reentry")
+
+    def stored_voxels(self, clear=False, colour=False):
+        """The re-entry store's live entries in store order: (n, 3) int32 global voxel index (window offset + index in the window),
+        (n,) int16 q and (n,) uint16 w (colour: also (n, 4) uint8 R, G, B, wc). clear=True empties the store and zeroes its counters
+        afterwards. Waits for everything pending."""
+        n = C.c_long(0)
+        L.check(self.lib.odo_volume_reentry_voxels(self.h, 0, None, None, None, C.byref(n), 0), "odo_volume_reentry_voxels")
+        m = max(n.value, 1)   # (an exact buffer: this thread enqueues nothing between the two calls)
+        g, vox = np.zeros((m, 3), np.int32), np.zeros(m, np.uint32)
+        col = np.zeros(m, np.uint32) if colour else None
+        u32 = C.POINTER(C.c_uint32)
+        L.check(self.lib.odo_volume_reentry_voxels(self.h, m, g.ctypes.data_as(C.POINTER(C.c_int32)), vox.ctypes.data_as(u32),
+                                                   col.ctypes.data_as(u32) if colour else None, C.byref(n), int(bool(clear))),
+                "odo_volume_reentry_voxels")
+        vox = vox[:n.value]
+        out = (g[:n.value].copy(), (vox & 0xFFFF).astype(np.uint16).view(np.int16), (vox >> 16).astype(np.uint16))
+        return out + (col[:n.value].copy().view(np.uint8).reshape(-1, 4),) if colour else out
+
+    def reentry_stats(self):
+        """dict(live, saved, restored, dropped): entries in the re-entry store now, and since enable_reentry / clear the entries
+        appended, the entries put back into the grid, and the leaving voxels that found the store full. Waits."""
+        s = (C.c_long * 4)()
+        L.check(self.lib.odo_volume_reentry_stats(self.h, s), "odo_volume_reentry_stats")
+        return dict(live=s[0], saved=s[1], restored=s[2], dropped=s[3])
+
+    def reentry_time(self, d, reps=50):
+        """Event timing of the re-entry passes for a shift by d that is not applied: microseconds, means over reps, of (save count, save
+        scan, save scatter, store pass, advance). The volume and the store stay as they are."""
+        d = (C.c_int * 3)(*[int(x) for x in d])
+        us = np.zeros(5, np.float32)
+        L.check(self.lib.odo_volume_reentry_time(self.h, d, int(reps), _fp(us)), "odo_volume_reentry_time")
+        return tuple(float(x) for x in us)
+
     def save_mesh_ply(self, path, spill=False):
         """Binary little-endian PLY of the mesh: float x y z nx ny nz per vertex (and uchar red green blue when the volume has
         colour), three int indices per face. spill=True: the mesh store's mesh in front of the window's, whose indices are offset

@@ -3330,6 +3330,7 @@ extern "C" int odo_depth_report(const odo_depth* d, int* iters, float* cost, int
 #include "map_api.hip.h"
 #include "volume_api.hip.h"
 #include "volume_shift_api.hip.h"
+#include "volume_reentry_api.hip.h"
 #include "volume_icp_api.hip.h"
 #include "rgbd_frontend_api.hip.h"
 #include "depth_filter_api.hip.h"

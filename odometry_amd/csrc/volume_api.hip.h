@@ -8,6 +8,7 @@
 #include "volume_colour.hip.h"
 #include "volume_raycast.hip.h"
 #include "volume_shift.hip.h"
+#include "volume_reentry.hip.h"
 
 struct odo_volume {
   odo_ctx* ctx;                 // standalone integrations (odo_volume_integrate_dev) run on its stream
@@ -65,6 +66,13 @@ struct odo_volume {
   uint32_t* d_smesh_rgba;       // with colour
   int* d_smesh_tri;
   VolSpillMeshCounters* d_smesh_ctr;
+  // the re-entry store (odo_volume_enable_reentry, volume_reentry_api.hip.h; nothing below is allocated without it)
+  long re_capacity;             // entries, 0: no store
+  uint4 *d_re_ent, *d_re_ent2;  // {gx, gy, gz, word}: the live set and the second set, swapped by every shift
+  uint32_t *d_re_col, *d_re_col2;   // with colour
+  unsigned long long *d_re_save_mask, *d_re_save_off, *d_re_keep_mask, *d_re_keep_off;
+  unsigned *d_re_save_cnt, *d_re_keep_cnt;
+  VolReentryCounters *d_re_ctr, *d_re_ctr_time;   // (_time: the copy odo_volume_reentry_time works on)
   int follow;                   // 1: odo_volume_set_follow's parameters are set
   odo_volume_follow_params fp;
 };
@@ -74,7 +82,9 @@ static int volume_release(odo_volume* v) {
                 v->d_mesh_mask, v->d_mesh_base, v->d_mesh_cnt, v->d_mesh_off, v->d_mesh_ctr, v->d_mesh_xyz0, v->d_mesh_nrmw, v->d_mesh_tri,
                 v->d_col, v->d_rgba, v->d_mesh_rgba, v->d_ray_depth, v->d_ray_raw, v->d_ray_nrmw, v->d_ray_rgba,
                 v->d_vox2, v->d_col2, v->d_spill_xyz0, v->d_spill_nrmw, v->d_spill_rgba, v->d_spill_ctr,
-                v->d_smesh_xyz0, v->d_smesh_nrmw, v->d_smesh_rgba, v->d_smesh_tri, v->d_smesh_ctr};
+                v->d_smesh_xyz0, v->d_smesh_nrmw, v->d_smesh_rgba, v->d_smesh_tri, v->d_smesh_ctr,
+                v->d_re_ent, v->d_re_ent2, v->d_re_col, v->d_re_col2, v->d_re_save_mask, v->d_re_save_off, v->d_re_keep_mask,
+                v->d_re_keep_off, v->d_re_save_cnt, v->d_re_keep_cnt, v->d_re_ctr, v->d_re_ctr_time};
   for (void* p : ps) if (p) (void)hipFree(p);
   if (v->ev_last) (void)hipEventDestroy(v->ev_last);
   if (v->own) (void)hipStreamDestroy(v->own);
@@ -106,6 +116,7 @@ static int volume_reset(odo_volume* v) {
   HIP_OK(hipMemsetAsync(v->d_ctr, 0, sizeof(VolCounters), v->own));
   if (v->d_spill_ctr) HIP_OK(hipMemsetAsync(v->d_spill_ctr, 0, sizeof(VolSpillCounters), v->own));   // (the window stays where it is)
   if (v->d_smesh_ctr) HIP_OK(hipMemsetAsync(v->d_smesh_ctr, 0, sizeof(VolSpillMeshCounters), v->own));
+  if (v->d_re_ctr) HIP_OK(hipMemsetAsync(v->d_re_ctr, 0, sizeof(VolReentryCounters), v->own));
   v->n_frames = 0;
   return volume_mark(v, v->own);
 }

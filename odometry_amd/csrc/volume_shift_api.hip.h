@@ -5,7 +5,8 @@
 //
 // Nothing here waits for the device but odo_volume_spill_points and odo_volume_spill_mesh (and the diagnostics, odo_volume_shift_time,
 // odo_volume_spill_mesh_time and the two guard hooks): a spill and a shift are five launches on the volume's own stream, a mesh spill
-// (odo_volume_enable_spill_mesh) five or six more in front of the shift's.
+// (odo_volume_enable_spill_mesh) five or six more in front of the shift's, and a re-entry store
+// (odo_volume_enable_reentry, volume_reentry_api.hip.h) two in front of the shift's and five behind it.
 // The shift writes into the grids' second buffers and the host swaps the pointers when it enqueues: launches enqueued earlier hold
 // the old pointers by value and are ordered in front by volume_order_on / volume_mark, and every later launcher reads v->d_vox,
 // v->d_col and v->p.origin when it is called.
@@ -76,6 +77,8 @@ static VolShiftArgs volume_shift_args(odo_volume* v, const int d[3]) {
   return a;
 }
 
+static VolReentryArgs volume_reentry_args(odo_volume* v, const int d[3], const int off_new[3]);   // (volume_reentry_api.hip.h)
+
 // Spill (when the volume has a store) and shift by d, on the volume's own stream. 0: enqueued, or d = 0 and nothing to do.
 static int volume_shift(const char* who, odo_volume* v, const int d[3]) {
   int off[3];
@@ -93,7 +96,15 @@ static int volume_shift(const char* who, odo_volume* v, const int d[3]) {
     launch_volume_spill_mesh(volume_spill_mesh_args(v, d), v->own);
     HIP_OK(hipGetLastError());
   }
+  // (the re-entry store, DESIGN.md section 9.14: its arguments hold the grids and the store's two sets as they are in front of the swaps)
+  const VolReentryArgs ra = v->re_capacity > 0 ? volume_reentry_args(v, d, off) : VolReentryArgs{};
+  if (v->re_capacity > 0) launch_volume_reentry_save(ra, v->own);
   launch_volume_shift(volume_shift_args(v, d), v->own);
+  if (v->re_capacity > 0) {
+    launch_volume_reentry_store(ra, v->own);
+    std::swap(v->d_re_ent, v->d_re_ent2);
+    std::swap(v->d_re_col, v->d_re_col2);
+  }
   HIP_OK(hipGetLastError());
   std::swap(v->d_vox, v->d_vox2);
   if (v->colour) std::swap(v->d_col, v->d_col2);

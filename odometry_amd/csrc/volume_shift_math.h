@@ -2,7 +2,8 @@
 // section 9.9), host + device like volume_math.h: the kernels of volume_shift_kernels.hip, the host object (volume_shift_api.hip.h)
 // and the g++ harness of tests/volume_shift_harness.cpp compile these same lines. Where a shifted voxel comes from, which voxels a
 // shift destroys, how far the window may travel, the shift that follows a pose, and which cells and edges of the mesh a shift spills
-// (tests/volume_spill_mesh_harness.cpp) are each written once, here. The window's origin is host_fp.h's
+// (tests/volume_spill_mesh_harness.cpp), and the key of the re-entry store (DESIGN.md section 9.14;
+// volume_reentry_kernels.hip, tests/volume_reentry_harness.cpp) are each written once, here. The window's origin is host_fp.h's
 // (hostfp::window_origin).
 #pragma once
 #include <stdint.h>
@@ -81,6 +82,34 @@ ODO_SHIFT_HD bool shift_offset(int off, int d, int* out) {
   if (s > kShiftMaxOff || s < -(long long)kShiftMaxOff) return false;
   *out = (int)s;
   return true;
+}
+
+// ---- re-entry -----------------------------------------------------------------------------------------------
+// A voxel's global index on one axis: the window's cumulative shift plus its index in the window. The same physical voxel has the
+// same g whenever it is in the window. (64-bit: every int is legal; with |off| <= kShiftMaxOff and i < 2^30 it fits an int32.)
+ODO_SHIFT_HD long long reentry_global(int off, int i) {
+  return (long long)off + i;
+}
+
+// The stored voxel g lies inside the window `off` voxels from where it was created, n voxels wide: *t is its index there (only read
+// when inside: then it fits).
+ODO_SHIFT_HD bool reentry_inside(int g, int off, int n, int* t) {
+  const long long s = (long long)g - off;
+  *t = (int)s;
+  return s >= 0 && s < n;
+}
+
+// All three axes, and the word of the window's grid the voxel comes back to.
+ODO_SHIFT_HD bool reentry_dest(const int g[3], const int off[3], int nx, int ny, int nz, long long* word) {
+  int i, j, k;
+  const bool in = reentry_inside(g[0], off[0], nx, &i) & reentry_inside(g[1], off[1], ny, &j) & reentry_inside(g[2], off[2], nz, &k);
+  *word = ((long long)k * ny + j) * nx + i;
+  return in;
+}
+
+// A leaving voxel is saved iff it has a non-zero bit: an all-zero voxel equals what an entering voxel holds anyway.
+ODO_SHIFT_HD bool reentry_saved(uint32_t word, uint32_t colour) {
+  return (word | colour) != 0u;
 }
 
 // The shift that brings the window's centre to the point `focus` metres in front of the camera (column-major camera-to-world pose A):

@@ -34,7 +34,8 @@
             and api.TsdfVolume.set_follow's defaults (focus max_depth / 2, threshold min(dims) // 8): the window moves with the
             camera; its lines carry `shifts`, the times the window moved during the timed frames (the window is read after every
             frame, a host call without a wait, in this mode only). `follow_none` is the same without a store and `follow_mesh`
-            the same with a mesh store (2^22 vertices, 2^23 triangles) in place of the point store.
+            the same with a mesh store (2^22 vertices, 2^23 triangles) in place of the point store, `follow_reentry` with a
+            re-entry store of 2^23 voxels in its place (the price of re-entry: --modes follow_none,follow_reentry alternating).
 
   icp       the frame-to-model alignment's two kernels timed with events (api.TsdfVolume.icp_time: `reps` launches of
             volume_icp_rows_kernel<29>, then of volume_icp_step_kernel<29>'s fold, each batch between two events on the volume's stream):
@@ -59,13 +60,17 @@
             (d = (0, 0, nz): every voxel is near the slab, the mesh's whole work through the spill's kernels); one line per case with
             the mesh spill's five stages (api.TsdfVolume.spill_mesh_time) beside the shift and the point spill's three stages from
             alternating batches, then the counts each shift really spills.
+            --reentry: each volume has a point store and a re-entry store that holds 0, 10^5, 10^6 or 10^7 live entries (whole grids
+            of observed voxels pushed out of the window first); one line per case with the re-entry store's five stages
+            (api.TsdfVolume.reentry_time: save count, save scan, save scatter, the store pass, advance) beside the shift and the
+            point spill's three stages from alternating batches, then what each shift really saves and its way back restores.
 
   python tools/volume_cost.py kernels [--frames 10] [--extractions 3] [--runs 7] [--reps 20] [--json FILE]
   python tools/volume_cost.py icp [--frames 10] [--runs 7] [--reps 50] [--photo [--sampling nearest|trilinear|both]]
-  python tools/volume_cost.py shift [--frames 10] [--runs 7] [--reps 20] [--mesh]
+  python tools/volume_cost.py shift [--frames 10] [--runs 7] [--reps 20] [--mesh | --reentry]
   python tools/volume_cost.py summary DIR [--json FILE]
   python tools/volume_cost.py track [--runs 3] [--steps 200] [--warmup 20] [--frames 100]
-                                    [--modes none,pinned,large[,coloured][,follow][,follow_none][,follow_mesh]]
+                                    [--modes none,pinned,large[,coloured][,follow][,follow_none][,follow_mesh][,follow_reentry]]
 
 A build without the volume is measured with tools/rgbd_cost.py --modes tum (the same drive and loop as `track`'s mode `none`).
 """
@@ -99,6 +104,8 @@ def make_volume(owner, grid, size, K, colour=False):
         vol.enable_spill(1 << 22)
     if grid == "follow_mesh":
         vol.enable_spill_mesh(1 << 22, 1 << 23)
+    if grid == "follow_reentry":
+        vol.enable_reentry(1 << 23)
     if grid.startswith("follow"):
         vol.set_follow(MAX_DEPTH / 2, min(g["dims"]) // 8)
     return vol
@@ -266,10 +273,12 @@ def track(args):
             if mode == "follow_mesh":
                 got = vol.spilled_mesh(clear=True, with_dropped=True)
                 st = dict(st, spilled_vertices=len(got[0]), spilled_triangles=len(got[2]), spilled_dropped=list(got[3]))
+            if mode == "follow_reentry":
+                st = dict(st, reentry=vol.reentry_stats())
             print(json.dumps(dict(run=run, mode=mode, fps=round(fps, 1), keyframes=kf + 1, lm_persistent_groups=groups,
                                   solves_redone=redo1 - redo0, depth_jobs_redone=djob1 - djob0, frames_integrated=st.get("frames"),
                                   updated_last=st.get("updated"), in_band_last=st.get("in_band"),
-                                  **{k_: st[k_] for k_ in ("shifts", "window", "spilled", "spilled_vertices", "spilled_triangles", "spilled_dropped") if k_ in st}, **{k_: round(v, 1) for k_, v in tm.items()})), flush=True)
+                                  **{k_: st[k_] for k_ in ("shifts", "window", "spilled", "spilled_vertices", "spilled_triangles", "spilled_dropped", "reentry") if k_ in st}, **{k_: round(v, 1) for k_, v in tm.items()})), flush=True)
     trk.attach_volume(None)
     print(json.dumps(dict(summary=True, **{m: dict(median_fps=round(float(np.median(res[m])), 1),
                                                    spread=[round(min(res[m]), 1), round(max(res[m]), 1)]) for m in modes})))
@@ -426,6 +435,71 @@ def shift_mesh(args):
     ctx.close()
 
 
+def shift_reentry(args):
+    """`shift --reentry`: the re-entry store's five stages beside the shift and the point spill's three, in alternating batches, with
+    stores of 10^5, 10^6 and 10^7 live entries; then what each shift really saves and, on the way back, restores."""
+    from odometry_amd import api, synth
+    seq = synth.make_rgbd_sequence(args.frames, seed=0)
+    K = (seq["K"]["f0"], seq["K"]["cx0"], seq["K"]["cy0"])
+    ctx = api.Context(0)
+    names = ("save_count", "save_scan", "save_scatter", "store_pass", "advance")
+    for grid in ("pinned", "large"):
+        nx, ny, nz = GRIDS[grid]["dims"]
+        n = nx * ny * nz
+        for coloured in ((False, True) if grid == "pinned" else (False,)):
+            src = make_volume(ctx, grid, (synth.TUM_ROWS, synth.TUM_COLS), K, colour=coloured)
+            cdev = [synth.colour_from_gray(g, 3, False, tint_seed=1) for g in seq["gray"]]
+            for d, c, A in zip(seq["depth"], cdev, seq["poses"]):
+                src.integrate(d, A, colour=c if coloured else None)
+            q, w = src.grid()
+            col = src.colour_grid() if coloured else None
+            src.close()
+            for live in (0, 10 ** 5, 10 ** 6, 10 ** 7):
+                vol = make_volume(ctx, grid, (synth.TUM_ROWS, synth.TUM_COLS), K, colour=coloured)
+                vol.enable_spill(1 << 22)
+                vol.enable_reentry(live + n)
+                fq, fw = np.zeros_like(q), np.zeros_like(w)
+                left = live
+                while left > 0:   # whole grids of `left` observed voxels, pushed out of the window: exactly `live` entries
+                    fw.reshape(-1)[:] = 0
+                    fw.reshape(-1)[:min(left, n)] = 1
+                    vol.upload(fq, fw)
+                    vol.shift((0, 0, nz))
+                    left -= min(left, n)
+                vol.spilled(clear=True)
+                assert vol.reentry_stats()["live"] == live
+                vol.upload(q, w)
+                if coloured:
+                    vol.upload_colour(col)
+                shifts = (("one layer", (0, 0, 1)), ("quarter grid", (0, 0, nz // 4)))
+                for tag, d in shifts:
+                    re, pt = [], []
+                    for _ in range(args.runs):   # alternating
+                        re.append(vol.reentry_time(d, reps=args.reps))
+                        pt.append(vol.shift_time(d, reps=args.reps))
+                    re, pt = np.array(re), np.array(pt)
+                    row = dict(grid=grid, coloured=coloured, shift=tag, d=list(d), voxels=n, live_entries=live,
+                               observed_voxels=int((w > 0).sum()))
+                    for k, nm in enumerate(names):
+                        row[nm + "_us_median"] = round(float(np.median(re[:, k])), 2)
+                        row[nm + "_us_min_max"] = [round(float(re[:, k].min()), 2), round(float(re[:, k].max()), 2)]
+                    row["reentry_stages_us_median_sum"] = round(float(np.median(re, 0).sum()), 2)
+                    for k, nm in ((0, "shift"), (3, "spill_count"), (4, "spill_scan"), (5, "spill_scatter")):
+                        row[nm + "_us_median"] = round(float(np.median(pt[:, k])), 2)
+                    print(json.dumps(row), flush=True)
+                for tag, d in shifts:   # what each really saves, and what the way back restores
+                    s0 = vol.reentry_stats()
+                    vol.shift(d)
+                    s1 = vol.reentry_stats()
+                    vol.shift(tuple(-x for x in d))
+                    s2 = vol.reentry_stats()
+                    print(json.dumps(dict(grid=grid, coloured=coloured, shift=tag, applied=True, live_entries=live, saved=s1["saved"] - s0["saved"],
+                                          restored_on_the_way_back=s2["restored"] - s1["restored"], dropped=s2["dropped"],
+                                          grid_restored=bool(np.array_equal(vol.grid()[1], w)))), flush=True)
+                vol.close()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -455,11 +529,14 @@ def main():
     h.add_argument("--runs", type=int, default=7)
     h.add_argument("--reps", type=int, default=20)
     h.add_argument("--mesh", action="store_true")
+    h.add_argument("--reentry", action="store_true")
     args = ap.parse_args()
     if args.cmd == "icp" and args.photo:
         return icp_photo(args)
     if args.cmd == "shift" and args.mesh:
         return shift_mesh(args)
+    if args.cmd == "shift" and args.reentry:
+        return shift_reentry(args)
     dict(kernels=kernels, summary=summary, track=track, icp=icp, shift=shift)[args.cmd](args)
 
 
