@@ -105,24 +105,8 @@ extern "C" int odo_depth_filter_time_dev(odo_depth_filter* f, const uint16_t* in
   HIP_OK(hipSetDevice(f->device));
   const DfArgs a = df_args(f, in_dev, out_dev);
   hipStream_t s = f->ctx->stream;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  bool ok = hipEventCreate(&ev[0]) == hipSuccess && hipEventCreate(&ev[1]) == hipSuccess;
-  float ms = 0.0f;
-  if (ok) {
-    launch_depth_filter(a, s);   // (warm)
-    ok = hipEventRecord(ev[0], s) == hipSuccess;
-    for (int i = 0; i < reps; i++) launch_depth_filter(a, s);
-    ok = ok && hipEventRecord(ev[1], s) == hipSuccess && hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess &&
-         hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess;
-  }
-  for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-  if (!ok) {
-    (void)hipGetLastError();
-    (void)hipStreamSynchronize(s);
-    return fail("%s: timing failed", who);
-  }
-  *us = 1e3f * ms / (float)reps;
-  return 0;
+  const auto run = [&]() { launch_depth_filter(a, s); return true; };
+  return time_stages(who, s, reps, 1, us, run, [&](int) { return run(); });
 }
 
 extern "C" int odo_depth_filter_destroy(odo_depth_filter* f) {

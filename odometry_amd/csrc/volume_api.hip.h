@@ -109,6 +109,44 @@ static int volume_sync(odo_volume* v) {
   HIP_OK(hipStreamSynchronize(v->own));
   return 0;
 }
+// Waits, then reads one of the volume's device-resident counter blocks (the volume's own or a store's).
+template <class Counters>
+static int volume_read_counters(odo_volume* v, const Counters* dev, Counters* c) {
+  if (volume_sync(v)) return -1;
+  HIP_OK(hipMemcpyAsync(c, dev, sizeof(Counters), hipMemcpyDeviceToHost, v->own));
+  HIP_OK(hipStreamSynchronize(v->own));
+  return 0;
+}
+
+// Event timing in stages, the shape of every *_time entry point: warm() once, then for each of the n stages `reps` calls of stage(q)
+// between two events on s; us[q] = the mean time of one call in microseconds. Both callables enqueue on s and return success. A
+// failure anywhere drains s and is reported as who's.
+constexpr int kTimedStages = 6;
+template <class Warm, class Stage>
+static int time_stages(const char* who, hipStream_t s, int reps, int n, float* us, Warm warm, Stage stage) {
+  hipEvent_t ev[kTimedStages + 1] = {};
+  bool ok = true;
+  for (int q = 0; q <= n; q++) ok = ok && hipEventCreate(&ev[q]) == hipSuccess;
+  ok = ok && warm() && hipEventRecord(ev[0], s) == hipSuccess;
+  for (int q = 0; q < n && ok; q++) {
+    for (int i = 0; i < reps && ok; i++) ok = stage(q);
+    ok = ok && hipEventRecord(ev[q + 1], s) == hipSuccess;
+  }
+  ok = ok && hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+  for (int q = 0; q < n && ok; q++) {
+    float ms = 0.0f;
+    ok = hipEventElapsedTime(&ms, ev[q], ev[q + 1]) == hipSuccess;
+    us[q] = 1e3f * ms / (float)reps;
+  }
+  for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+  if (!ok) {
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(s);
+    return fail("%s: timing failed", who);
+  }
+  return 0;
+}
+
 static int volume_reset(odo_volume* v) {
   if (volume_order_on(v, v->own)) return -1;
   HIP_OK(hipMemsetAsync(v->d_vox, 0, sizeof(uint32_t) * (size_t)v->n_vox, v->own));
@@ -271,17 +309,10 @@ extern "C" int odo_volume_sync(odo_volume* v) {
   return volume_sync(v);
 }
 
-static int volume_counters(odo_volume* v, VolCounters* c) {
-  if (volume_sync(v)) return -1;
-  HIP_OK(hipMemcpyAsync(c, v->d_ctr, sizeof(VolCounters), hipMemcpyDeviceToHost, v->own));
-  HIP_OK(hipStreamSynchronize(v->own));
-  return 0;
-}
-
 extern "C" int odo_volume_stats(odo_volume* v, long out[4]) {
   if (!v || !out) return fail("odo_volume_stats: NULL arg");
   VolCounters c;
-  if (volume_counters(v, &c)) return -1;
+  if (volume_read_counters(v, v->d_ctr, &c)) return -1;
   out[0] = v->n_frames; out[1] = (long)c.updated; out[2] = (long)c.band; out[3] = (long)c.cumulative;
   return 0;
 }
@@ -575,24 +606,10 @@ extern "C" int odo_volume_raycast_time(odo_volume* v, const odo_raycast_params* 
   if (with_colour && !v->colour) return fail("%s: the volume has no colour grid (odo_volume_enable_colour first)", who);
   HIP_OK(hipSetDevice(v->device));
   if (volume_ray_frames(who, v, (long)rp->rows * rp->cols, with_colour != 0)) return -1;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  bool ok = true;
-  for (auto& x : ev) ok = ok && hipEventCreate(&x) == hipSuccess;
-  float ms = 0.0f;
-  for (int i = 0; ok && i <= reps; i++) {
-    ok = volume_raycast_launch(v, rp, abs_pose_colmajor, v->d_ray_depth, nullptr, v->d_ray_nrmw, with_colour ? v->d_ray_rgba : nullptr) == 0;
-    if (i == 0) ok = ok && hipEventRecord(ev[0], v->own) == hipSuccess;   // (behind the warming launch)
-  }
-  ok = ok && hipEventRecord(ev[1], v->own) == hipSuccess && hipStreamSynchronize(v->own) == hipSuccess &&
-       hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess;
-  for (auto& x : ev) if (x) (void)hipEventDestroy(x);
-  if (!ok) {
-    (void)hipGetLastError();
-    (void)hipStreamSynchronize(v->own);
-    return fail("%s: timing failed", who);
-  }
-  *us = 1e3f * ms / (float)reps;
-  return 0;
+  const auto cast = [&]() {
+    return volume_raycast_launch(v, rp, abs_pose_colmajor, v->d_ray_depth, nullptr, v->d_ray_nrmw, with_colour ? v->d_ray_rgba : nullptr) == 0;
+  };
+  return time_stages(who, v->own, reps, 1, us, cast, [&](int) { return cast(); });
 }
 
 extern "C" int odo_volume_clear(odo_volume* v) {

@@ -7,24 +7,22 @@
 #include "volume_colour.hip.h"
 #include "volume_colour_math.h"
 #include "volume_mesh_table.h"
+#include "volume_scan.hip.h"
 
 namespace odo {
 
 // ---- colours of the extraction's points -------------------------------------------------------------------------------------------
-// A thread per voxel, volume_scatter_kernel's index arithmetic: block offset + the points of the waves before + the points of the
-// lanes before; one dword per point.
+// A thread per voxel at volume_scatter_kernel's index (block offset + volume_scan.hip.h's rank); one dword per point.
 __global__ void __launch_bounds__(kVolExtBlock) volume_extract_colour_kernel(VolExtractColourArgs ac) {
   const VolExtractArgs& a = ac.a;
   const int v = blockIdx.x * kVolExtBlock + threadIdx.x;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const unsigned long long* wm = a.wave_mask + 3 * (size_t)blockIdx.x * (kVolExtBlock / 64);
-  const unsigned long long bx = wm[3 * w], by = wm[3 * w + 1], bz = wm[3 * w + 2];
-  const unsigned long long bit = 1ull << lane;
+  const unsigned long long bit = 1ull << (threadIdx.x & 63);
+  unsigned long long e[3];
+  ballot_wave(a.wave_mask, e);
+  const unsigned long long bx = e[0], by = e[1], bz = e[2];
   if (v >= a.n || !((bx | by | bz) & bit)) return;
-  int pre = 0;
-  for (int q = 0; q < 3 * w; q++) pre += __popcll(wm[q]);
-  const unsigned long long below = bit - 1ull;
-  unsigned long long idx = a.blk_off[blockIdx.x] + (unsigned long long)(pre + __popcll(bx & below) + __popcll(by & below) + __popcll(bz & below));
+  const int rank = ballot_rank<3, int>(a.wave_mask, e);
+  unsigned long long idx = a.blk_off[blockIdx.x] + (unsigned long long)rank;
   const unsigned long long cap = (unsigned long long)a.capacity;
   if (idx >= cap) return;
   const uint32_t va = a.g.vox[v], ca = ac.col[v];
@@ -45,7 +43,8 @@ void launch_volume_extract_colour(const VolExtractColourArgs& a, hipStream_t s) 
 }
 
 // ---- colours of the mesh's vertices -----------------------------------------------------------------------------------------------
-// A thread per voxel: the vertex kernel left the voxel's first index (vertex_base) beside its edge mask.
+// A thread per voxel: the vertex kernel left the voxel's first index (vertex_base) beside its edge mask. The body is
+// volume_mesh_emit.hip.h's mesh_vertex_colours in this kernel's own text: calling the function cost 3 to 5 % (see that header).
 __global__ void __launch_bounds__(kMeshBlock) volume_mesh_colour_kernel(VolMeshColourArgs ac) {
   const VolMeshArgs& a = ac.a;
   const int v = blockIdx.x * kMeshBlock + threadIdx.x;

@@ -184,30 +184,18 @@ static int icp_time(const char* who, odo_volume* v, const IcpFrames& f, const fl
                     float huber_delta, const odo_icp_photo_params* ph, int reps, float us[2]) {
   IcpEval<N> e;
   if (icp_eval_prepare(&e, v, f, P_m, Cm, stride, dist_max, huber_delta, ph, nullptr)) return -1;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  bool ok = true;
-  for (auto& x : ev) ok = ok && hipEventCreate(&x) == hipSuccess;
-  if (ok) {
+  const auto warm = [&]() {
     launch_volume_icp_init(e.sc.state, e.init, v->own);
-    launch_volume_icp_rows(e.rows, v->own);   // (warm)
+    launch_volume_icp_rows(e.rows, v->own);
     launch_volume_icp_step(e.fold, v->own);
-    ok = hipEventRecord(ev[0], v->own) == hipSuccess;
-    for (int i = 0; i < reps; i++) launch_volume_icp_rows(e.rows, v->own);
-    ok = ok && hipEventRecord(ev[1], v->own) == hipSuccess;
-    for (int i = 0; i < reps; i++) launch_volume_icp_step(e.fold, v->own);
-    ok = ok && hipEventRecord(ev[2], v->own) == hipSuccess && hipGetLastError() == hipSuccess && hipStreamSynchronize(v->own) == hipSuccess;
-    float ms0 = 0.0f, ms1 = 0.0f;
-    ok = ok && hipEventElapsedTime(&ms0, ev[0], ev[1]) == hipSuccess && hipEventElapsedTime(&ms1, ev[1], ev[2]) == hipSuccess;
-    us[0] = 1e3f * ms0 / (float)reps;
-    us[1] = 1e3f * ms1 / (float)reps;
-  }
-  for (auto& x : ev) if (x) (void)hipEventDestroy(x);
-  if (!ok) {
-    (void)hipGetLastError();
-    (void)hipStreamSynchronize(v->own);
-    return fail("%s: timing failed", who);
-  }
-  return 0;
+    return true;
+  };
+  const auto stage = [&](int q) {
+    if (q == 0) launch_volume_icp_rows(e.rows, v->own);
+    else launch_volume_icp_step(e.fold, v->own);
+    return true;
+  };
+  return time_stages(who, v->own, reps, 2, us, warm, stage);
 }
 
 static void icp_nan_pose(float* A) {

@@ -111,8 +111,9 @@ void launch_volume_integrate_colour(const VolIntegrateColourArgs& a, hipStream_t
 }
 
 // ---- extraction ----------------------------------------------------------------------------------------------------------------
+// The passes are volume_scan.hip.h's: the three ballots per wave and the block's count, the scan of the counts, a thread's rank and
+// its voxel's points.
 __global__ void __launch_bounds__(kVolExtBlock) volume_count_kernel(VolExtractArgs a) {
-  __shared__ int sh[kVolExtBlock / 64];
   const int v = blockIdx.x * kVolExtBlock + threadIdx.x;
   bool ex = false, ey = false, ez = false;
   if (v < a.n) {
@@ -126,73 +127,28 @@ __global__ void __launch_bounds__(kVolExtBlock) volume_count_kernel(VolExtractAr
       ez = k + 1 < a.g.nz && vox_edge(va, a.g.vox[v + sz]);
     }
   }
-  const unsigned long long bx = __ballot(ex), by = __ballot(ey), bz = __ballot(ez);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    unsigned long long* wm = a.wave_mask + 3 * ((size_t)blockIdx.x * (kVolExtBlock / 64) + w);
-    wm[0] = bx; wm[1] = by; wm[2] = bz;
-    sh[w] = __popcll(bx) + __popcll(by) + __popcll(bz);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int t = 0;
-    for (int q = 0; q < kVolExtBlock / 64; q++) t += sh[q];
-    a.blk[blockIdx.x] = t;
-  }
+  const unsigned long long b[3] = {__ballot(ex), __ballot(ey), __ballot(ez)};
+  ballot_counts(b, a.wave_mask, a.blk);
 }
 
-// One block: exclusive scan of the per-block counts, 1024 at a time (coalesced loads and stores, a running base), the total, the
-// clamp at capacity.
+// One block: the blocks' exclusive offsets, the total, the clamp at capacity.
 __global__ void __launch_bounds__(kVolScanThreads) volume_scan_kernel(VolExtractArgs a) {
-  __shared__ unsigned wsum[kVolScanThreads / 64];
-  const int t = threadIdx.x;
-  unsigned long long base = 0;
-  for (int c0 = 0; c0 < a.nblk; c0 += kVolScanThreads) {
-    const int b = c0 + t;
-    const unsigned s = b < a.nblk ? (unsigned)a.blk[b] : 0u;   // (<= 3 072 per block: a chunk's sum stays far below 2^32)
-    const ScanRank r = scan_block<kVolScanThreads>(s, wsum);
-    if (b < a.nblk) a.blk_off[b] = base + (unsigned long long)r.rank;
-    base += r.total;
-    __syncthreads();   // wsum is written again
-  }
-  if (t == 0) {
-    a.ctr->ext_total = base;
-    a.ctr->ext_written = base < (unsigned long long)a.capacity ? base : (unsigned long long)a.capacity;
+  const unsigned long long total = scan_counts<kVolScanThreads, 1>(a.blk, a.blk_off, a.nblk).t[0];
+  if (threadIdx.x == 0) {
+    a.ctr->ext_total = total;
+    a.ctr->ext_written = total < (unsigned long long)a.capacity ? total : (unsigned long long)a.capacity;
   }
 }
 
 __global__ void __launch_bounds__(kVolExtBlock) volume_scatter_kernel(VolExtractArgs a) {
   const int v = blockIdx.x * kVolExtBlock + threadIdx.x;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const unsigned long long* wm = a.wave_mask + 3 * (size_t)blockIdx.x * (kVolExtBlock / 64);
-  const unsigned long long bx = wm[3 * w], by = wm[3 * w + 1], bz = wm[3 * w + 2];
-  const unsigned long long bit = 1ull << lane;
-  if (v >= a.n || !((bx | by | bz) & bit)) return;
-  int pre = 0;
-  for (int q = 0; q < 3 * w; q++) pre += __popcll(wm[q]);
-  const unsigned long long below = bit - 1ull;
-  unsigned long long idx = a.blk_off[blockIdx.x] + (unsigned long long)(pre + __popcll(bx & below) + __popcll(by & below) + __popcll(bz & below));
-  if (idx >= (unsigned long long)a.capacity) return;   // (so are this voxel's later edges)
-  int i, j, k;
-  vox_ijk(a.g, v, &i, &j, &k);
-  const uint32_t va = a.g.vox[v];
-  float ga[3], gb[3];
-  const bool has_a = vox_gradient(a.g, v, i, j, k, va, ga);
-  const float cx = vox_centre(a.g.ox, i, a.g.vs), cy = vox_centre(a.g.oy, j, a.g.vs), cz = vox_centre(a.g.oz, k, a.g.vs);
-  const unsigned long long bits[3] = {bx, by, bz};
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    if (!(bits[c] & bit)) continue;
-    if (idx >= (unsigned long long)a.capacity) return;
-    const int dx = c == 0, dy = c == 1, dz = c == 2;
-    const long long vb_i = vox_corner_word(a.g, v, 1 << c);
-    const uint32_t vb = a.g.vox[vb_i];
-    const bool has_b = vox_gradient(a.g, vb_i, i + dx, j + dy, k + dz, vb, gb);
-    const VoxEdgePoint e = vox_edge_point(va, vb, has_a, ga, has_b, gb, cx, cy, cz, a.g.vs, dx, dy, dz);
-    a.xyz0[idx] = make_float4(e.x, e.y, e.z, 0.0f);
-    a.nrmw[idx] = make_float4(e.nx, e.ny, e.nz, e.w);
-    idx++;
-  }
+  const unsigned long long bit = 1ull << (threadIdx.x & 63);
+  unsigned long long e[3];
+  ballot_wave(a.wave_mask, e);
+  if (v >= a.n || !((e[0] | e[1] | e[2]) & bit)) return;
+  const int rank = ballot_rank<3, int>(a.wave_mask, e);
+  const unsigned long long idx = a.blk_off[blockIdx.x] + (unsigned long long)rank;
+  extract_points(a.g, v, e, bit, idx, (unsigned long long)a.capacity, a.xyz0, a.nrmw, nullptr, nullptr);
 }
 
 void launch_volume_extract(const VolExtractArgs& a, hipStream_t s) {

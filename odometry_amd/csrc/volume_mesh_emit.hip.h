@@ -1,10 +1,14 @@
 // volume_mesh_emit.hip.h — the device code that the mesh of the window (volume_mesh_kernels.hip) and the mesh of the leaving slab
-// (volume_shift_kernels.hip) share: what a voxel contributes to the mesh (mesh_voxel, compiled by both), and a
-// voxel's vertices, its cell's triangles and its vertices' colours as functions, which the slab's kernels call. The window's vertex,
-// triangle and colour kernels keep these three bodies in their own text: calling the functions from them changed a few instructions
-// of their gfx950 code (an if-conversion, two operand orders), and their code is held instruction for instruction; the tests hold
-// the two to the same bits. The arithmetic is volume_math.h's and volume_colour_math.h's (fp32, one rounding per operation: every
-// unit is built with -ffp-contract=off and correctly rounded divide / sqrt), the triangles are integers out of volume_mesh_table.h.
+// (volume_shift_kernels.hip) share: what a voxel contributes to the mesh (mesh_voxel), and a voxel's
+// vertices, its cell's triangles and its vertices' colours as functions. Both units' vertex and triangle kernels call mesh_vertices
+// and mesh_triangles: in the window's kernels the call moves an if-conversion and two operand orders (vertices, 16 of 2 298 lines
+// of gfx950 code) or one instruction's place (triangles), same registers, and their times are the parent's within what kernels
+// with identical code move in the same runs. mesh_vertex_colours is called by the slab's colour kernel
+// only: volume_mesh_colour_kernel (volume_colour_kernels.hip) keeps the same body in its own text, because calling the function
+// cost it 15 instructions more and, measured against the parent in alternating runs, 15.64 -> 16.38 us on the pinned grid and
+// 97.78 -> 100.98 us on the large one (+4.7 % / +3.3 %, identical kernels within 2.3 %); the tests hold the two to the same bits.
+// The arithmetic is volume_math.h's and volume_colour_math.h's (fp32, one rounding per operation: every unit is built with
+// -ffp-contract=off and correctly rounded divide / sqrt), the triangles are integers out of volume_mesh_table.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -5,7 +5,7 @@
 // table of volume_mesh_table.h. Nothing is combined across threads but counts.
 #include <hip/hip_runtime.h>
 #include "volume_mesh.hip.h"
-#include "volume_mesh_emit.hip.h"   // mesh_voxel: shared with the mesh of the leaving slab
+#include "volume_mesh_emit.hip.h"   // shared with the mesh of the leaving slab
 #include "volume_scan.hip.h"
 
 namespace odo {
@@ -13,7 +13,6 @@ namespace odo {
 __constant__ MtetTable c_mtet = make_mtet_table();   // 672 bytes, derived at compile time
 
 __global__ void __launch_bounds__(kMeshBlock) volume_mesh_count_kernel(VolMeshArgs a) {
-  __shared__ unsigned sh[2][kMeshBlock / 64];
   const int v = blockIdx.x * kMeshBlock + threadIdx.x;
   unsigned nv = 0, nt = 0;
   if (v < a.n) {
@@ -24,45 +23,18 @@ __global__ void __launch_bounds__(kMeshBlock) volume_mesh_count_kernel(VolMeshAr
     nv = (unsigned)__popc(mask);
     nt = live ? (unsigned)mtet_cell_count(pos8) : 0u;
   }
-  for (int o = 32; o > 0; o >>= 1) { nv += __shfl_xor(nv, o, 64); nt += __shfl_xor(nt, o, 64); }
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { sh[0][w] = nv; sh[1][w] = nt; }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    unsigned t = 0;
-    for (int q = 0; q < kMeshBlock / 64; q++) t += sh[threadIdx.x][q];
-    a.blk[2 * blockIdx.x + threadIdx.x] = t;   // (<= 7 168 vertices, <= 12 288 triangles per block)
-  }
+  block_sum2<kMeshBlock>(nv, nt, a.blk);   // (<= 7 168 vertices, <= 12 288 triangles per block)
 }
 
-// One block: exclusive scans of both per-block counts, 1024 blocks at a time (coalesced, a running base), the totals, the clamps.
+// One block: both per-block counts' exclusive offsets (volume_scan.hip.h), the totals, the clamps.
 __global__ void __launch_bounds__(kMeshScanThreads) volume_mesh_scan_kernel(VolMeshArgs a) {
-  __shared__ unsigned wsum[2][kMeshScanThreads / 64];
-  const int t = threadIdx.x;
-  unsigned long long base[2] = {0, 0};
-  for (int c0 = 0; c0 < a.nblk; c0 += kMeshScanThreads) {
-    const int b = c0 + t;
-    unsigned s[2], inc[2];
-#pragma unroll
-    for (int x = 0; x < 2; x++) {
-      s[x] = b < a.nblk ? a.blk[2 * b + x] : 0u;   // (a chunk's sum is at most 1024 * 12 288: far below 2^32)
-      inc[x] = scan_wave(s[x], wsum[x]);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int x = 0; x < 2; x++) {
-      const ScanRank r = scan_rank<kMeshScanThreads>(s[x], inc[x], wsum[x]);
-      if (b < a.nblk) a.blk_off[2 * b + x] = base[x] + (unsigned long long)r.rank;
-      base[x] += r.total;
-    }
-    __syncthreads();   // wsum is written again
-  }
-  if (t == 0) {
+  const ScanTotals<2> total = scan_counts<kMeshScanThreads, 2>(a.blk, a.blk_off, a.nblk);
+  if (threadIdx.x == 0) {
     const unsigned long long vc = (unsigned long long)a.vertex_capacity, tc = (unsigned long long)a.triangle_capacity;
-    a.ctr->v_total = base[0];
-    a.ctr->v_written = base[0] < vc ? base[0] : vc;
-    a.ctr->t_total = base[1];
-    a.ctr->t_written = base[1] < tc ? base[1] : tc;
+    a.ctr->v_total = total.t[0];
+    a.ctr->v_written = total.t[0] < vc ? total.t[0] : vc;
+    a.ctr->t_total = total.t[1];
+    a.ctr->t_written = total.t[1] < tc ? total.t[1] : tc;
   }
 }
 
@@ -71,29 +43,11 @@ __global__ void __launch_bounds__(kMeshBlock) volume_mesh_vertex_kernel(VolMeshA
   const int v = blockIdx.x * kMeshBlock + threadIdx.x;
   const unsigned mask = v < a.n ? (unsigned)a.edge_mask[v] : 0u;
   const unsigned rank = scan_block<kMeshBlock>((unsigned)__popc(mask), wsum).rank;
-  unsigned long long idx = a.blk_off[2 * blockIdx.x] + rank;
+  const unsigned long long idx = a.blk_off[2 * blockIdx.x] + rank;
   if (v < a.n) a.vertex_base[v] = (uint32_t)idx;   // (the host ends the call when the total does not fit 31 bits)
   const unsigned long long cap = (unsigned long long)a.vertex_capacity;
   if (!mask || idx >= cap) return;   // (so are this voxel's later vertices)
-  int i, j, k;
-  vox_ijk(a.g, v, &i, &j, &k);
-  const uint32_t va = a.g.vox[v];
-  float ga[3], gb[3];
-  const bool has_a = vox_gradient(a.g, v, i, j, k, va, ga);
-  const float cx = vox_centre(a.g.ox, i, a.g.vs), cy = vox_centre(a.g.oy, j, a.g.vs), cz = vox_centre(a.g.oz, k, a.g.vs);
-  for (int e = 0; e < 7; e++) {
-    if (!((mask >> e) & 1u)) continue;
-    if (idx >= cap) return;
-    const int c = mtet_dir_offset(e);
-    const int dx = c & 1, dy = (c >> 1) & 1, dz = (c >> 2) & 1;
-    const long long vb_i = vox_corner_word(a.g, v, c);
-    const uint32_t vb = a.g.vox[vb_i];
-    const bool has_b = vox_gradient(a.g, vb_i, i + dx, j + dy, k + dz, vb, gb);
-    const VoxEdgePoint p = vox_edge_point(va, vb, has_a, ga, has_b, gb, cx, cy, cz, a.g.vs, dx, dy, dz);
-    a.xyz0[idx] = make_float4(p.x, p.y, p.z, (float)e);
-    a.nrmw[idx] = make_float4(p.nx, p.ny, p.nz, p.w);
-    idx++;
-  }
+  mesh_vertices(a.g, v, mask, idx, cap, a.xyz0, a.nrmw);
 }
 
 __global__ void __launch_bounds__(kMeshBlock) volume_mesh_triangle_kernel(VolMeshArgs a) {
@@ -107,31 +61,9 @@ __global__ void __launch_bounds__(kMeshBlock) volume_mesh_triangle_kernel(VolMes
     nt = live ? (unsigned)mtet_cell_count(pos8) : 0u;
   }
   const unsigned rank = scan_block<kMeshBlock>(nt, wsum).rank;
-  unsigned long long idx = a.blk_off[2 * blockIdx.x + 1] + rank;
-  const unsigned long long cap = (unsigned long long)a.triangle_capacity;
+  const unsigned long long idx = a.blk_off[2 * blockIdx.x + 1] + rank;
   if (!nt) return;
-  for (int t = 0; t < 6; t++) {
-    const int m = mtet_mask(t, pos8);
-    const int n = mtet_count(m);
-    for (int r = 0; r < n; r++) {
-      if (idx >= cap) return;   // (so are the cell's later triangles)
-      int id[3];
-#pragma unroll
-      for (int x = 0; x < 3; x++) {
-        int c, e;
-        mtet_lookup(c_mtet, t, m, r, x, &c, &e);
-        const long long owner = vox_corner_word(a.g, v, c);   // (a live cell: all eight corners are inside the grid)
-        id[x] = (int)(a.vertex_base[owner] + (unsigned)__popc((unsigned)a.edge_mask[owner] & ((1u << e) - 1u)));
-      }
-      // the smallest index first, the cyclic order kept
-      int o0 = id[0], o1 = id[1], o2 = id[2];
-      if (id[1] < id[0] && id[1] < id[2]) { o0 = id[1]; o1 = id[2]; o2 = id[0]; }
-      else if (id[2] < id[0] && id[2] < id[1]) { o0 = id[2]; o1 = id[0]; o2 = id[1]; }
-      int* out = a.tri + 3 * idx;
-      out[0] = o0; out[1] = o1; out[2] = o2;
-      idx++;
-    }
-  }
+  mesh_triangles(a.g, c_mtet, v, pos8, idx, (unsigned long long)a.triangle_capacity, a.vertex_base, a.edge_mask, a.tri);
 }
 
 void launch_volume_mesh_count(const VolMeshArgs& a, hipStream_t s) {

@@ -40,52 +40,23 @@ extern "C" int odo_volume_enable_reentry(odo_volume* v, long capacity) {
   if (v->attached) return fail("%s: the volume is attached to a tracker (odo_tracker_attach_volume(t, NULL) first)", who);
   HIP_OK(hipSetDevice(v->device));
   if (volume_shift_buffers(who, v)) return -1;
-  const size_t ne = (size_t)(capacity + kSpillGuard);
+  const size_t ne = (size_t)capacity;
   const size_t nblk = (size_t)((v->n_vox + kVolExtBlock - 1) / kVolExtBlock), sblk = (size_t)((capacity + kVolExtBlock - 1) / kVolExtBlock);
   const size_t waves = kVolExtBlock / 64;
-  uint4* ent[2] = {nullptr, nullptr};
-  uint32_t* col[2] = {nullptr, nullptr};
-  unsigned long long *save_mask = nullptr, *save_off = nullptr, *keep_mask = nullptr, *keep_off = nullptr;
-  unsigned *save_cnt = nullptr, *keep_cnt = nullptr;
-  VolReentryCounters *ctr = nullptr, *ctr_time = nullptr;
-  bool ok = true;
-  for (int s = 0; s < 2; s++)
-    ok = ok && hipMalloc((void**)&ent[s], sizeof(uint4) * ne) == hipSuccess &&
-         (!v->colour || hipMalloc((void**)&col[s], sizeof(uint32_t) * ne) == hipSuccess);
-  ok = ok && hipMalloc((void**)&save_mask, sizeof(unsigned long long) * waves * nblk) == hipSuccess &&
-       hipMalloc((void**)&save_off, sizeof(unsigned long long) * nblk) == hipSuccess &&
-       hipMalloc((void**)&save_cnt, sizeof(unsigned) * nblk) == hipSuccess &&
-       hipMalloc((void**)&keep_mask, sizeof(unsigned long long) * waves * sblk) == hipSuccess &&
-       hipMalloc((void**)&keep_off, sizeof(unsigned long long) * sblk) == hipSuccess &&
-       hipMalloc((void**)&keep_cnt, sizeof(unsigned) * sblk) == hipSuccess &&
-       hipMalloc((void**)&ctr, sizeof(VolReentryCounters)) == hipSuccess &&
-       hipMalloc((void**)&ctr_time, sizeof(VolReentryCounters)) == hipSuccess;
-  ok = ok && volume_order_on(v, v->own) == 0 && hipMemsetAsync(ctr, 0, sizeof(VolReentryCounters), v->own) == hipSuccess &&
-       hipMemsetAsync(ctr_time, 0, sizeof(VolReentryCounters), v->own) == hipSuccess;
-  for (int s = 0; s < 2; s++)
-    ok = ok && hipMemsetAsync(ent[s], 0xAB, sizeof(uint4) * ne, v->own) == hipSuccess &&
-         (!col[s] || hipMemsetAsync(col[s], 0xAB, sizeof(uint32_t) * ne, v->own) == hipSuccess);
-  ok = ok && volume_mark(v, v->own) == 0;
-  if (!ok) {
-    (void)hipGetLastError();
-    (void)hipStreamSynchronize(v->own);
-    void* ps[] = {ent[0], ent[1], col[0], col[1], save_mask, save_off, save_cnt, keep_mask, keep_off, keep_cnt, ctr, ctr_time};
-    for (void* p : ps) if (p) (void)hipFree(p);
+  if (!volume_store_alloc(v, {{(void**)&v->d_re_ent, sizeof(uint4), ne, kGuarded},
+                              {(void**)&v->d_re_ent2, sizeof(uint4), ne, kGuarded},
+                              {v->colour ? (void**)&v->d_re_col : nullptr, sizeof(uint32_t), ne, kGuarded},
+                              {v->colour ? (void**)&v->d_re_col2 : nullptr, sizeof(uint32_t), ne, kGuarded},
+                              {(void**)&v->d_re_save_mask, sizeof(unsigned long long), waves * nblk, kPlain},
+                              {(void**)&v->d_re_save_off, sizeof(unsigned long long), nblk, kPlain},
+                              {(void**)&v->d_re_save_cnt, sizeof(unsigned), nblk, kPlain},
+                              {(void**)&v->d_re_keep_mask, sizeof(unsigned long long), waves * sblk, kPlain},
+                              {(void**)&v->d_re_keep_off, sizeof(unsigned long long), sblk, kPlain},
+                              {(void**)&v->d_re_keep_cnt, sizeof(unsigned), sblk, kPlain},
+                              {(void**)&v->d_re_ctr, sizeof(VolReentryCounters), 1, kZeroed},
+                              {(void**)&v->d_re_ctr_time, sizeof(VolReentryCounters), 1, kZeroed}}))
     return fail("%s: device allocation failed (%ld entries)", who, capacity);
-  }
-  v->d_re_ent = ent[0]; v->d_re_ent2 = ent[1]; v->d_re_col = col[0]; v->d_re_col2 = col[1];
-  v->d_re_save_mask = save_mask; v->d_re_save_off = save_off; v->d_re_save_cnt = save_cnt;
-  v->d_re_keep_mask = keep_mask; v->d_re_keep_off = keep_off; v->d_re_keep_cnt = keep_cnt;
-  v->d_re_ctr = ctr; v->d_re_ctr_time = ctr_time;
   v->re_capacity = capacity;
-  return 0;
-}
-
-// Waits, then reads the store's counters.
-static int volume_reentry_counters(odo_volume* v, VolReentryCounters* c) {
-  if (volume_sync(v)) return -1;
-  HIP_OK(hipMemcpyAsync(c, v->d_re_ctr, sizeof(*c), hipMemcpyDeviceToHost, v->own));
-  HIP_OK(hipStreamSynchronize(v->own));
   return 0;
 }
 
@@ -96,7 +67,7 @@ extern "C" int odo_volume_reentry_voxels(odo_volume* v, long capacity, int32_t (
   if (v->re_capacity <= 0) return fail("%s: the volume has no re-entry store (odo_volume_enable_reentry first)", who);
   if (col && !v->d_re_col) return fail("%s: the store has no colours (odo_volume_enable_colour before odo_volume_enable_reentry)", who);
   VolReentryCounters c;
-  if (volume_reentry_counters(v, &c)) return -1;
+  if (volume_read_counters(v, v->d_re_ctr, &c)) return -1;
   *n = (long)c.live;
   if (capacity > 0 && c.live > (unsigned long long)capacity)
     return fail("%s: the store holds %llu entries, the buffers %ld (nothing copied, nothing cleared; the count is returned)", who, c.live,
@@ -125,7 +96,7 @@ extern "C" int odo_volume_reentry_stats(odo_volume* v, long stats[4]) {
   if (!v || !stats) return fail("%s: NULL arg", who);
   if (v->re_capacity <= 0) return fail("%s: the volume has no re-entry store (odo_volume_enable_reentry first)", who);
   VolReentryCounters c;
-  if (volume_reentry_counters(v, &c)) return -1;
+  if (volume_read_counters(v, v->d_re_ctr, &c)) return -1;
   stats[0] = (long)c.live; stats[1] = (long)c.saved; stats[2] = (long)c.restored; stats[3] = (long)c.dropped;
   return 0;
 }
@@ -140,41 +111,24 @@ extern "C" int odo_volume_reentry_time(odo_volume* v, const int d[3], int reps, 
   if (v->re_capacity <= 0) return fail("%s: the volume has no re-entry store (odo_volume_enable_reentry first)", who);
   if (v->attached) return fail("%s: the volume is attached to a tracker (odo_tracker_attach_volume(t, NULL) first)", who);
   int off[3];
-  for (int c = 0; c < 3; c++)
-    if (!shift_offset(v->off[c], d[c], &off[c]))
-      return fail("%s: the window would be %lld voxels from where it was created on axis %d (at most 2^24)", who, (long long)v->off[c] + d[c], c);
+  if (volume_shift_window(who, v, d, off)) return -1;
   HIP_OK(hipSetDevice(v->device));
   if (volume_shift_buffers(who, v)) return -1;
   if (volume_order_on(v, v->own)) return -1;
   VolReentryArgs a = volume_reentry_args(v, d, off);
   a.rc = v->d_re_ctr_time;
   hipStream_t s = v->own;
-  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  bool ok = true;
-  for (auto& e : ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-  if (ok) {
-    ok = hipMemcpyAsync(v->d_re_ctr_time, v->d_re_ctr, sizeof(VolReentryCounters), hipMemcpyDeviceToDevice, s) == hipSuccess;
+  static const int order[5] = {0, 1, 3, 2, 4};   // (the shift's order: the scatter reads the store scan's `kept`)
+  const auto stage = [&](int q) { launch_volume_reentry_stage(a, order[q], s); return true; };
+  const auto warm = [&]() {
+    const bool ok = hipMemcpyAsync(v->d_re_ctr_time, v->d_re_ctr, sizeof(VolReentryCounters), hipMemcpyDeviceToDevice, s) == hipSuccess;
     launch_volume_shift(volume_shift_args(v, d), s);
-    static const int order[5] = {0, 1, 3, 2, 4};   // (the shift's order: the scatter reads the store scan's `kept`)
-    for (int st = 0; st < 4; st++) launch_volume_reentry_stage(a, order[st], s);   // (warm)
-    ok = ok && hipEventRecord(ev[0], s) == hipSuccess;
-    for (int q = 0; q < 5; q++) {
-      for (int i = 0; i < reps; i++) launch_volume_reentry_stage(a, order[q], s);
-      ok = ok && hipEventRecord(ev[1 + q], s) == hipSuccess;
-    }
-    ok = ok && hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-    for (int q = 0; q < 5 && ok; q++) {
-      float ms = 0.0f;
-      ok = hipEventElapsedTime(&ms, ev[q], ev[q + 1]) == hipSuccess;
-      us[order[q]] = 1e3f * ms / (float)reps;
-    }
-  }
-  for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-  if (!ok) {
-    (void)hipGetLastError();
-    (void)hipStreamSynchronize(s);
-    return fail("%s: timing failed", who);
-  }
+    for (int q = 0; q < 4; q++) stage(q);
+    return ok;
+  };
+  float t[5];
+  if (time_stages(who, s, reps, 5, t, warm, stage)) return -1;
+  for (int q = 0; q < 5; q++) us[order[q]] = t[q];
   return volume_mark(v, s);
 }
 
@@ -183,23 +137,17 @@ extern "C" int odo_debug_volume_reentry_guard(odo_volume* v, long* n_changed, lo
   if (!v || !n_changed || !n_guard) return fail("%s: NULL arg", who);
   if (v->re_capacity <= 0) return fail("%s: the volume has no re-entry store (odo_volume_enable_reentry first)", who);
   VolReentryCounters c;
-  if (volume_reentry_counters(v, &c)) return -1;
+  if (volume_read_counters(v, v->d_re_ctr, &c)) return -1;
   const size_t cap = (size_t)v->re_capacity, from = (size_t)std::min<unsigned long long>(c.live, (unsigned long long)cap);
-  std::vector<uint8_t> host;
-  try { host.resize(sizeof(uint4) * (cap + kSpillGuard - from)); } catch (...) { return fail("out of memory"); }
-  // behind the live entries of the live set, then the guards of both sets
-  const uint8_t* at[6] = {(const uint8_t*)(v->d_re_ent + from), (const uint8_t*)(v->d_re_col ? v->d_re_col + from : nullptr),
-                          (const uint8_t*)(v->d_re_ent + cap), (const uint8_t*)(v->d_re_ent2 + cap),
-                          (const uint8_t*)(v->d_re_col ? v->d_re_col + cap : nullptr), (const uint8_t*)(v->d_re_col2 ? v->d_re_col2 + cap : nullptr)};
-  const size_t bytes[6] = {sizeof(uint4) * (cap + kSpillGuard - from), sizeof(uint32_t) * (cap + kSpillGuard - from),
-                           sizeof(uint4) * kSpillGuard, sizeof(uint4) * kSpillGuard, sizeof(uint32_t) * kSpillGuard, sizeof(uint32_t) * kSpillGuard};
+  const size_t tail = cap + kSpillGuard - from, guard = (size_t)kSpillGuard;
   long bad[2] = {0, 0};
-  for (int b = 0; b < 6; b++) {
-    if (!at[b]) continue;
-    HIP_OK(hipMemcpyAsync(host.data(), at[b], bytes[b], hipMemcpyDeviceToHost, v->own));
-    HIP_OK(hipStreamSynchronize(v->own));
-    for (size_t i = 0; i < bytes[b]; i++) bad[b >= 2] += host[i] != 0xAB;
-  }
+  // behind the live entries of the live set, then the guards of both sets
+  if (volume_count_not_ab(v, {{v->d_re_ent + from, sizeof(uint4) * tail}, {v->d_re_col ? v->d_re_col + from : nullptr, sizeof(uint32_t) * tail}},
+                          &bad[0]) ||
+      volume_count_not_ab(v, {{v->d_re_ent + cap, sizeof(uint4) * guard}, {v->d_re_ent2 + cap, sizeof(uint4) * guard},
+                              {v->d_re_col ? v->d_re_col + cap : nullptr, sizeof(uint32_t) * guard},
+                              {v->d_re_col2 ? v->d_re_col2 + cap : nullptr, sizeof(uint32_t) * guard}}, &bad[1]))
+    return -1;
   *n_changed = bad[0];
   *n_guard = bad[1];
   return 0;

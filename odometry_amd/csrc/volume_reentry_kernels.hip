@@ -1,15 +1,14 @@
 // volume_reentry_kernels.hip — the re-entry store's kernels (volume_reentry.hip.h) as a translation unit of their own, plus their
 // host-side launchers: the voxels a shift pushes out of the window are saved with their global index, and those whose index lies in
-// the new window are put back. Integers only; the rules are volume_shift_math.h's. include/odometry_hip.h,
-// odo_volume_enable_reentry; DESIGN.md section 9.14.
+// the new window are put back. Integers only; the rules are volume_shift_math.h's, the ballots with their counts, the ranks and the
+// scans of the counts volume_scan.hip.h's with one mask per wave. include/odometry_hip.h, odo_volume_enable_reentry; DESIGN.md
+// section 9.14.
 #include <hip/hip_runtime.h>
 #include "volume_reentry.hip.h"
 #include "volume_shift_math.h"
 #include "volume_scan.hip.h"
 
 namespace odo {
-
-constexpr int kReWaves = kVolExtBlock / 64;
 
 // Voxel v's index on the three axes. The save's blocks are runs of kVolExtBlock voxels in raster order, so that block order and rank
 // give the store's order and the scan has as few blocks as the extraction's: the launch geometry does not hold (i, j, k).
@@ -18,48 +17,6 @@ __device__ __forceinline__ void reentry_ijk(const VolReentryArgs& a, int v, int*
   *i = v - row * a.nx;
   *k = row / a.ny;
   *j = row - *k * a.ny;
-}
-
-// The ballot of `bit` over every wave of the block into mask[block][wave], the block's count into cnt[block].
-__device__ __forceinline__ void reentry_ballot(bool bit, unsigned long long* mask, unsigned* cnt) {
-  __shared__ unsigned sh[kReWaves];
-  const unsigned long long b = __ballot(bit);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    mask[(size_t)blockIdx.x * kReWaves + w] = b;
-    sh[w] = (unsigned)__popcll(b);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned t = 0;
-    for (int q = 0; q < kReWaves; q++) t += sh[q];
-    cnt[blockIdx.x] = t;
-  }
-}
-
-// This thread's rank among the set bits of its block's masks, in thread order. Only for a thread whose own bit is set.
-__device__ __forceinline__ unsigned reentry_rank(const unsigned long long* mask) {
-  const unsigned long long* wm = mask + (size_t)blockIdx.x * kReWaves;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  unsigned pre = 0;
-  for (int q = 0; q < w; q++) pre += (unsigned)__popcll(wm[q]);
-  return pre + (unsigned)__popcll(wm[w] & ((1ull << lane) - 1ull));
-}
-
-// One block: the exclusive scan of cnt[0 .. nb) into off (volume_scan_kernel's walk), the sum into *total.
-__device__ __forceinline__ void reentry_scan(const unsigned* cnt, unsigned long long* off, int nb, unsigned long long* total) {
-  __shared__ unsigned wsum[kVolScanThreads / 64];
-  const int t = threadIdx.x;
-  unsigned long long base = 0;
-  for (int c0 = 0; c0 < nb; c0 += kVolScanThreads) {
-    const int b = c0 + t;
-    const unsigned s = b < nb ? cnt[b] : 0u;   // (<= 1 024 per block: a chunk's sum stays far below 2^32)
-    const ScanRank r = scan_block<kVolScanThreads>(s, wsum);
-    if (b < nb) off[b] = base + (unsigned long long)r.rank;
-    base += r.total;
-    __syncthreads();   // wsum is written again
-  }
-  if (t == 0) *total = base;
 }
 
 // ---- the save ----------------------------------------------------------------------------------------------------------------------
@@ -76,20 +33,23 @@ __global__ void __launch_bounds__(kVolExtBlock) volume_reentry_save_count_kernel
     return;
   }
   const bool save = leaves && reentry_saved(a.old_vox[v], a.old_col ? a.old_col[v] : 0u);
-  reentry_ballot(save, a.save_mask, a.save_cnt);
+  const unsigned long long b[1] = {__ballot(save)};
+  ballot_counts(b, a.save_mask, a.save_cnt);
 }
 
 __global__ void __launch_bounds__(kVolScanThreads) volume_reentry_save_scan_kernel(VolReentryArgs a) {
-  reentry_scan(a.save_cnt, a.save_off, a.nblk, &a.rc->pending);
+  const unsigned long long total = scan_counts<kVolScanThreads, 1>(a.save_cnt, a.save_off, a.nblk).t[0];
+  if (threadIdx.x == 0) a.rc->pending = total;
 }
 
 // The saved voxels behind the kept entries: index = kept + block offset + rank; nothing at or beyond capacity is written.
 __global__ void __launch_bounds__(kVolExtBlock) volume_reentry_save_scatter_kernel(VolReentryArgs a) {
   if (a.save_cnt[blockIdx.x] == 0u) return;   // (block-uniform; the count kernel left no masks for such a block)
   const int v = blockIdx.x * kVolExtBlock + threadIdx.x;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (!((a.save_mask[(size_t)blockIdx.x * kReWaves + w] >> lane) & 1ull)) return;   // (set for v < n only)
-  const unsigned long long idx = a.rc->kept + a.save_off[blockIdx.x] + reentry_rank(a.save_mask);
+  unsigned long long m[1];
+  ballot_wave(a.save_mask, m);
+  if (!((m[0] >> (threadIdx.x & 63)) & 1ull)) return;   // (set for v < n only)
+  const unsigned long long idx = a.rc->kept + a.save_off[blockIdx.x] + ballot_rank<1, unsigned>(a.save_mask, m);
   if (idx >= (unsigned long long)a.capacity) return;
   int i, j, k;
   reentry_ijk(a, v, &i, &j, &k);
@@ -115,21 +75,24 @@ __global__ void __launch_bounds__(kVolExtBlock) volume_reentry_store_count_kerne
       keep = true;
     }
   }
-  reentry_ballot(keep, a.keep_mask, a.keep_cnt);
+  const unsigned long long b[1] = {__ballot(keep)};
+  ballot_counts(b, a.keep_mask, a.keep_cnt);
 }
 
 __global__ void __launch_bounds__(kVolScanThreads) volume_reentry_store_scan_kernel(VolReentryArgs a) {
   const unsigned long long live = a.rc->live;
-  reentry_scan(a.keep_cnt, a.keep_off, (int)((live + kVolExtBlock - 1) / kVolExtBlock), &a.rc->kept);
+  const unsigned long long total = scan_counts<kVolScanThreads, 1>(a.keep_cnt, a.keep_off, (int)((live + kVolExtBlock - 1) / kVolExtBlock)).t[0];
+  if (threadIdx.x == 0) a.rc->kept = total;
 }
 
 // The kept entries in their order into the second set: index = block offset + rank (< live <= capacity).
 __global__ void __launch_bounds__(kVolExtBlock) volume_reentry_compact_kernel(VolReentryArgs a) {
   const unsigned long long live = a.rc->live, e = (unsigned long long)blockIdx.x * kVolExtBlock + threadIdx.x;
   if ((unsigned long long)blockIdx.x * kVolExtBlock >= live) return;   // (block-uniform)
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (!((a.keep_mask[(size_t)blockIdx.x * kReWaves + w] >> lane) & 1ull)) return;   // (set for e < live only)
-  const unsigned long long idx = a.keep_off[blockIdx.x] + reentry_rank(a.keep_mask);
+  unsigned long long m[1];
+  ballot_wave(a.keep_mask, m);
+  if (!((m[0] >> (threadIdx.x & 63)) & 1ull)) return;   // (set for e < live only)
+  const unsigned long long idx = a.keep_off[blockIdx.x] + ballot_rank<1, unsigned>(a.keep_mask, m);
   a.dst[idx] = a.src[e];
   if (a.dst_col) a.dst_col[idx] = a.src_col[e];
 }

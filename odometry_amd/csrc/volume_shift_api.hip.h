@@ -20,6 +20,62 @@
 // odo_debug_volume_spill_guard counts the bytes there that do not (held by tests/test_gpu_volume_shift.py).
 constexpr long kSpillGuard = 64;
 
+// One device allocation of a store: `items` of `item` bytes. kGuarded: kSpillGuard items more, all of it filled with 0xAB; kZeroed:
+// cleared (the counters); kPlain: left as allocated (the passes' scratch). p == nullptr: not wanted (no colour, scratch that exists).
+enum StoreFill { kPlain, kZeroed, kGuarded };
+struct StoreBuf {
+  void** p;
+  size_t item, items;
+  StoreFill fill;
+};
+
+// Allocates a store's buffers and fills them on the volume's own stream, behind whatever changed the volume last. Any failure: the
+// stream is drained, every buffer allocated here is freed and its pointer nullptr again, false (the message is the caller's).
+static bool volume_store_alloc(odo_volume* v, std::initializer_list<StoreBuf> bufs) {
+  const auto bytes = [](const StoreBuf& b) { return b.item * (b.items + (b.fill == kGuarded ? (size_t)kSpillGuard : 0)); };
+  bool ok = true;
+  for (const StoreBuf& b : bufs) ok = ok && (!b.p || hipMalloc(b.p, bytes(b)) == hipSuccess);
+  ok = ok && volume_order_on(v, v->own) == 0;
+  for (const StoreBuf& b : bufs)
+    ok = ok && (!b.p || b.fill == kPlain || hipMemsetAsync(*b.p, b.fill == kGuarded ? 0xAB : 0, bytes(b), v->own) == hipSuccess);
+  ok = ok && volume_mark(v, v->own) == 0;
+  if (ok) return true;
+  (void)hipGetLastError();
+  (void)hipStreamSynchronize(v->own);
+  for (const StoreBuf& b : bufs) {
+    if (b.p && *b.p) (void)hipFree(*b.p);
+    if (b.p) *b.p = nullptr;
+  }
+  return false;
+}
+
+// The guard hooks: copies each span of device memory back and adds the bytes that are not 0xAB to *bad. at == nullptr: no such span.
+struct GuardSpan {
+  const void* at;
+  size_t bytes;
+};
+static int volume_count_not_ab(odo_volume* v, std::initializer_list<GuardSpan> spans, long* bad) {
+  size_t most = 0;
+  for (const GuardSpan& g : spans) most = std::max(most, g.at ? g.bytes : 0);
+  std::vector<uint8_t> host;
+  try { host.resize(most); } catch (...) { return fail("out of memory"); }
+  for (const GuardSpan& g : spans) {
+    if (!g.at) continue;
+    HIP_OK(hipMemcpyAsync(host.data(), g.at, g.bytes, hipMemcpyDeviceToHost, v->own));
+    HIP_OK(hipStreamSynchronize(v->own));
+    for (size_t i = 0; i < g.bytes; i++) *bad += host[i] != 0xAB;
+  }
+  return 0;
+}
+
+// The window's offsets after a shift by d, refused when an axis would leave the range that the origin's arithmetic is exact on.
+static int volume_shift_window(const char* who, const odo_volume* v, const int d[3], int off[3]) {
+  for (int c = 0; c < 3; c++)
+    if (!shift_offset(v->off[c], d[c], &off[c]))
+      return fail("%s: the window would be %lld voxels from where it was created on axis %d (at most 2^24)", who, (long long)v->off[c] + d[c], c);
+  return 0;
+}
+
 // The grids' second buffers, which a shift writes into: allocated by the first of odo_volume_set_follow (so that an attached
 // tracker's frame call never allocates), the first shift, and the first shift after odo_volume_enable_colour; kept until destroy.
 static int volume_shift_buffers(const char* who, odo_volume* v) {
@@ -82,9 +138,7 @@ static VolReentryArgs volume_reentry_args(odo_volume* v, const int d[3], const i
 // Spill (when the volume has a store) and shift by d, on the volume's own stream. 0: enqueued, or d = 0 and nothing to do.
 static int volume_shift(const char* who, odo_volume* v, const int d[3]) {
   int off[3];
-  for (int c = 0; c < 3; c++)
-    if (!shift_offset(v->off[c], d[c], &off[c]))
-      return fail("%s: the window would be %lld voxels from where it was created on axis %d (at most 2^24)", who, (long long)v->off[c] + d[c], c);
+  if (volume_shift_window(who, v, d, off)) return -1;
   if (d[0] == 0 && d[1] == 0 && d[2] == 0) return 0;
   if (volume_shift_buffers(who, v)) return -1;
   if (volume_order_on(v, v->own)) return -1;
@@ -135,41 +189,21 @@ extern "C" int odo_volume_shift_time(odo_volume* v, const int d[3], int reps, fl
   const VolSpillArgs sa = store ? volume_spill_args(v, d) : VolSpillArgs{};
   const size_t bytes = sizeof(uint32_t) * (size_t)v->n_vox;
   hipStream_t s = v->own;
-  hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  bool ok = true;
-  for (auto& e : ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-  if (ok) {
-    launch_volume_shift(a, s);   // (warm)
+  const auto warm = [&]() {
+    launch_volume_shift(a, s);
     if (store) for (int st = 0; st < 3; st++) launch_volume_spill_stage(sa, st, s);
-    ok = hipEventRecord(ev[0], s) == hipSuccess;
-    for (int i = 0; i < reps; i++) launch_volume_shift(a, s);
-    ok = ok && hipEventRecord(ev[1], s) == hipSuccess;
-    for (int i = 0; i < reps && ok; i++) {
-      ok = hipMemcpyAsync(v->d_vox2, v->d_vox, bytes, hipMemcpyDeviceToDevice, s) == hipSuccess &&
-           (!v->colour || hipMemcpyAsync(v->d_col2, v->d_col, bytes, hipMemcpyDeviceToDevice, s) == hipSuccess);
-    }
-    ok = ok && hipEventRecord(ev[2], s) == hipSuccess;
-    for (int i = 0; i < reps && ok; i++) {
-      ok = hipMemsetAsync(v->d_vox2, 0, bytes, s) == hipSuccess && (!v->colour || hipMemsetAsync(v->d_col2, 0, bytes, s) == hipSuccess);
-    }
-    ok = ok && hipEventRecord(ev[3], s) == hipSuccess;
-    for (int st = 0; st < 3; st++) {
-      if (store) for (int i = 0; i < reps; i++) launch_volume_spill_stage(sa, st, s);
-      ok = ok && hipEventRecord(ev[4 + st], s) == hipSuccess;
-    }
-    ok = ok && hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-    for (int q = 0; q < 6 && ok; q++) {
-      float ms = 0.0f;
-      ok = hipEventElapsedTime(&ms, ev[q], ev[q + 1]) == hipSuccess;
-      us[q] = q >= 3 && !store ? 0.0f : 1e3f * ms / (float)reps;
-    }
-  }
-  for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-  if (!ok) {
-    (void)hipGetLastError();
-    (void)hipStreamSynchronize(s);
-    return fail("%s: timing failed", who);
-  }
+    return true;
+  };
+  const auto stage = [&](int q) {
+    if (q == 0) launch_volume_shift(a, s);
+    else if (q == 1) return hipMemcpyAsync(v->d_vox2, v->d_vox, bytes, hipMemcpyDeviceToDevice, s) == hipSuccess &&
+                            (!v->colour || hipMemcpyAsync(v->d_col2, v->d_col, bytes, hipMemcpyDeviceToDevice, s) == hipSuccess);
+    else if (q == 2) return hipMemsetAsync(v->d_vox2, 0, bytes, s) == hipSuccess && (!v->colour || hipMemsetAsync(v->d_col2, 0, bytes, s) == hipSuccess);
+    else if (store) launch_volume_spill_stage(sa, q - 3, s);
+    return true;
+  };
+  if (time_stages(who, s, reps, 6, us, warm, stage)) return -1;
+  if (!store) us[3] = us[4] = us[5] = 0.0f;
   return volume_mark(v, s);
 }
 
@@ -191,32 +225,15 @@ extern "C" int odo_volume_enable_spill(odo_volume* v, long capacity) {
   const int nblk = (int)((v->n_vox + kVolExtBlock - 1) / kVolExtBlock);
   // the extraction's scratch is the spill's too (both run on the volume's own stream); whichever comes first allocates all three
   const bool scratch = v->d_cnt != nullptr;
-  unsigned long long *wave = nullptr, *off = nullptr;
-  int* cnt = nullptr;
-  float4 *xyz0 = nullptr, *nrmw = nullptr;
-  uint32_t* rgba = nullptr;
-  VolSpillCounters* ctr = nullptr;
-  bool ok = (scratch || (hipMalloc((void**)&wave, sizeof(unsigned long long) * 3 * (kVolExtBlock / 64) * (size_t)nblk) == hipSuccess &&
-                         hipMalloc((void**)&off, sizeof(unsigned long long) * (size_t)nblk) == hipSuccess &&
-                         hipMalloc((void**)&cnt, sizeof(int) * (size_t)nblk) == hipSuccess)) &&
-            hipMalloc((void**)&xyz0, sizeof(float4) * (size_t)(capacity + kSpillGuard)) == hipSuccess &&
-            hipMalloc((void**)&nrmw, sizeof(float4) * (size_t)(capacity + kSpillGuard)) == hipSuccess &&
-            (!v->colour || hipMalloc((void**)&rgba, sizeof(uint32_t) * (size_t)(capacity + kSpillGuard)) == hipSuccess) &&
-            hipMalloc((void**)&ctr, sizeof(VolSpillCounters)) == hipSuccess;
-  ok = ok && volume_order_on(v, v->own) == 0 && hipMemsetAsync(ctr, 0, sizeof(VolSpillCounters), v->own) == hipSuccess &&
-       hipMemsetAsync(xyz0, 0xAB, sizeof(float4) * (size_t)(capacity + kSpillGuard), v->own) == hipSuccess &&
-       hipMemsetAsync(nrmw, 0xAB, sizeof(float4) * (size_t)(capacity + kSpillGuard), v->own) == hipSuccess &&
-       (!rgba || hipMemsetAsync(rgba, 0xAB, sizeof(uint32_t) * (size_t)(capacity + kSpillGuard), v->own) == hipSuccess) &&
-       volume_mark(v, v->own) == 0;
-  if (!ok) {
-    (void)hipGetLastError();
-    (void)hipStreamSynchronize(v->own);
-    void* ps[] = {wave, off, cnt, xyz0, nrmw, rgba, ctr};
-    for (void* p : ps) if (p) (void)hipFree(p);
+  const size_t n = (size_t)capacity;
+  if (!volume_store_alloc(v, {{scratch ? nullptr : (void**)&v->d_wave, sizeof(unsigned long long), 3 * (kVolExtBlock / 64) * (size_t)nblk, kPlain},
+                              {scratch ? nullptr : (void**)&v->d_off, sizeof(unsigned long long), (size_t)nblk, kPlain},
+                              {scratch ? nullptr : (void**)&v->d_cnt, sizeof(int), (size_t)nblk, kPlain},
+                              {(void**)&v->d_spill_xyz0, sizeof(float4), n, kGuarded},
+                              {(void**)&v->d_spill_nrmw, sizeof(float4), n, kGuarded},
+                              {v->colour ? (void**)&v->d_spill_rgba : nullptr, sizeof(uint32_t), n, kGuarded},
+                              {(void**)&v->d_spill_ctr, sizeof(VolSpillCounters), 1, kZeroed}}))
     return fail("odo_volume_enable_spill: device allocation failed (%ld points)", capacity);
-  }
-  if (!scratch) { v->d_wave = wave; v->d_off = off; v->d_cnt = cnt; }
-  v->d_spill_xyz0 = xyz0; v->d_spill_nrmw = nrmw; v->d_spill_rgba = rgba; v->d_spill_ctr = ctr;
   v->spill_capacity = capacity;
   return 0;
 }
@@ -228,10 +245,8 @@ extern "C" int odo_volume_spill_points(odo_volume* v, long capacity, float* xyz0
   if (v->spill_capacity <= 0) return fail("odo_volume_spill_points: the volume has no spill store (odo_volume_enable_spill first)");
   if (rgba && !v->d_spill_rgba)
     return fail("odo_volume_spill_points: the store has no colours (odo_volume_enable_colour before odo_volume_enable_spill)");
-  if (volume_sync(v)) return -1;
   VolSpillCounters c;
-  HIP_OK(hipMemcpyAsync(&c, v->d_spill_ctr, sizeof(c), hipMemcpyDeviceToHost, v->own));
-  HIP_OK(hipStreamSynchronize(v->own));
+  if (volume_read_counters(v, v->d_spill_ctr, &c)) return -1;
   const size_t n = (size_t)std::min<unsigned long long>(c.written, (unsigned long long)capacity);
   if (n > 0) {
     HIP_OK(hipMemcpyAsync(xyz0, v->d_spill_xyz0, sizeof(float4) * n, hipMemcpyDeviceToHost, v->own));
@@ -251,23 +266,13 @@ extern "C" int odo_volume_spill_points(odo_volume* v, long capacity, float* xyz0
 extern "C" int odo_debug_volume_spill_guard(odo_volume* v, long* n_changed) {
   if (!v || !n_changed) return fail("odo_debug_volume_spill_guard: NULL arg");
   if (v->spill_capacity <= 0) return fail("odo_debug_volume_spill_guard: the volume has no spill store (odo_volume_enable_spill first)");
-  if (volume_sync(v)) return -1;
   VolSpillCounters c;
-  HIP_OK(hipMemcpyAsync(&c, v->d_spill_ctr, sizeof(c), hipMemcpyDeviceToHost, v->own));
-  HIP_OK(hipStreamSynchronize(v->own));
+  if (volume_read_counters(v, v->d_spill_ctr, &c)) return -1;
   const size_t from = (size_t)std::min<unsigned long long>(c.written, (unsigned long long)v->spill_capacity);
   const size_t points = (size_t)(v->spill_capacity + kSpillGuard) - from;
-  std::vector<uint8_t> host;
-  try { host.resize(sizeof(float4) * points); } catch (...) { return fail("out of memory"); }
-  const void* at[3] = {v->d_spill_xyz0 + from, v->d_spill_nrmw + from, v->d_spill_rgba ? v->d_spill_rgba + from : nullptr};
-  const size_t bytes[3] = {sizeof(float4) * points, sizeof(float4) * points, sizeof(uint32_t) * points};
   long bad = 0;
-  for (int b = 0; b < 3; b++) {
-    if (!at[b]) continue;
-    HIP_OK(hipMemcpyAsync(host.data(), at[b], bytes[b], hipMemcpyDeviceToHost, v->own));
-    HIP_OK(hipStreamSynchronize(v->own));
-    for (size_t i = 0; i < bytes[b]; i++) bad += host[i] != 0xAB;
-  }
+  if (volume_count_not_ab(v, {{v->d_spill_xyz0 + from, sizeof(float4) * points}, {v->d_spill_nrmw + from, sizeof(float4) * points},
+                              {v->d_spill_rgba ? v->d_spill_rgba + from : nullptr, sizeof(uint32_t) * points}}, &bad)) return -1;
   *n_changed = bad;
   return 0;
 }
@@ -284,36 +289,14 @@ extern "C" int odo_volume_enable_spill_mesh(odo_volume* v, long vertex_capacity,
   if (v->attached) return fail("%s: the volume is attached to a tracker (odo_tracker_attach_volume(t, NULL) first)", who);
   HIP_OK(hipSetDevice(v->device));
   if (volume_mesh_scratch(who, v)) return -1;
-  const size_t nv = (size_t)(vertex_capacity + kSpillGuard), nt = (size_t)(triangle_capacity + kSpillGuard);
-  float4 *xyz0 = nullptr, *nrmw = nullptr;
-  uint32_t* rgba = nullptr;
-  int* tri = nullptr;
-  VolSpillMeshCounters* ctr = nullptr;
-  bool ok = hipMalloc((void**)&xyz0, sizeof(float4) * nv) == hipSuccess && hipMalloc((void**)&nrmw, sizeof(float4) * nv) == hipSuccess &&
-            (!v->colour || hipMalloc((void**)&rgba, sizeof(uint32_t) * nv) == hipSuccess) &&
-            hipMalloc((void**)&tri, 3 * sizeof(int) * nt) == hipSuccess && hipMalloc((void**)&ctr, sizeof(VolSpillMeshCounters)) == hipSuccess;
-  ok = ok && volume_order_on(v, v->own) == 0 && hipMemsetAsync(ctr, 0, sizeof(VolSpillMeshCounters), v->own) == hipSuccess &&
-       hipMemsetAsync(xyz0, 0xAB, sizeof(float4) * nv, v->own) == hipSuccess &&
-       hipMemsetAsync(nrmw, 0xAB, sizeof(float4) * nv, v->own) == hipSuccess &&
-       (!rgba || hipMemsetAsync(rgba, 0xAB, sizeof(uint32_t) * nv, v->own) == hipSuccess) &&
-       hipMemsetAsync(tri, 0xAB, 3 * sizeof(int) * nt, v->own) == hipSuccess && volume_mark(v, v->own) == 0;
-  if (!ok) {
-    (void)hipGetLastError();
-    (void)hipStreamSynchronize(v->own);
-    void* ps[] = {xyz0, nrmw, rgba, tri, ctr};
-    for (void* p : ps) if (p) (void)hipFree(p);
+  const size_t nv = (size_t)vertex_capacity, nt = (size_t)triangle_capacity;
+  if (!volume_store_alloc(v, {{(void**)&v->d_smesh_xyz0, sizeof(float4), nv, kGuarded},
+                              {(void**)&v->d_smesh_nrmw, sizeof(float4), nv, kGuarded},
+                              {v->colour ? (void**)&v->d_smesh_rgba : nullptr, sizeof(uint32_t), nv, kGuarded},
+                              {(void**)&v->d_smesh_tri, 3 * sizeof(int), nt, kGuarded},
+                              {(void**)&v->d_smesh_ctr, sizeof(VolSpillMeshCounters), 1, kZeroed}}))
     return fail("%s: device allocation failed (%ld vertices, %ld triangles)", who, vertex_capacity, triangle_capacity);
-  }
-  v->d_smesh_xyz0 = xyz0; v->d_smesh_nrmw = nrmw; v->d_smesh_rgba = rgba; v->d_smesh_tri = tri; v->d_smesh_ctr = ctr;
   v->smesh_vertex_capacity = vertex_capacity; v->smesh_triangle_capacity = triangle_capacity;
-  return 0;
-}
-
-// Waits, then reads the store's counters.
-static int volume_spill_mesh_counters(odo_volume* v, VolSpillMeshCounters* c) {
-  if (volume_sync(v)) return -1;
-  HIP_OK(hipMemcpyAsync(c, v->d_smesh_ctr, sizeof(*c), hipMemcpyDeviceToHost, v->own));
-  HIP_OK(hipStreamSynchronize(v->own));
   return 0;
 }
 
@@ -327,7 +310,7 @@ extern "C" int odo_volume_spill_mesh(odo_volume* v, long vertex_capacity, long t
   if (rgba && !v->d_smesh_rgba)
     return fail("%s: the store has no colours (odo_volume_enable_colour before odo_volume_enable_spill_mesh)", who);
   VolSpillMeshCounters c;
-  if (volume_spill_mesh_counters(v, &c)) return -1;
+  if (volume_read_counters(v, v->d_smesh_ctr, &c)) return -1;
   *n_vertices = (long)c.v_written;
   *n_triangles = (long)c.t_written;
   if (dropped) { dropped[0] = (long)(c.v_total - c.v_written); dropped[1] = (long)(c.t_total - c.t_written); }
@@ -366,29 +349,10 @@ extern "C" int odo_volume_spill_mesh_time(odo_volume* v, const int d[3], int rep
   if (volume_order_on(v, v->own)) return -1;
   const VolSpillMeshArgs sa = volume_spill_mesh_args(v, d);
   hipStream_t s = v->own;
-  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  bool ok = true;
-  for (auto& e : ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-  if (ok) {
-    for (int st = 0; st < 5; st++) launch_volume_spill_mesh_stage(sa, st, s);   // (warm)
-    ok = hipEventRecord(ev[0], s) == hipSuccess;
-    for (int st = 0; st < 5; st++) {
-      for (int i = 0; i < reps; i++) launch_volume_spill_mesh_stage(sa, st, s);
-      ok = ok && hipEventRecord(ev[1 + st], s) == hipSuccess;
-    }
-    ok = ok && hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-    for (int q = 0; q < 5 && ok; q++) {
-      float ms = 0.0f;
-      ok = hipEventElapsedTime(&ms, ev[q], ev[q + 1]) == hipSuccess;
-      us[q] = q == 4 && !sa.col ? 0.0f : 1e3f * ms / (float)reps;
-    }
-  }
-  for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-  if (!ok) {
-    (void)hipGetLastError();
-    (void)hipStreamSynchronize(s);
-    return fail("%s: timing failed", who);
-  }
+  const auto stage = [&](int st) { launch_volume_spill_mesh_stage(sa, st, s); return true; };
+  const auto warm = [&]() { for (int st = 0; st < 5; st++) stage(st); return true; };
+  if (time_stages(who, s, reps, 5, us, warm, stage)) return -1;
+  if (!sa.col) us[4] = 0.0f;
   return volume_mark(v, s);
 }
 
@@ -397,22 +361,14 @@ extern "C" int odo_debug_volume_spill_mesh_guard(odo_volume* v, long* n_changed)
   if (!v || !n_changed) return fail("%s: NULL arg", who);
   if (v->smesh_vertex_capacity <= 0) return fail("%s: the volume has no mesh store (odo_volume_enable_spill_mesh first)", who);
   VolSpillMeshCounters c;
-  if (volume_spill_mesh_counters(v, &c)) return -1;
+  if (volume_read_counters(v, v->d_smesh_ctr, &c)) return -1;
   const size_t vfrom = (size_t)std::min<unsigned long long>(c.v_written, (unsigned long long)v->smesh_vertex_capacity);
   const size_t tfrom = (size_t)std::min<unsigned long long>(c.t_written, (unsigned long long)v->smesh_triangle_capacity);
   const size_t nv = (size_t)(v->smesh_vertex_capacity + kSpillGuard) - vfrom, nt = (size_t)(v->smesh_triangle_capacity + kSpillGuard) - tfrom;
-  const void* at[4] = {v->d_smesh_xyz0 + vfrom, v->d_smesh_nrmw + vfrom, v->d_smesh_rgba ? v->d_smesh_rgba + vfrom : nullptr,
-                       v->d_smesh_tri + 3 * tfrom};
-  const size_t bytes[4] = {sizeof(float4) * nv, sizeof(float4) * nv, sizeof(uint32_t) * nv, 3 * sizeof(int32_t) * nt};
-  std::vector<uint8_t> host;
-  try { host.resize(std::max(bytes[0], bytes[3])); } catch (...) { return fail("out of memory"); }
   long bad = 0;
-  for (int b = 0; b < 4; b++) {
-    if (!at[b]) continue;
-    HIP_OK(hipMemcpyAsync(host.data(), at[b], bytes[b], hipMemcpyDeviceToHost, v->own));
-    HIP_OK(hipStreamSynchronize(v->own));
-    for (size_t i = 0; i < bytes[b]; i++) bad += host[i] != 0xAB;
-  }
+  if (volume_count_not_ab(v, {{v->d_smesh_xyz0 + vfrom, sizeof(float4) * nv}, {v->d_smesh_nrmw + vfrom, sizeof(float4) * nv},
+                              {v->d_smesh_rgba ? v->d_smesh_rgba + vfrom : nullptr, sizeof(uint32_t) * nv},
+                              {v->d_smesh_tri + 3 * tfrom, 3 * sizeof(int32_t) * nt}}, &bad)) return -1;
   *n_changed = bad;
   return 0;
 }

@@ -73,10 +73,10 @@ void launch_volume_shift(const VolShiftArgs& a, hipStream_t s) {
 }
 
 // ---- the spill -------------------------------------------------------------------------------------------------------------------
-// volume_count_kernel's ballots with the predicate ANDed in: the edge a -> b counts iff it carries a point and a or b leaves.
+// The extraction's passes (volume_scan.hip.h) with the predicate ANDed in: the edge a -> b counts iff it carries a point and a or b
+// leaves.
 __global__ void __launch_bounds__(kVolExtBlock) volume_spill_count_kernel(VolSpillArgs sa) {
   const VolExtractArgs& a = sa.a;
-  __shared__ int sh[kVolExtBlock / 64];
   const int v = blockIdx.x * kVolExtBlock + threadIdx.x;
   bool ex = false, ey = false, ez = false;
   if (v < a.n) {
@@ -91,76 +91,28 @@ __global__ void __launch_bounds__(kVolExtBlock) volume_spill_count_kernel(VolSpi
       ez = k + 1 < a.g.nz && (la || shift_leaves(k + 1, sa.dz, a.g.nz)) && vox_edge(va, a.g.vox[v + sz]);
     }
   }
-  const unsigned long long bx = __ballot(ex), by = __ballot(ey), bz = __ballot(ez);
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    unsigned long long* wm = a.wave_mask + 3 * ((size_t)blockIdx.x * (kVolExtBlock / 64) + w);
-    wm[0] = bx; wm[1] = by; wm[2] = bz;
-    sh[w] = __popcll(bx) + __popcll(by) + __popcll(bz);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int t = 0;
-    for (int q = 0; q < kVolExtBlock / 64; q++) t += sh[q];
-    a.blk[blockIdx.x] = t;
-  }
+  const unsigned long long b[3] = {__ballot(ex), __ballot(ey), __ballot(ez)};
+  ballot_counts(b, a.wave_mask, a.blk);
 }
 
-// One block: exclusive scan of the per-block counts (volume_scan_kernel's walk); the sum is left for scatter's clamp and advance.
+// One block: the blocks' exclusive offsets; the sum is left for scatter's clamp and advance.
 __global__ void __launch_bounds__(kVolScanThreads) volume_spill_scan_kernel(VolSpillArgs sa) {
-  const VolExtractArgs& a = sa.a;
-  __shared__ unsigned wsum[kVolScanThreads / 64];
-  const int t = threadIdx.x;
-  unsigned long long base = 0;
-  for (int c0 = 0; c0 < a.nblk; c0 += kVolScanThreads) {
-    const int b = c0 + t;
-    const unsigned s = b < a.nblk ? (unsigned)a.blk[b] : 0u;   // (<= 3 072 per block: a chunk's sum stays far below 2^32)
-    const ScanRank r = scan_block<kVolScanThreads>(s, wsum);
-    if (b < a.nblk) a.blk_off[b] = base + (unsigned long long)r.rank;
-    base += r.total;
-    __syncthreads();   // wsum is written again
-  }
-  if (t == 0) sa.sc->pending = base;
+  const unsigned long long total = scan_counts<kVolScanThreads, 1>(sa.a.blk, sa.a.blk_off, sa.a.nblk).t[0];
+  if (threadIdx.x == 0) sa.sc->pending = total;
 }
 
-// volume_scatter_kernel's points behind the store's earlier ones: index = written + block offset + rank; nothing at or beyond
-// capacity is written. The colour, when the store has one, is volume_extract_colour_kernel's.
+// The points behind the store's earlier ones: index = written + block offset + rank; nothing at or beyond capacity is written. With
+// the colours, when the store has them.
 __global__ void __launch_bounds__(kVolExtBlock) volume_spill_scatter_kernel(VolSpillArgs sa) {
   const VolExtractArgs& a = sa.a;
   const int v = blockIdx.x * kVolExtBlock + threadIdx.x;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const unsigned long long* wm = a.wave_mask + 3 * (size_t)blockIdx.x * (kVolExtBlock / 64);
-  const unsigned long long bx = wm[3 * w], by = wm[3 * w + 1], bz = wm[3 * w + 2];
-  const unsigned long long bit = 1ull << lane;
-  if (v >= a.n || !((bx | by | bz) & bit)) return;
-  int pre = 0;
-  for (int q = 0; q < 3 * w; q++) pre += __popcll(wm[q]);
-  const unsigned long long below = bit - 1ull, cap = (unsigned long long)a.capacity;
-  unsigned long long idx = sa.sc->written + a.blk_off[blockIdx.x] +
-                           (unsigned long long)(pre + __popcll(bx & below) + __popcll(by & below) + __popcll(bz & below));
-  if (idx >= cap) return;   // (so are this voxel's later edges)
-  int i, j, k;
-  vox_ijk(a.g, v, &i, &j, &k);
-  const uint32_t va = a.g.vox[v];
-  float ga[3], gb[3];
-  const bool has_a = vox_gradient(a.g, v, i, j, k, va, ga);
-  const float cx = vox_centre(a.g.ox, i, a.g.vs), cy = vox_centre(a.g.oy, j, a.g.vs), cz = vox_centre(a.g.oz, k, a.g.vs);
-  const uint32_t ca = sa.col ? sa.col[v] : 0u;
-  const unsigned long long bits[3] = {bx, by, bz};
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    if (!(bits[c] & bit)) continue;
-    if (idx >= cap) return;
-    const int dx = c == 0, dy = c == 1, dz = c == 2;
-    const long long vb_i = vox_corner_word(a.g, v, 1 << c);
-    const uint32_t vb = a.g.vox[vb_i];
-    const bool has_b = vox_gradient(a.g, vb_i, i + dx, j + dy, k + dz, vb, gb);
-    const VoxEdgePoint e = vox_edge_point(va, vb, has_a, ga, has_b, gb, cx, cy, cz, a.g.vs, dx, dy, dz);
-    a.xyz0[idx] = make_float4(e.x, e.y, e.z, 0.0f);
-    a.nrmw[idx] = make_float4(e.nx, e.ny, e.nz, e.w);
-    if (sa.col) sa.rgba[idx] = colour_interpolate(ca, sa.col[vb_i], vox_alpha(va, vb));
-    idx++;
-  }
+  const unsigned long long bit = 1ull << (threadIdx.x & 63);
+  unsigned long long e[3];
+  ballot_wave(a.wave_mask, e);
+  if (v >= a.n || !((e[0] | e[1] | e[2]) & bit)) return;
+  const int rank = ballot_rank<3, int>(a.wave_mask, e);
+  const unsigned long long idx = sa.sc->written + a.blk_off[blockIdx.x] + (unsigned long long)rank;
+  extract_points(a.g, v, e, bit, idx, (unsigned long long)a.capacity, a.xyz0, a.nrmw, sa.col, sa.rgba);
 }
 
 // One thread, behind the scatter that read `written`: the counters move on.
@@ -218,7 +170,6 @@ __device__ __forceinline__ bool spill_mesh_fits(const VolSpillMeshArgs& sa, unsi
 
 __global__ void __launch_bounds__(kMeshBlock) volume_spill_mesh_count_kernel(VolSpillMeshArgs sa) {
   const VolMeshArgs& a = sa.a;
-  __shared__ unsigned sh[2][kMeshBlock / 64];
   const int v = blockIdx.x * kMeshBlock + threadIdx.x;
   int i = 0, j = 0, k = 0;
   const bool near = spill_mesh_near(sa, v, &i, &j, &k);
@@ -241,41 +192,13 @@ __global__ void __launch_bounds__(kMeshBlock) volume_spill_mesh_count_kernel(Vol
     // (a live cell has all eight corners inside the grid: i + 1 < nx, j + 1 < ny, k + 1 < nz)
     nt = live && shift_cell_spilled(i, j, k, sa.dx, sa.dy, sa.dz, a.g.nx, a.g.ny, a.g.nz) ? (unsigned)mtet_cell_count(pos8) : 0u;
   }
-  for (int o = 32; o > 0; o >>= 1) { nv += __shfl_xor(nv, o, 64); nt += __shfl_xor(nt, o, 64); }
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { sh[0][w] = nv; sh[1][w] = nt; }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    unsigned t = 0;
-    for (int q = 0; q < kMeshBlock / 64; q++) t += sh[threadIdx.x][q];
-    a.blk[2 * blockIdx.x + threadIdx.x] = t;
-  }
+  block_sum2<kMeshBlock>(nv, nt, a.blk);
 }
 
-// One block: volume_mesh_scan_kernel's walk over both per-block counts; the two sums are left for the emitting kernels and advance.
+// One block: both per-block counts' exclusive offsets; the two sums are left for the emitting kernels and advance.
 __global__ void __launch_bounds__(kMeshScanThreads) volume_spill_mesh_scan_kernel(VolSpillMeshArgs sa) {
-  const VolMeshArgs& a = sa.a;
-  __shared__ unsigned wsum[2][kMeshScanThreads / 64];
-  const int t = threadIdx.x;
-  unsigned long long base[2] = {0, 0};
-  for (int c0 = 0; c0 < a.nblk; c0 += kMeshScanThreads) {
-    const int b = c0 + t;
-    unsigned s[2], inc[2];
-#pragma unroll
-    for (int x = 0; x < 2; x++) {
-      s[x] = b < a.nblk ? a.blk[2 * b + x] : 0u;   // (a chunk's sum is at most 1024 * 12 288: far below 2^32)
-      inc[x] = scan_wave(s[x], wsum[x]);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int x = 0; x < 2; x++) {
-      const ScanRank r = scan_rank<kMeshScanThreads>(s[x], inc[x], wsum[x]);
-      if (b < a.nblk) a.blk_off[2 * b + x] = base[x] + (unsigned long long)r.rank;
-      base[x] += r.total;
-    }
-    __syncthreads();   // wsum is written again
-  }
-  if (t == 0) { sa.sc->v_pending = base[0]; sa.sc->t_pending = base[1]; }
+  const ScanTotals<2> total = scan_counts<kMeshScanThreads, 2>(sa.a.blk, sa.a.blk_off, sa.a.nblk);
+  if (threadIdx.x == 0) { sa.sc->v_pending = total.t[0]; sa.sc->t_pending = total.t[1]; }
 }
 
 // volume_mesh_vertex_kernel behind the store's earlier vertices: index = v_written + block offset + rank, left per voxel as the

@@ -230,6 +230,25 @@ def test_track_equals_raycast_plus_align_and_changes_nothing(ctx, ribbed):
     vol.close()
 
 
+def test_the_timing_call_gives_two_figures_and_changes_nothing(ctx, ribbed):
+    """icp_time (tools/volume_cost.py icp): two finite figures >= 0, and the grid, the counters and the sums of an evaluation read the
+    same afterwards."""
+    k = 2
+    vol = _fused(ctx, ribbed, k)
+    q, w = vol.grid()
+    stats = vol.stats()
+    P_m = ribbed["poses"][k - 1]
+    depth, nrmw = vol.raycast(P_m)
+    acc = vol.icp_eval(ribbed["depth"][k], depth, nrmw, P_m, np.eye(4), stride=2)
+    us = vol.icp_time(ribbed["depth"][k], depth, nrmw, P_m, np.eye(4), stride=2, reps=3)
+    assert len(us) == 2 and all(np.isfinite(u) and u >= 0 for u in us), us
+    _grid_equal(vol, q, w, "after the timing call")
+    assert vol.stats() == stats
+    again = vol.icp_eval(ribbed["depth"][k], depth, nrmw, P_m, np.eye(4), stride=2)
+    assert acc[28] > 0 and np.array_equal(acc.view(np.uint64), again.view(np.uint64))
+    vol.close()
+
+
 def test_integrate_track_integrate_without_a_host_wait(ctx, ribbed):
     """An integration on the context's stream, a track on the volume's and a second integration, device frames, nothing waited for in
     between: the track sees the first integration and not the second, and the second is not lost."""

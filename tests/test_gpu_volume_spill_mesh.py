@@ -363,9 +363,22 @@ def test_clear_refusals_on_a_live_volume_timing_and_destroy_with_a_spill_pending
     _store_equals(vol, want["store"], "before timing")
     # the timing call changes neither the store nor the grids nor the window
     us = vol.spill_mesh_time((0, 2, 0), 3)
-    assert len(us) == 5 and all(x > 0 for x in us)
+    assert len(us) == 5 and all(np.isfinite(x) and x > 0 for x in us)
     _store_equals(vol, want["store"], "after timing")
     _after(vol, p, want, "after timing", off0=(0, 0, 0))
+    # without a colour grid the colour stage is not launched: its figure is exactly 0, and the grid and the store stay as they are
+    plain = _volume(ctx, p)
+    plain.enable_spill_mesh(*BIG)
+    plain.upload(q, w)
+    plain.shift(d)
+    before = (plain.grid(), plain.window(), plain.spilled_mesh(with_dropped=True))
+    us = plain.spill_mesh_time((0, 2, 0), 2)
+    assert len(us) == 5 and all(np.isfinite(x) and x > 0 for x in us[:4]) and us[4] == 0.0, us
+    after = (plain.grid(), plain.window(), plain.spilled_mesh(with_dropped=True))
+    assert before[1][0] == after[1][0] == d and before[2][3] == after[2][3] and len(before[2][0]) > 0
+    flat = lambda t: list(t[0]) + [np.asarray(t[1][1])] + list(t[2][:3])
+    assert all(x.tobytes() == y.tobytes() for x, y in zip(flat(before), flat(after)))
+    plain.close()
     # and the next spill lands behind the store's items as if the timing had not run
     vol.shift((0, 2, 0))
     _store_equals(vol, M.run_shifts(p, q, w, col, [d, (0, 2, 0)], BIG)["store"], "a spill after timing")
