@@ -428,10 +428,13 @@ def acc_matrix(acc):
     return A
 
 
-def icp_align_model(raw, depth_m, nrmw_m, P_m, P_init, p, ic, step=icp_step_py, sums=None):
+def icp_align_model(raw, depth_m, nrmw_m, P_m, P_init, p, ic, step=icp_step_py, sums=None, strided_sums=None):
     """The whole loop: dict(status, iterations, pairs, cost, eig_min, eig_max, C, abs_pose, trace [(level, acc, delta, C)]). step: the
     step function (the Python restatement, or the host library's); sums(rows8, mask) -> acc: the order of the sums (default: fp64
-    pairwise)."""
+    pairwise); strided_sums(rows8, mask, stride) -> acc: the same for an order that depends on the level's stride, as the kernels'
+    does (icp_acc_kernel_order)."""
+    if strided_sums:
+        assert sums is None
     M, Cm = icp_frame(P_m, P_init)
     status, n, trace, acc = 0, 0, [], None
     for level, (stride, iters) in enumerate(zip(ic["strides"], ic["iters"])):
@@ -439,7 +442,7 @@ def icp_align_model(raw, depth_m, nrmw_m, P_m, P_init, p, ic, step=icp_step_py, 
             if status:
                 break
             rows8, mask = icp_rows_model(raw, depth_m, nrmw_m, M, Cm, p, stride, ic["dist_max"], ic["huber_delta"])
-            acc = sums(rows8, mask) if sums else icp_acc(rows8, mask)[0]
+            acc = strided_sums(rows8, mask, stride) if strided_sums else sums(rows8, mask) if sums else icp_acc(rows8, mask)[0]
             failed, converged, delta, Cm = step(acc, Cm, ic["min_pairs"], ic["eps_t"], ic["eps_r"])
             trace.append((level, acc, delta, Cm))
             n += 1
