@@ -1148,6 +1148,58 @@ int odo_depth_filter_time_dev(odo_depth_filter* f, const uint16_t* in_dev, uint1
 /* Safe with a run in flight: waits for ctx's stream first. */
 int odo_depth_filter_destroy(odo_depth_filter* f);
 
+/* ---- Dense stereo depth: census matching from a rectified pair to a uint16 depth frame, exact to the last bit -------------------
+ * L, R: fp32 frames rows x cols, dense, rectified: a point at left column x with disparity d >= 0 lies at right column x - d.
+ * Integers dmin >= 1, dmin + 2 <= dmax <= 255, agg_radius A in 0 .. 3, uniqueness in 0 .. 99 (percent), lr_max >= 0 or -1 (no
+ * left-right check), max_raw in 1 .. 65535; k = (float)(16.0 * fx * baseline * depth_scale), computed in double, rounded once.
+ *   Census   9 wide x 7 high, 62 bits: neighbour < centre as fp32 (a NaN on either side: 0), where 4 <= x < cols - 4, 3 <= y < rows - 3.
+ *   Cost     h(x, y, d) = popcount(cL(x, y) ^ cR(x - d, y)); C(x, y, d) = sum of h(x + i, y + j, d) over |i|, |j| <= A (<= 3038).
+ *   Interior A + 4 <= x < cols - A - 4 and A + 3 <= y < rows - A - 3; d is admissible iff dmin <= d <= dmax and x - d >= A + 4. A pixel
+ *            without an admissible d is not interior: it gets 0 and is counted nowhere.
+ *   Winner   dl = the smallest admissible d of minimal cost c0.
+ *   Unique   c2 = the minimal cost over admissible d with |d - dl| > 1; rejected if there is none or unless c2 (100 - uniqueness) >
+ *            100 c0 (so a flat patch is always rejected).
+ *   L-R      CR(x', y, d) = C(x' + d, y, d) over the d for which left pixel x' + d is interior and d admissible there; dr = the
+ *            smallest such d of minimal cost; rejected unless |dr(x - dl, y) - dl| <= lr_max.
+ *   Sub-pixel, in sixteenths: cm = C(dl - 1), cp = C(dl + 1); f = 0 if dl is dmin or dmax, a neighbour is not admissible, or den =
+ *            cm - 2 c0 + cp <= 0; else with num = cm - cp, f = sgn(num) ((16 |num| + den) / (2 den)) (truncating), -8 .. 8.
+ *            q = 16 dl + f.
+ *   Depth    raw = rintf(k / (float)q), one correctly rounded fp32 division, half to even; raw > max_raw is a range reject (0).
+ * Outputs: the depth frame, a uint16 frame of q (0: none), and exact counters; the first reason of a rejection counts only. */
+typedef struct odo_stereo_depth odo_stereo_depth;
+typedef struct {
+  int rows, cols, dmin, dmax, agg_radius, uniqueness, lr_max, max_raw;
+  double fx, baseline, depth_scale;
+} odo_stereo_depth_params;
+/* Validates every bound above (and rows, cols in 1 .. 8192) before it touches the device: -1 with a message and *out untouched on
+ * any violation. A frame too small to have an interior pixel is valid and gives all zeros. Device memory, allocated once: 21 B per
+ * pixel (two census planes, dr, the q frame, an internal depth frame) + 32 B per tile of 64 x 4 pixels. ctx must outlive the matcher.
+ * One host thread at a time. */
+int odo_stereo_depth_create(odo_ctx* ctx, const odo_stereo_depth_params* p, odo_stereo_depth** out);
+/* Three launches on ctx's stream, returns at once: out_depth_dev = the depth of the pair (rows x cols uint16 on the device, dense;
+ * NULL: the matcher's internal frame, odo_stereo_depth_depth_dev; 8-byte alignment and cols % 4 == 0 take the wide stores). -1 and
+ * nothing enqueued for a NULL input, a misaligned pointer and an output that overlaps an input. Ordered behind it without a host wait:
+ * whatever is enqueued on ctx's stream afterwards (odo_dev_download, odo_ctx_synchronize, and of a volume created on ctx the calls
+ * that read a depth frame: odo_volume_integrate_dev / _colour_dev run on ctx's stream, odo_volume_icp_*_dev and odo_volume_track*_dev
+ * order the volume's stream behind it). NOT ordered behind it: a tracker, which reads its depth frame on a stream of its own
+ * (odo_ctx_synchronize(ctx) before odo_tracker_init_rgbd / _track_rgbd / _hint_next_rgbd receive the frame), and an RGB-D front
+ * end's submit_dev, which runs on the front end's stream. */
+int odo_stereo_depth_run_dev(odo_stereo_depth* s, const float* left_dev, const float* right_dev, uint16_t* out_depth_dev);
+/* The q frame of the last run (rows x cols uint16 on the device, the matcher's own; zeros before the first run). Does not wait. */
+int odo_stereo_depth_disparity_dev(odo_stereo_depth* s, const uint16_t** q_dev);
+/* The internal depth frame (what a run with out_depth_dev == NULL writes). Does not wait. */
+int odo_stereo_depth_depth_dev(odo_stereo_depth* s, const uint16_t** depth_dev);
+/* Of the last run, exact: interior, matched, rejected by uniqueness, by left-right, by range, the sum of q over the matched pixels as
+ * its low and its high 32-bit word, and a spare 0. Waits for ctx's stream. Zeros before the first run. */
+int odo_stereo_depth_stats(odo_stereo_depth* s, long out[8]);
+/* Diagnostic, like odo_depth_filter_time_dev: one run to warm, then for each of the three kernels `reps` (1 .. 10000) launches between
+ * two events on ctx's stream; us[0 .. 2] = the mean time of one census / right-match / left-match launch in microseconds. Waits. The
+ * outputs and the statistics are those of one run afterwards. */
+int odo_stereo_depth_time_dev(odo_stereo_depth* s, const float* left_dev, const float* right_dev, uint16_t* out_depth_dev, int reps,
+                              float us[3]);
+/* Safe with a run in flight: waits for ctx's stream first. */
+int odo_stereo_depth_destroy(odo_stereo_depth* s);
+
 /* ---- S sequences in lock step on one GPU (the data-parallel axis of SURVEY section 8e inside one device) -----------------
  * One odo_tracker tracks one sequence as a serial chain of ~70 short launches per frame, which leaves most of the chip
  * idle. odo_tracker_batch runs the same frame loop (ref: run_odometry_kitti_offline.cpp:198-271) for n_sequences independent

@@ -48,6 +48,12 @@ class DepthFilterParams(C.Structure):
                 ("shift", C.c_uint8 * 256)]
 
 
+class StereoDepthParams(C.Structure):
+    _fields_ = [("rows", C.c_int), ("cols", C.c_int), ("dmin", C.c_int), ("dmax", C.c_int), ("agg_radius", C.c_int),
+                ("uniqueness", C.c_int), ("lr_max", C.c_int), ("max_raw", C.c_int), ("fx", C.c_double), ("baseline", C.c_double),
+                ("depth_scale", C.c_double)]
+
+
 class VolumeParams(C.Structure):
     _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("voxel_size", C.c_float), ("origin", C.c_float * 3),
                 ("mu", C.c_float), ("max_depth", C.c_float), ("max_weight", C.c_int), ("rows", C.c_int), ("cols", C.c_int),
@@ -324,6 +330,13 @@ SIGNATURES = {
     "odo_depth_filter_stats": (C.c_int, [_vp, C.POINTER(C.c_long)]),
     "odo_depth_filter_time_dev": (C.c_int, [_vp, _vp, _vp, C.c_int, _fp]),
     "odo_depth_filter_destroy": (C.c_int, [_vp]),
+    "odo_stereo_depth_create": (C.c_int, [_vp, C.POINTER(StereoDepthParams), C.POINTER(_vp)]),
+    "odo_stereo_depth_run_dev": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "odo_stereo_depth_disparity_dev": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "odo_stereo_depth_depth_dev": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "odo_stereo_depth_stats": (C.c_int, [_vp, C.POINTER(C.c_long)]),
+    "odo_stereo_depth_time_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _fp]),
+    "odo_stereo_depth_destroy": (C.c_int, [_vp]),
 }
 
 _lib = None

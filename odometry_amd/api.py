@@ -1739,6 +1739,87 @@ class DepthFilter:
             pass
 
 
+class StereoDepth:
+    """Dense stereo depth on the device (odo_stereo_depth_*): a rectified pair of fp32 grey frames in, the uint16 depth frame a
+    sensor would give out, by census matching in exact integers (include/odometry_hip.h): three launches on the context's stream.
+    ctx_or_tracker: a Context, or a Tracker (its context). size = (rows, cols); fx in pixels, baseline in metres; candidates
+    min_disp .. max_disp; max_depth in metres (None: whatever fits 16 bits)."""
+
+    STATS = ("interior", "matched", "rej_unique", "rej_lr", "rej_range", "sum_q")
+
+    def __init__(self, ctx_or_tracker, size, fx, baseline, depth_scale=1000.0, min_disp=1, max_disp=127, agg_radius=2, uniqueness=10,
+                 lr_max=1, max_depth=None):
+        self.lib = L.load()
+        self._owner = ctx_or_tracker   # keeps the stream's owner alive as long as the matcher
+        self._ctx = ctx_or_tracker._ctx if isinstance(ctx_or_tracker, Tracker) else ctx_or_tracker.h
+        p = L.StereoDepthParams()
+        p.rows, p.cols = size
+        p.dmin, p.dmax, p.agg_radius, p.uniqueness, p.lr_max = int(min_disp), int(max_disp), int(agg_radius), int(uniqueness), int(lr_max)
+        p.max_raw = 65535 if max_depth is None else int(min(max(np.floor(float(max_depth) * float(depth_scale)), -1.0), 65535.0))
+        p.fx, p.baseline, p.depth_scale = float(fx), float(baseline), float(depth_scale)
+        self.params = p
+        self.rows, self.cols = p.rows, p.cols
+        self._out = None
+        self.h = None
+        h = C.c_void_p()
+        L.check(self.lib.odo_stereo_depth_create(self._ctx, C.byref(p), C.byref(h)), "odo_stereo_depth_create")
+        self.h = h
+
+    def run(self, left_dev, right_dev, out_dev=None):
+        """Enqueues the depth of the device pair and returns the handle of the output at once: out_dev, or the matcher's internal
+        frame (overwritten by the next such run)."""
+        L.check(self.lib.odo_stereo_depth_run_dev(self.h, left_dev, right_dev, out_dev), "odo_stereo_depth_run_dev")
+        return self._internal() if out_dev is None else out_dev
+
+    def _internal(self):
+        if self._out is None:
+            p = C.c_void_p()
+            L.check(self.lib.odo_stereo_depth_depth_dev(self.h, C.byref(p)), "odo_stereo_depth_depth_dev")
+            self._out = p
+        return self._out
+
+    def _fetch(self, dev):
+        out = np.empty((self.rows, self.cols), np.uint16)
+        L.check(self.lib.odo_dev_download(self._ctx, out.ctypes.data_as(C.c_void_p), dev, out.nbytes), "odo_dev_download")
+        return out
+
+    def disparity(self):
+        """The last run's q frame on the host, sixteenths of a pixel, 0 = none (ordered behind the run): rows x cols uint16."""
+        p = C.c_void_p()
+        L.check(self.lib.odo_stereo_depth_disparity_dev(self.h, C.byref(p)), "odo_stereo_depth_disparity_dev")
+        return self._fetch(p)
+
+    def download(self, out_dev=None):
+        """A depth frame on the host (ordered behind the run on the context's stream): rows x cols uint16."""
+        return self._fetch(self._internal() if out_dev is None else out_dev)
+
+    def stats(self):
+        """The last run's exact counters by name (waits for it)."""
+        o = (C.c_long * 8)()
+        L.check(self.lib.odo_stereo_depth_stats(self.h, o), "odo_stereo_depth_stats")
+        v = list(o)
+        return dict(zip(self.STATS, v[:5] + [v[5] + (v[6] << 32)]))
+
+    def time(self, left_dev, right_dev, out_dev=None, reps=20):
+        """Mean microseconds of one launch of each kernel, `reps` between two events (a diagnostic: tools/stereo_depth_cost.py):
+        dict(census, match_right, match_left)."""
+        us = (C.c_float * 3)()
+        L.check(self.lib.odo_stereo_depth_time_dev(self.h, left_dev, right_dev, out_dev, reps, us), "odo_stereo_depth_time_dev")
+        return dict(zip(("census", "match_right", "match_left"), list(us)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.odo_stereo_depth_destroy(self.h)
+            self.h = None
+            self._out = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def write_ply(path, xyzi):
     """(N, 4) float32 x, y, z, intensity -> binary little-endian PLY with float x y z and uchar red green blue (grey)."""
     xyzi = np.asarray(xyzi, np.float32).reshape(-1, 4)

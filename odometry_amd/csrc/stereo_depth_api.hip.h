@@ -1,0 +1,160 @@
+// stereo_depth_api.hip.h — the dense stereo matcher (odo_stereo_depth_*): the host object over the kernels of
+// stereo_depth_kernels.hip. A rectified pair of fp32 grey frames on the device in, a uint16 depth frame out, three launches on the
+// CONTEXT's stream: whatever the caller enqueues on that stream afterwards (odo_dev_download, odo_volume_integrate_dev of a volume
+// created on the same context) is ordered behind them without a host wait; a tracker reads its depth frame on a stream of its own and
+// is not. Included by odometry_hip.hip.
+#pragma once
+#include "stereo_depth.hip.h"
+
+struct odo_stereo_depth {
+  odo_ctx* ctx;
+  int device;
+  odo_stereo_depth_params p;
+  int blocks;              // workgroups of the left match launch = rows of `d_partials`
+  uint64_t* d_census;      // the left plane, then the right one: rows * cols words each
+  uint8_t* d_dr;           // rows * cols
+  uint16_t* d_q;           // rows * cols, zero until the first run
+  uint16_t* d_depth;       // the internal depth frame, zero until the first run that uses it
+  uint32_t* d_partials;    // [blocks][kSdStatWords], zero until the first run
+};
+
+static SdArgs sd_args(const odo_stereo_depth* s, const float* left, const float* right, uint16_t* out) {
+  SdArgs a;
+  memset(&a, 0, sizeof(a));
+  const size_t n = (size_t)s->p.rows * s->p.cols;
+  a.left = left; a.right = right; a.cl = s->d_census; a.cr = s->d_census + n; a.dr = s->d_dr;
+  a.depth = out ? out : s->d_depth; a.q = s->d_q; a.partials = s->d_partials;
+  a.rows = s->p.rows; a.cols = s->p.cols;
+  a.r.dmin = s->p.dmin; a.r.dmax = s->p.dmax; a.r.A = s->p.agg_radius; a.r.uniq = s->p.uniqueness; a.r.lr_max = s->p.lr_max;
+  a.r.max_raw = s->p.max_raw; a.r.k = sd_k(s->p.fx, s->p.baseline, s->p.depth_scale);
+  return a;
+}
+
+static void sd_free(odo_stereo_depth* s) {
+  if (s->d_census) (void)hipFree(s->d_census);
+  if (s->d_dr) (void)hipFree(s->d_dr);
+  if (s->d_q) (void)hipFree(s->d_q);
+  if (s->d_depth) (void)hipFree(s->d_depth);
+  if (s->d_partials) (void)hipFree(s->d_partials);
+}
+
+extern "C" int odo_stereo_depth_create(odo_ctx* ctx, const odo_stereo_depth_params* p, odo_stereo_depth** out) {
+  const char* who = "odo_stereo_depth_create";
+  if (!ctx || !p || !out) return fail("%s: NULL arg", who);
+  switch (sd_check_params(p->rows, p->cols, p->dmin, p->dmax, p->agg_radius, p->uniqueness, p->lr_max, p->max_raw, p->fx, p->baseline,
+                          p->depth_scale)) {
+    case 0: break;
+    case 1: return fail("%s: bad size %dx%d (1 .. %d each)", who, p->cols, p->rows, kSdMaxSize);
+    case 2: return fail("%s: dmin %d must be at least 1", who, p->dmin);
+    case 3: return fail("%s: dmax %d out of range (dmin + 2 .. %d)", who, p->dmax, kSdMaxDisp);
+    case 4: return fail("%s: agg_radius %d out of range (0 .. %d)", who, p->agg_radius, kSdMaxAgg);
+    case 5: return fail("%s: uniqueness %d out of range (0 .. 99 percent)", who, p->uniqueness);
+    case 6: return fail("%s: lr_max %d must be >= 0, or -1 for no left-right check", who, p->lr_max);
+    case 7: return fail("%s: max_raw %d out of range (1 .. 65535)", who, p->max_raw);
+    default: return fail("%s: 16 * fx * baseline * depth_scale must be a finite positive float", who);
+  }
+  HIP_OK(hipSetDevice(ctx->device));
+  odo_stereo_depth* s = new (std::nothrow) odo_stereo_depth();
+  if (!s) return fail("out of memory");
+  memset((void*)s, 0, sizeof(*s));
+  s->ctx = ctx; s->device = ctx->device; s->p = *p;
+  s->blocks = sd_blocks_x(p->cols) * sd_blocks_y(p->rows);
+  const size_t n = (size_t)p->rows * p->cols, pbytes = sizeof(uint32_t) * kSdStatWords * (size_t)s->blocks;
+  const bool ok = hipMalloc((void**)&s->d_census, 2 * sizeof(uint64_t) * n) == hipSuccess && hipMalloc((void**)&s->d_dr, n) == hipSuccess &&
+                  hipMalloc((void**)&s->d_q, sizeof(uint16_t) * n) == hipSuccess &&
+                  hipMalloc((void**)&s->d_depth, sizeof(uint16_t) * n) == hipSuccess &&
+                  hipMalloc((void**)&s->d_partials, pbytes) == hipSuccess &&
+                  hipMemsetAsync(s->d_q, 0, sizeof(uint16_t) * n, ctx->stream) == hipSuccess &&
+                  hipMemsetAsync(s->d_depth, 0, sizeof(uint16_t) * n, ctx->stream) == hipSuccess &&
+                  hipMemsetAsync(s->d_partials, 0, pbytes, ctx->stream) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(ctx->stream);
+    sd_free(s);
+    delete s;
+    return fail("%s: device allocation failed (%dx%d)", who, p->cols, p->rows);
+  }
+  *out = s;
+  return 0;
+}
+
+// NULL or misaligned frames, or an output that shares a byte with an input: -1 and nothing enqueued.
+static int sd_check_frames(const char* who, const odo_stereo_depth* s, const float* left, const float* right, const uint16_t* out) {
+  if (!s || !left || !right) return fail("%s: NULL arg", who);
+  if ((((uintptr_t)left | (uintptr_t)right) & 3) || ((uintptr_t)out & 1)) return fail("%s: misaligned frame", who);
+  if (out) {
+    const uintptr_t n = (uintptr_t)s->p.rows * s->p.cols, o0 = (uintptr_t)out;
+    const float* ins[2] = {left, right};
+    for (const float* in : ins) {
+      const uintptr_t i0 = (uintptr_t)in;
+      if (i0 < o0 + sizeof(uint16_t) * n && o0 < i0 + sizeof(float) * n) return fail("%s: the output overlaps an input frame", who);
+    }
+  }
+  return 0;
+}
+
+extern "C" int odo_stereo_depth_run_dev(odo_stereo_depth* s, const float* left_dev, const float* right_dev, uint16_t* out_depth_dev) {
+  if (sd_check_frames("odo_stereo_depth_run_dev", s, left_dev, right_dev, out_depth_dev)) return -1;
+  HIP_OK(hipSetDevice(s->device));
+  const SdArgs a = sd_args(s, left_dev, right_dev, out_depth_dev);
+  for (int stage = 0; stage < 3; stage++) launch_stereo_depth_stage(a, stage, s->ctx->stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int odo_stereo_depth_disparity_dev(odo_stereo_depth* s, const uint16_t** q_dev) {
+  if (!s || !q_dev) return fail("odo_stereo_depth_disparity_dev: NULL arg");
+  *q_dev = s->d_q;
+  return 0;
+}
+
+extern "C" int odo_stereo_depth_depth_dev(odo_stereo_depth* s, const uint16_t** depth_dev) {
+  if (!s || !depth_dev) return fail("odo_stereo_depth_depth_dev: NULL arg");
+  *depth_dev = s->d_depth;
+  return 0;
+}
+
+extern "C" int odo_stereo_depth_stats(odo_stereo_depth* s, long out[8]) {
+  if (!s || !out) return fail("odo_stereo_depth_stats: NULL arg");
+  HIP_OK(hipSetDevice(s->device));
+  std::vector<uint32_t> rows;
+  try { rows.resize((size_t)kSdStatWords * s->blocks); } catch (...) { return fail("out of memory"); }
+  HIP_OK(hipMemcpyAsync(rows.data(), s->d_partials, sizeof(uint32_t) * rows.size(), hipMemcpyDeviceToHost, s->ctx->stream));
+  HIP_OK(hipStreamSynchronize(s->ctx->stream));
+  unsigned long long sum[6] = {0, 0, 0, 0, 0, 0};
+  for (int b = 0; b < s->blocks; b++)   // in block order
+    for (int k = 0; k < 6; k++) sum[k] += rows[(size_t)kSdStatWords * b + k];
+  for (int k = 0; k < 5; k++) out[k] = (long)sum[k];
+  out[5] = (long)(sum[5] & 0xffffffffull);
+  out[6] = (long)(sum[5] >> 32);
+  out[7] = 0;
+  return 0;
+}
+
+// Event timing (tools/stereo_depth_cost.py): one run to warm, then for each of the three kernels `reps` launches between two events on
+// the context's stream; us[0 .. 2] the mean time of one census / right match / left match launch in microseconds. The outputs and the
+// statistics hold the result of one run afterwards.
+extern "C" int odo_stereo_depth_time_dev(odo_stereo_depth* s, const float* left_dev, const float* right_dev, uint16_t* out_depth_dev,
+                                         int reps, float us[3]) {
+  const char* who = "odo_stereo_depth_time_dev";
+  if (!us) return fail("%s: NULL arg", who);
+  if (sd_check_frames(who, s, left_dev, right_dev, out_depth_dev)) return -1;
+  if (reps < 1 || reps > 10000) return fail("%s: reps 1 .. 10000", who);
+  HIP_OK(hipSetDevice(s->device));
+  const SdArgs a = sd_args(s, left_dev, right_dev, out_depth_dev);
+  hipStream_t st = s->ctx->stream;
+  const auto warm = [&]() { for (int q = 0; q < 3; q++) launch_stereo_depth_stage(a, q, st); return true; };
+  float t[3] = {0.0f, 0.0f, 0.0f};
+  if (time_stages(who, st, reps, 3, t, warm, [&](int q) { launch_stereo_depth_stage(a, q, st); return true; })) return -1;
+  for (int q = 0; q < 3; q++) us[q] = t[q];
+  return 0;
+}
+
+extern "C" int odo_stereo_depth_destroy(odo_stereo_depth* s) {
+  if (!s) return 0;
+  (void)hipSetDevice(s->device);
+  (void)hipStreamSynchronize(s->ctx->stream);   // a run in flight reads and writes every block below
+  sd_free(s);
+  delete s;
+  return 0;
+}
