@@ -1200,6 +1200,54 @@ int odo_stereo_depth_time_dev(odo_stereo_depth* s, const float* left_dev, const 
 /* Safe with a run in flight: waits for ctx's stream first. */
 int odo_stereo_depth_destroy(odo_stereo_depth* s);
 
+/* ---- Speckle filter: small connected components of a uint16 key frame are removed, exact to the last bit ----------------------
+ * K: a key frame rows x cols uint16, dense, 0 = no value (the matcher's q frame, or a depth frame). Integers max_diff in 0 .. 65535
+ * and min_size in 1 .. 2^30; rows, cols in 1 .. 8192, so a linear pixel index y cols + x fits int32.
+ *   Connection  two pixels are connected iff they are 4-neighbours, both keys are non-zero, and |K_a - K_b| <= max_diff.
+ *   Component   a class of the transitive closure of that relation. Connection itself is not transitive: a ramp whose neighbours
+ *               each differ by exactly max_diff is one component. A non-zero pixel without a connected neighbour is a component of
+ *               size 1. A pixel with key 0 belongs to none.
+ *   Survival    a non-zero pixel survives iff its component has at least min_size pixels.
+ *   Output      every non-surviving pixel is set to 0 in each of up to two uint16 target frames of K's size, in place; K itself may
+ *               be one of them. Every other byte of the targets stays as it was. min_size == 1 removes nothing.
+ *   Counters    all exact: pixels (non-zero keys), components, removed_components, removed_pixels, largest (the largest component's
+ *               size), guard (0; see below).
+ * The result does not depend on any order of evaluation and nothing in it is floating point. The kernels are a union-find: integer
+ * atomicMin puts the larger root under the smaller, so a component's root is its smallest linear index whatever order the unions
+ * happen in, and sizes are integer sums. Every device loop whose trip count depends on data strictly decreases an index and also
+ * carries a hard trip bound; a loop that runs into the bound sets a bit of `guard` and leaves. */
+typedef struct odo_speckle odo_speckle;
+typedef struct {
+  int rows, cols, max_diff, min_size;
+} odo_speckle_params;
+/* Validates every bound above before it touches the device: -1 with the bound named in the message and *out untouched on any
+ * violation. Device memory, allocated once: 8 B per pixel (the parent and size planes) + 32 B per tile of 64 x 16 pixels. ctx must
+ * outlive the filter. One host thread at a time. */
+int odo_speckle_create(odo_ctx* ctx, const odo_speckle_params* p, odo_speckle** out);
+/* Four launches on ctx's stream, returns at once, no host wait: the components of key_dev, the non-surviving pixels zeroed in
+ * target_a_dev and, unless it is NULL, in target_b_dev (all rows x cols uint16 on the device, dense). A target may be key_dev. -1 and
+ * nothing enqueued for a NULL filter, key or target_a, a misaligned pointer and two different targets that overlap. Ordering is
+ * odo_depth_filter_run_dev's: what is enqueued on ctx's stream afterwards is ordered behind it; a tracker and an RGB-D front end's
+ * submit_dev are not. */
+int odo_speckle_run_dev(odo_speckle* s, const uint16_t* key_dev, uint16_t* target_a_dev, uint16_t* target_b_dev);
+/* Of the last run, exact: pixels, components, removed_components, removed_pixels, largest, guard, 0, 0. Waits for ctx's stream. Zeros
+ * before the first run. */
+int odo_speckle_stats(odo_speckle* s, long out[8]);
+/* Diagnostic: `reps` (1 .. 10000) launches between two events on ctx's stream for each prefix of the run, on scratch copies of the key
+ * and a target; us[0 .. 3] = the mean time of the label / seam / count / apply launch in microseconds (each the difference of two
+ * prefixes), us[4] = of the whole run. Waits. The targets and the statistics are those of exactly one run afterwards. */
+int odo_speckle_time_dev(odo_speckle* s, const uint16_t* key_dev, uint16_t* target_a_dev, uint16_t* target_b_dev, int reps,
+                         float us[5]);
+/* Safe with a run in flight: waits for ctx's stream first. */
+int odo_speckle_destroy(odo_speckle* s);
+/* Every later odo_stereo_depth_run_dev (and _time_dev) enqueues a speckle filter behind the left match, on the same stream: the key is
+ * the q frame, the targets are the q frame and the run's depth output, the internal frame or the caller's. The bounds are
+ * odo_speckle_create's; min_size == 0 takes the filter off again. odo_stereo_depth_stats keeps returning the match's own counters. A
+ * matcher on which this was never called enqueues what it always did. Waits for ctx's stream when it replaces a filter. */
+int odo_stereo_depth_enable_speckle(odo_stereo_depth* s, int max_diff, int min_size);
+/* odo_speckle_stats of the matcher's filter; -1 while none is enabled. */
+int odo_stereo_depth_speckle_stats(odo_stereo_depth* s, long out[8]);
+
 /* ---- S sequences in lock step on one GPU (the data-parallel axis of SURVEY section 8e inside one device) -----------------
  * One odo_tracker tracks one sequence as a serial chain of ~70 short launches per frame, which leaves most of the chip
  * idle. odo_tracker_batch runs the same frame loop (ref: run_odometry_kitti_offline.cpp:198-271) for n_sequences independent

@@ -54,6 +54,10 @@ class StereoDepthParams(C.Structure):
                 ("depth_scale", C.c_double)]
 
 
+class SpeckleParams(C.Structure):
+    _fields_ = [("rows", C.c_int), ("cols", C.c_int), ("max_diff", C.c_int), ("min_size", C.c_int)]
+
+
 class VolumeParams(C.Structure):
     _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("voxel_size", C.c_float), ("origin", C.c_float * 3),
                 ("mu", C.c_float), ("max_depth", C.c_float), ("max_weight", C.c_int), ("rows", C.c_int), ("cols", C.c_int),
@@ -337,6 +341,13 @@ SIGNATURES = {
     "odo_stereo_depth_stats": (C.c_int, [_vp, C.POINTER(C.c_long)]),
     "odo_stereo_depth_time_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _fp]),
     "odo_stereo_depth_destroy": (C.c_int, [_vp]),
+    "odo_speckle_create": (C.c_int, [_vp, C.POINTER(SpeckleParams), C.POINTER(_vp)]),
+    "odo_speckle_run_dev": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "odo_speckle_stats": (C.c_int, [_vp, C.POINTER(C.c_long)]),
+    "odo_speckle_time_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _fp]),
+    "odo_speckle_destroy": (C.c_int, [_vp]),
+    "odo_stereo_depth_enable_speckle": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "odo_stereo_depth_speckle_stats": (C.c_int, [_vp, C.POINTER(C.c_long)]),
 }
 
 _lib = None

@@ -1807,11 +1807,76 @@ class StereoDepth:
         L.check(self.lib.odo_stereo_depth_time_dev(self.h, left_dev, right_dev, out_dev, reps, us), "odo_stereo_depth_time_dev")
         return dict(zip(("census", "match_right", "match_left"), list(us)))
 
+    def enable_speckle(self, max_diff=8, min_size=200):
+        """Every later run enqueues a speckle filter behind the match (SpeckleFilter's rule; max_diff in sixteenths of a pixel): the
+        key is the q frame, the targets are the q frame and the run's depth output. min_size=0 takes it off again."""
+        L.check(self.lib.odo_stereo_depth_enable_speckle(self.h, int(max_diff), int(min_size)), "odo_stereo_depth_enable_speckle")
+
+    def speckle_stats(self):
+        """The last run's speckle counters by name (waits for it); an error while no filter is enabled."""
+        o = (C.c_long * 8)()
+        L.check(self.lib.odo_stereo_depth_speckle_stats(self.h, o), "odo_stereo_depth_speckle_stats")
+        return dict(zip(SpeckleFilter.STATS, list(o)[:len(SpeckleFilter.STATS)]))
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.odo_stereo_depth_destroy(self.h)
             self.h = None
             self._out = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SpeckleFilter:
+    """The speckle filter on the device (odo_speckle_*): the connected components of a uint16 key frame (4-neighbours, both keys
+    non-zero, |difference| <= max_diff) with fewer than min_size pixels are zeroed in up to two target frames, in place, in exact
+    integers (include/odometry_hip.h): four launches on the context's stream. ctx_or_tracker: a Context, or a Tracker (its
+    context). size = (rows, cols)."""
+
+    STATS = ("pixels", "components", "removed_components", "removed_pixels", "largest", "guard")
+    KERNELS = ("label", "seams", "count", "apply", "run")
+
+    def __init__(self, ctx_or_tracker, size, max_diff, min_size):
+        self.lib = L.load()
+        self._owner = ctx_or_tracker   # keeps the stream's owner alive as long as the filter
+        self._ctx = ctx_or_tracker._ctx if isinstance(ctx_or_tracker, Tracker) else ctx_or_tracker.h
+        p = L.SpeckleParams()
+        p.rows, p.cols = size
+        p.max_diff, p.min_size = int(max_diff), int(min_size)
+        self.params = p
+        self.rows, self.cols = p.rows, p.cols
+        self.h = None
+        h = C.c_void_p()
+        L.check(self.lib.odo_speckle_create(self._ctx, C.byref(p), C.byref(h)), "odo_speckle_create")
+        self.h = h
+
+    def run(self, key_dev, target_a_dev, target_b_dev=None):
+        """Enqueues the filter and returns at once: the components are those of key_dev, the pixels of the small ones are zeroed in
+        target_a_dev and target_b_dev (either may be key_dev itself)."""
+        L.check(self.lib.odo_speckle_run_dev(self.h, key_dev, target_a_dev, target_b_dev), "odo_speckle_run_dev")
+        return target_a_dev
+
+    def stats(self):
+        """The last run's exact counters by name (waits for it)."""
+        o = (C.c_long * 8)()
+        L.check(self.lib.odo_speckle_stats(self.h, o), "odo_speckle_stats")
+        return dict(zip(self.STATS, list(o)[:len(self.STATS)]))
+
+    def time(self, key_dev, target_a_dev, target_b_dev=None, reps=20):
+        """Mean microseconds of each kernel and of the whole run, `reps` between two events, on scratch copies (a diagnostic:
+        tools/speckle_cost.py): dict(label, seams, count, apply, run). The targets hold one run's result afterwards."""
+        us = (C.c_float * 5)()
+        L.check(self.lib.odo_speckle_time_dev(self.h, key_dev, target_a_dev, target_b_dev, reps, us), "odo_speckle_time_dev")
+        return dict(zip(self.KERNELS, list(us)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.odo_speckle_destroy(self.h)
+            self.h = None
 
     def __del__(self):
         try:

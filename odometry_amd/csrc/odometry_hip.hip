@@ -3334,6 +3334,7 @@ extern "C" int odo_depth_report(const odo_depth* d, int* iters, float* cost, int
 #include "volume_icp_api.hip.h"
 #include "rgbd_frontend_api.hip.h"
 #include "depth_filter_api.hip.h"
+#include "speckle_api.hip.h"
 #include "stereo_depth_api.hip.h"
 #include "rgbd.hip.h"
 #include "tracker.hip.h"

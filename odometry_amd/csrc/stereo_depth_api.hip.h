@@ -16,6 +16,7 @@ struct odo_stereo_depth {
   uint16_t* d_q;           // rows * cols, zero until the first run
   uint16_t* d_depth;       // the internal depth frame, zero until the first run that uses it
   uint32_t* d_partials;    // [blocks][kSdStatWords], zero until the first run
+  odo_speckle* speckle;    // odo_stereo_depth_enable_speckle: the filter every run enqueues behind the left match, or NULL
 };
 
 static SdArgs sd_args(const odo_stereo_depth* s, const float* left, const float* right, uint16_t* out) {
@@ -99,7 +100,29 @@ extern "C" int odo_stereo_depth_run_dev(odo_stereo_depth* s, const float* left_d
   const SdArgs a = sd_args(s, left_dev, right_dev, out_depth_dev);
   for (int stage = 0; stage < 3; stage++) launch_stereo_depth_stage(a, stage, s->ctx->stream);
   HIP_OK(hipGetLastError());
+  if (s->speckle) return sp_enqueue(s->speckle, sp_args(s->speckle, a.q, a.q, a.depth));
   return 0;
+}
+
+// The speckle filter behind every later run: the key is the q frame, the targets are the q frame and the run's depth output.
+// min_size == 0 takes it off again. The bounds are odo_speckle_create's.
+extern "C" int odo_stereo_depth_enable_speckle(odo_stereo_depth* s, int max_diff, int min_size) {
+  if (!s) return fail("odo_stereo_depth_enable_speckle: NULL arg");
+  odo_speckle* f = nullptr;
+  if (min_size != 0) {
+    odo_speckle_params p;
+    p.rows = s->p.rows; p.cols = s->p.cols; p.max_diff = max_diff; p.min_size = min_size;
+    if (odo_speckle_create(s->ctx, &p, &f)) return -1;
+  }
+  if (s->speckle) (void)odo_speckle_destroy(s->speckle);   // (waits for the runs that use it)
+  s->speckle = f;
+  return 0;
+}
+
+extern "C" int odo_stereo_depth_speckle_stats(odo_stereo_depth* s, long out[8]) {
+  if (!s || !out) return fail("odo_stereo_depth_speckle_stats: NULL arg");
+  if (!s->speckle) return fail("odo_stereo_depth_speckle_stats: no speckle filter is enabled (odo_stereo_depth_enable_speckle)");
+  return odo_speckle_stats(s->speckle, out);
 }
 
 extern "C" int odo_stereo_depth_disparity_dev(odo_stereo_depth* s, const uint16_t** q_dev) {
@@ -147,6 +170,7 @@ extern "C" int odo_stereo_depth_time_dev(odo_stereo_depth* s, const float* left_
   float t[3] = {0.0f, 0.0f, 0.0f};
   if (time_stages(who, st, reps, 3, t, warm, [&](int q) { launch_stereo_depth_stage(a, q, st); return true; })) return -1;
   for (int q = 0; q < 3; q++) us[q] = t[q];
+  if (s->speckle) return sp_enqueue(s->speckle, sp_args(s->speckle, a.q, a.q, a.depth));
   return 0;
 }
 
@@ -154,6 +178,7 @@ extern "C" int odo_stereo_depth_destroy(odo_stereo_depth* s) {
   if (!s) return 0;
   (void)hipSetDevice(s->device);
   (void)hipStreamSynchronize(s->ctx->stream);   // a run in flight reads and writes every block below
+  if (s->speckle) (void)odo_speckle_destroy(s->speckle);
   sd_free(s);
   delete s;
   return 0;
