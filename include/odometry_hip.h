@@ -1248,6 +1248,42 @@ int odo_stereo_depth_enable_speckle(odo_stereo_depth* s, int max_diff, int min_s
 /* odo_speckle_stats of the matcher's filter; -1 while none is enabled. */
 int odo_stereo_depth_speckle_stats(odo_stereo_depth* s, long out[8]);
 
+/* ---- Semi-global path aggregation for the dense stereo matcher: an opt-in mode, exact to the last bit ---------------------------
+ * Everything of the matcher's rule above stays: census, h, C for the A the matcher was created with, interior, admissibility. In
+ * this mode the selection reads an aggregate S in place of C. Integers P1, P2 and paths with
+ *   1 <= P1 <= P2;  paths is 4 or 8;  paths (62 (2A + 1)^2 + P2) <= 65534, so that an aggregate fits uint16 and 0xFFFF can mean
+ *   "inadmissible";  rows cols D <= 2^30 with D = dmax - dmin + 1.
+ *   Active     an interior pixel with at least one admissible candidate: A + 3 <= y < rows - A - 3, A + 4 + dmin <= x < cols - A - 4.
+ *              The active pixels form a rectangle; the admissible set of one is dmin .. min(dmax, x - A - 4): contiguous from dmin.
+ *   Directions r = (dx, dy): (1, 0), (-1, 0), (0, 1), (0, -1) for 4 paths; these and (1, 1), (-1, -1), (1, -1), (-1, 1) for 8.
+ *   Path cost  for an admissible (p, d) let q = p - r. If q is not active, L_r(p, d) = C(p, d): the path starts here. Otherwise with
+ *              M = min over q's admissible k of L_r(q, k):  L_r(p, d) = C(p, d) + min(a0, a1, a2, P2),  a0 = L_r(q, d) - M,
+ *              a1 = L_r(q, d - 1) - M + P1,  a2 = L_r(q, d + 1) - M + P1,  a term left out if its candidate is not admissible at q.
+ *              Hence 0 <= L_r <= C + P2.
+ *   Aggregate  S(p, d) = the sum of L_r(p, d) over the directions: integer sums, independent of the order of the paths.
+ *   Selection  exactly the rule above with S in place of C: the smallest d of minimal S wins; c2 over |d - dl| > 1; left-right with
+ *              SR(x', y, d) = S(x' + d, y, d) and dr the smallest d of minimal cost (255: none); sub-pixel on the S triple, one
+ *              division, range reject; the same eight counters.
+ * It is not a win everywhere: on an untextured patch the census bits are noise, and no path has a signal to propagate (DESIGN.md
+ * section 9.18 has the figures). The default stays the box matcher, bit for bit.
+ *
+ * odo_stereo_depth_enable_sgm validates before it touches the device: -1 with the bound named in the message, and the matcher as
+ * it was, on a bad bound or a failed allocation. Device memory: two uint16 volumes [rows][cols][D], 4 rows cols D bytes, allocated
+ * here and freed by paths == 0 (which takes the mode off: a later run gives the box matcher's bytes; waits for ctx's stream) or by
+ * destroy. Every later odo_stereo_depth_run_dev enqueues census, cost, one launch per path, right selection and left selection on
+ * ctx's stream and returns; an enabled speckle filter follows as before. Its refusals and its ordering are unchanged. Calling it
+ * again with other penalties or paths keeps the volumes. */
+int odo_stereo_depth_enable_sgm(odo_stereo_depth* s, int p1, int p2, int paths);
+/* odo_stereo_depth_time_dev for the semi-global mode: us[0 .. 4] = the mean time in microseconds of the census launch, the cost
+ * launch, ALL path launches as one unit (the group is repeated as a whole, because its first launch stores), the right selection
+ * and the left selection. reps 1 .. 10000. Waits. The outputs and the statistics are those of one run afterwards. -1 while the mode
+ * is off; while it is on, odo_stereo_depth_time_dev returns -1 and names this call. */
+int odo_stereo_depth_sgm_time_dev(odo_stereo_depth* s, const float* left_dev, const float* right_dev, uint16_t* out_depth_dev, int reps,
+                                  float us[5]);
+/* TEST ONLY. Waits for ctx's stream, then copies the last run's S to host_out: rows cols D uint16 in the order [y][x][d - dmin],
+ * 0xFFFF where the candidate is not admissible (everywhere before the first run). -1 while the mode is off. */
+int odo_debug_sgm_volume(odo_stereo_depth* s, uint16_t* host_out);
+
 /* ---- S sequences in lock step on one GPU (the data-parallel axis of SURVEY section 8e inside one device) -----------------
  * One odo_tracker tracks one sequence as a serial chain of ~70 short launches per frame, which leaves most of the chip
  * idle. odo_tracker_batch runs the same frame loop (ref: run_odometry_kitti_offline.cpp:198-271) for n_sequences independent

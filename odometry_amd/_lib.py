@@ -348,6 +348,9 @@ SIGNATURES = {
     "odo_speckle_destroy": (C.c_int, [_vp]),
     "odo_stereo_depth_enable_speckle": (C.c_int, [_vp, C.c_int, C.c_int]),
     "odo_stereo_depth_speckle_stats": (C.c_int, [_vp, C.POINTER(C.c_long)]),
+    "odo_stereo_depth_enable_sgm": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
+    "odo_stereo_depth_sgm_time_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _fp]),
+    "odo_debug_sgm_volume": (C.c_int, [_vp, _vp]),
 }
 
 _lib = None

@@ -1818,6 +1818,36 @@ class StereoDepth:
         L.check(self.lib.odo_stereo_depth_speckle_stats(self.h, o), "odo_stereo_depth_speckle_stats")
         return dict(zip(SpeckleFilter.STATS, list(o)[:len(SpeckleFilter.STATS)]))
 
+    SGM_GROUPS = ("census", "cost", "paths", "select_right", "select_left")
+
+    def enable_sgm(self, p1=None, p2=None, paths=8):
+        """Every later run aggregates the box-summed cost along 4 or 8 paths (semi-global matching, include/odometry_hip.h) before
+        the selection. p1 / p2: the penalties of a disparity step of one / of more; None: 4 / 24 times the window's area (100 / 600
+        at agg_radius 2). Allocates two uint16 volumes rows x cols x (max_disp - min_disp + 1)."""
+        n = (2 * self.params.agg_radius + 1) ** 2
+        p1 = 4 * n if p1 is None else int(p1)
+        p2 = 24 * n if p2 is None else int(p2)
+        if int(paths) == 0:
+            raise ValueError("paths must be 4 or 8 (disable_sgm takes the mode off)")
+        L.check(self.lib.odo_stereo_depth_enable_sgm(self.h, p1, p2, int(paths)), "odo_stereo_depth_enable_sgm")
+
+    def disable_sgm(self):
+        """Back to the box matcher; frees the volumes (waits for the runs that use them)."""
+        L.check(self.lib.odo_stereo_depth_enable_sgm(self.h, 0, 0, 0), "odo_stereo_depth_enable_sgm")
+
+    def sgm_time(self, left_dev, right_dev, out_dev=None, reps=20):
+        """time() for the semi-global mode (tools/stereo_sgm_cost.py): dict(census, cost, paths, select_right, select_left), the
+        path launches of one run as one figure."""
+        us = (C.c_float * 5)()
+        L.check(self.lib.odo_stereo_depth_sgm_time_dev(self.h, left_dev, right_dev, out_dev, reps, us), "odo_stereo_depth_sgm_time_dev")
+        return dict(zip(self.SGM_GROUPS, list(us)))
+
+    def sgm_volume(self):
+        """The last run's aggregate S on the host (a test's read-out; waits): rows x cols x D uint16, 65535 = not admissible."""
+        out = np.empty((self.rows, self.cols, self.params.dmax - self.params.dmin + 1), np.uint16)
+        L.check(self.lib.odo_debug_sgm_volume(self.h, out.ctypes.data_as(C.c_void_p)), "odo_debug_sgm_volume")
+        return out
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.odo_stereo_depth_destroy(self.h)

@@ -52,7 +52,8 @@ SCHED_DENSE = os.environ.get("ODO_SCHED_DENSE", "")   # dense_kernels.hip: "" = 
 UNITS = [(SRC, ""), (SRC_DENSE, SCHED_DENSE), (SRC_CHAIN, SCHED_CHAIN)] + [(os.path.join(_CSRC, n), "") for n in (
     "map_kernels.hip", "rgbd_kernels.hip", "rgbd_frontend_kernels.hip", "volume_kernels.hip", "volume_mesh_kernels.hip",
     "volume_colour_kernels.hip", "volume_raycast_kernels.hip", "volume_icp_kernels.hip", "volume_shift_kernels.hip",
-    "depth_filter_kernels.hip", "volume_reentry_kernels.hip", "stereo_depth_kernels.hip", "speckle_kernels.hip")]
+    "depth_filter_kernels.hip", "volume_reentry_kernels.hip", "stereo_depth_kernels.hip", "speckle_kernels.hip",
+    "stereo_sgm_kernels.hip")]
 
 
 def _flags_for(src, flags):

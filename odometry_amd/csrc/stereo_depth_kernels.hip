@@ -30,119 +30,37 @@ __global__ void __launch_bounds__(kSdBlock) stereo_census_kernel(SdArgs a) {
   if (x >= kSdCensusRx && x < cols - kSdCensusRx && y >= kSdCensusRy && y < rows - kSdCensusRy) out[(size_t)y * cols + x] = w;
 }
 
-// A census word of a plane, 0 outside the census domain (where the plane was never written).
-__device__ __forceinline__ uint64_t sd_word(const uint64_t* plane, int rows, int cols, int y, int x) {
-  uint64_t v = 0;
-  if (x >= kSdCensusRx && x < cols - kSdCensusRx && y >= kSdCensusRy && y < rows - kSdCensusRy) v = plane[(size_t)y * cols + x];
-  return v;
-}
-
-// ---- match. Right = false: the tile is of left pixels, the other image is the right one, candidate d of the pixel at tile column tx
-// pairs own column tx + i with the other image's column x + i - d. Right = true: the tile is of right pixels, candidate d pairs own
-// column tx + i with the LEFT image's column x + i + d (CR(x, y, d) = C(x + d, y, d)). In the other block, column 0 is the image
-// column gx0 - A - dmax (Right: gx0 - A + dmin), so that the tap sits at tx + i + s with s = dmax - d (Right: d - dmin), 0 <= s <=
-// dmax - dmin: inside the block for every admissible candidate, whatever the frame's size.
+// ---- match: the staging, the taps and the left pixel's outputs are stereo_depth.hip.h's (sd_stage_tile, sd_tap_cost,
+// sd_left_outputs). Right = false: the tile is of left pixels; Right = true: of right pixels, and the kernel ends with dr.
 // Vec (Right = false only): cols % 4 == 0 and both output frames 8-byte aligned. Then four lanes' outputs leave as one 8-byte store.
 template <int A, bool Right, bool Vec>
 __global__ void __launch_bounds__(kSdBlock) stereo_match_kernel(SdArgs a) {
-  constexpr int kN = 2 * A + 1;
-  constexpr int kRows = kSdTileH + 2 * A;
-  constexpr int kOwnStride = kSdTileW + 2 * A;
-  constexpr int kOtherStride = kSdTileW + 2 * A + kSdMaxSpan;
-  __shared__ __attribute__((aligned(16))) uint64_t s_own[kRows * kOwnStride];
-  __shared__ __attribute__((aligned(16))) uint64_t s_other[kRows * kOtherStride];
+  using T = SdTile<A>;
+  __shared__ __attribute__((aligned(16))) uint64_t s_own[T::kRows * T::kOwnStride];
+  __shared__ __attribute__((aligned(16))) uint64_t s_other[T::kRows * T::kOtherStride];
   __shared__ uint32_t s_red[kSdBlock / 64][6];
 
   const int rows = a.rows, cols = a.cols, dmin = a.r.dmin, dmax = a.r.dmax;
   const int tid = (int)threadIdx.x;
-  const int gx0 = (int)blockIdx.x * kSdTileW, gy0 = (int)blockIdx.y * kSdTileH;
-  const uint64_t* own = Right ? a.cr : a.cl;
-  const uint64_t* other = Right ? a.cl : a.cr;
-
-  // ---- stage
-  for (int i = tid; i < kRows * kOwnStride; i += kSdBlock) {
-    const int r = i / kOwnStride, c = i - r * kOwnStride;
-    s_own[i] = sd_word(own, rows, cols, gy0 - A + r, gx0 - A + c);
-  }
-  const int span = kSdTileW + 2 * A + dmax - dmin;            // columns of the other block in use
-  const int ox0 = Right ? gx0 - A + dmin : gx0 - A - dmax;    // image column of its column 0
-  for (int i = tid; i < kRows * span; i += kSdBlock) {
-    const int r = i / span, c = i - r * span;
-    s_other[r * kOtherStride + c] = sd_word(other, rows, cols, gy0 - A + r, ox0 + c);
-  }
-  __syncthreads();
+  sd_stage_tile<A, Right>(a, s_own, s_other);
 
   // ---- the walk
   const int tx = tid & (kSdTileW - 1), ty = tid / kSdTileW;
-  const int x = gx0 + tx, y = gy0 + ty;
-  uint64_t win[kN][kN];
-#pragma unroll
-  for (int j = 0; j < kN; j++)
-#pragma unroll
-    for (int i = 0; i < kN; i++) win[j][i] = s_own[(ty + j) * kOwnStride + tx + i];
-  int last = dmin - 1;                                         // the largest admissible candidate; none: no trip
-  if (sd_interior_row(y, rows, A)) {
-    if (Right) { if (x >= A + kSdCensusRx) last = sd_right_last(x, cols, dmax, A); }
-    else if (sd_interior_col(x, cols, A)) last = sd_left_last(x, dmax, A);
-  }
+  const int x = (int)blockIdx.x * kSdTileW + tx, y = (int)blockIdx.y * kSdTileH + ty;
+  uint64_t win[T::kN][T::kN];
+  sd_window<A>(s_own, tx, ty, win);
+  const int last = sd_last<A, Right>(a, x, y);                 // the largest admissible candidate; none: no trip
   SdWalk w;
   sd_walk_init(&w);
-  const uint64_t* base = s_other + ty * kOtherStride + tx;
+  const uint64_t* base = s_other + ty * T::kOtherStride + tx;
 #pragma unroll 1
-  for (int d = dmin; d <= last; d++) {
-    const uint64_t* p = base + (Right ? d - dmin : dmax - d);
-    int c = 0;
-#pragma unroll
-    for (int j = 0; j < kN; j++)
-#pragma unroll
-      for (int i = 0; i < kN; i++) c += sd_hamming(win[j][i], p[j * kOtherStride + i]);
-    sd_walk_step(&w, d, c);
-  }
+  for (int d = dmin; d <= last; d++) sd_walk_step(&w, d, sd_tap_cost<A, Right>(win, base, d, dmin, dmax));
 
   if (Right) {
     if (x < cols && y < rows) a.dr[(size_t)y * cols + x] = w.c0 == kSdNone ? (uint8_t)kSdNoRight : (uint8_t)w.dl;
     return;
   }
-
-  // ---- the left pixel's rejections, outputs and the workgroup's counters
-  SdRule rule;
-  rule.dmin = dmin; rule.dmax = dmax; rule.A = A; rule.uniq = a.r.uniq; rule.lr_max = a.r.lr_max; rule.max_raw = a.r.max_raw; rule.k = a.r.k;
-  uint16_t depth, q;
-  const int outcome = sd_finish(w, rule, a.dr + (size_t)(y < rows ? y : 0) * cols, x, &depth, &q);
-  if (Vec) {
-    uint32_t d01 = (uint32_t)depth, q01 = (uint32_t)q;
-    d01 |= (uint32_t)__shfl_down(d01, 1) << 16;
-    q01 |= (uint32_t)__shfl_down(q01, 1) << 16;
-    const uint32_t d23 = (uint32_t)__shfl_down(d01, 2), q23 = (uint32_t)__shfl_down(q01, 2);
-    if ((tx & 3) == 0 && x < cols && y < rows) {
-      *reinterpret_cast<uint2*>(a.depth + (size_t)y * cols + x) = make_uint2(d01, d23);
-      *reinterpret_cast<uint2*>(a.q + (size_t)y * cols + x) = make_uint2(q01, q23);
-    }
-  } else if (x < cols && y < rows) {
-    a.depth[(size_t)y * cols + x] = depth;
-    a.q[(size_t)y * cols + x] = q;
-  }
-  uint32_t n[6] = {(uint32_t)(outcome != kSdNotInterior), (uint32_t)(outcome == kSdMatched), (uint32_t)(outcome == kSdRejUnique),
-                   (uint32_t)(outcome == kSdRejLr), (uint32_t)(outcome == kSdRejRange), (uint32_t)q};
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-    for (int k = 0; k < 6; k++) n[k] += __shfl_down(n[k], off);
-  if (tx == 0)
-#pragma unroll
-    for (int k = 0; k < 6; k++) s_red[ty][k] = n[k];
-  __syncthreads();
-  if (tid == 0) {
-    uint32_t r[6] = {0u, 0u, 0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int v = 0; v < kSdBlock / 64; v++)
-#pragma unroll
-      for (int k = 0; k < 6; k++) r[k] += s_red[v][k];
-    const size_t b = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-    uint4* row = reinterpret_cast<uint4*>(a.partials + kSdStatWords * b);
-    row[0] = make_uint4(r[0], r[1], r[2], r[3]);
-    row[1] = make_uint4(r[4], r[5], 0u, 0u);   // (a workgroup's sum of q fits its low word)
-  }
+  sd_left_outputs<Vec>(a, w, A, x, y, s_red);
 }
 
 template <int A>
