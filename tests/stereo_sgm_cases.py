@@ -360,7 +360,8 @@ def rows():
         and T["n_cand"].max() < 60)
     add("left strip, 4 paths, A = 0", sdc.shifted_pair(3, (20, 60), 5), P(A=0, dmax=30), sgm(A=0, paths=4), newest)
     # the lane and slot seams
-    for D, size in ((3, (9, 20)), (64, (12, 90)), (65, (12, 90)), (128, (10, 150)), (129, (10, 150)), (255, (10, 280))):
+    for D, size in ((3, (9, 20)), (64, (12, 90)), (65, (12, 90)), (128, (10, 150)), (129, (10, 150)), (192, (10, 220)), (193, (10, 220)),
+                    (255, (10, 280))):
         add(f"D = {D}", sdc.shifted_pair(4, size, min(D - 1, 70)), P(A=0, dmin=1, dmax=D), sgm(A=0),
             lambda s, T, sg, D=D, size=size: T["n_cand"].max() == min(D, size[1] - 9) and s["interior"] > 0)
     # diagonal lines enter through both sides
@@ -368,6 +369,16 @@ def rows():
         add(f"frame {size[0]} x {size[1]}", sdc.shifted_pair(5, size, 3), P(A=1, dmax=10), sgm(A=1),
             lambda s, T, sg, size=size: (T["rect"][3] - T["rect"][2] > T["rect"][1] - T["rect"][0]) == (size[0] > size[1])
             and not np.array_equal(T["L"][4], T["L"][6]))
+    # line lengths round the path kernel's load-ahead ring (kSgmAhead steps; a line's loop runs in rounds of that many): one short of
+    # it, the ring itself, one more, and two rounds and one. The vertical and diagonal launches meet them as the active rectangle's
+    # height, the horizontal ones (instantiations of their own) as its width. At A = 1 the rectangle is rows - 8 high and, with
+    # dmin = 1, cols - 11 wide.
+    AH = kc["kSgmAhead"]
+    for n in (AH - 1, AH, AH + 1, 2 * AH + 1):
+        add(f"active rectangle {n} high", sdc.shifted_pair(12, (8 + n, 60), 3), P(A=1, dmax=10), sgm(A=1),
+            lambda s, T, sg, n=n: T["rect"][3] - T["rect"][2] == n and T["rect"][1] - T["rect"][0] >= 40 and s["matched"] > 0)
+        add(f"active rectangle {n} wide", sdc.shifted_pair(13, (22, 11 + n), 1), P(A=1, dmax=10), sgm(A=1),
+            lambda s, T, sg, n=n: T["rect"][1] - T["rect"][0] == n and T["rect"][3] - T["rect"][2] >= 12 and s["matched"] > 0)
     # either side of the tile (64 x 4), of the lines per workgroup (4) and every cols % 4
     for r_, c_ in ((3 * TH, TW - 1), (3 * TH, TW), (3 * TH, TW + 1), (3 * TH - 1, TW), (3 * TH + 1, TW), (3 * TH + 1, 2 * TW + 1),
                    (3 * TH + 1, TW + 2), (3 * TH + 2, TW + 3)):

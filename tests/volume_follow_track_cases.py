@@ -105,15 +105,16 @@ def shift_step(p, st, d, capacities):
 
 
 def drive_model(name, reentry=False, spill=False, step=None, sums="kernel", frames=None):
-    """The closed loop on the model. Frame 0: the follow step for the first true pose, then its integration. Frame k: the ray-cast of
-    window(p, off) from the last good pose, the alignment from that pose, and on status 0 the follow step for the returned pose, the
+    """The closed loop on the model, for a drive by name or a drive dict with drive()'s keys (depth, poses, p, follow, ic, checkpoints:
+    tests/stereo_drive_cases.py brings the frames of a stereo matcher). Frame 0: the follow step for the first true pose, then its
+    integration. Frame k: the ray-cast of window(p, off) from the last good pose, the alignment from that pose, and on status 0 the follow step for the returned pose, the
     shift it asks for, and the integration into the window as it then is; on any other status nothing changes and the good pose stays.
     sums: "kernel" (the device's bits) or "pairwise" (fp64, numpy's order). frames: stop behind that many.
 
     Returns dict(frames, q, w, off, points, reentry, shifts). frames[k]: status, iterations, pairs, cost, eig_min, eig_max, C, pose (what
     track returns: NaNs when refused), good (the pose the next frame starts from), d, off, origin, fused (stats()["frames"]), hits (the
     ray-cast's pixels with a surface), sum_ratio (see kernel_sums) and, at the drive's checkpoints, grid = (q, w)."""
-    c = drive(name)
+    c = drive(name) if isinstance(name, str) else name
     p, ic, fo = c["p"], c["ic"], c["follow"]
     step = step or default_step()
     caps = dict(points=SPILL_CAPACITY, reentry=REENTRY_CAPACITY)
