@@ -1284,6 +1284,85 @@ int odo_stereo_depth_sgm_time_dev(odo_stereo_depth* s, const float* left_dev, co
  * 0xFFFF where the candidate is not admissible (everywhere before the first run). -1 while the mode is off. */
 int odo_debug_sgm_volume(odo_stereo_depth* s, uint16_t* host_out);
 
+/* ---- Mesh welder: coincident vertices merged, degenerate and duplicate triangles removed, exact to the last bit -----------------
+ * Input: n_v vertices (xyz0 float4, nrmw float4, optionally rgba uint8[4]) and n_t triangles (int32[3]) on the device, as
+ * odo_volume_mesh and odo_volume_spill_mesh give them. A rule: eps > 0 (fp32), origin[3] (fp32, finite), grids in {1, 8},
+ * drop_unreferenced in {0, 1}.
+ * One pass with grid k (k = 0 .. 7, bit a of k belongs to axis a):
+ *   Cell            inv = 1.0f / eps, correctly rounded, once. c_a = floorf((x_a - o_a) * inv + (bit_a ? 0.5f : 0.0f)): three fp32
+ *                   operations, each rounded, no contraction. A vertex is keyless if a coordinate or a c_a is not finite or
+ *                   |c_a| >= 2^20; a keyless vertex is never merged and is its own representative. Otherwise its key is the three
+ *                   cells + 2^20 packed as 21-bit fields into 63 bits.
+ *   Representative  rep(i) = the smallest index with the same key.
+ *   Triangles       in input order. An index outside [0, n_v): dropped, counted bad_index; no such index is ever dereferenced.
+ *                   Otherwise the indices become their representatives; two equal: dropped, counted degenerate. Otherwise the triple
+ *                   is rotated so that its smallest index comes first, winding kept; it is dropped and counted duplicate if an
+ *                   earlier surviving triangle has the same rotated triple. The opposite winding is a different triangle.
+ *   Vertices kept   with drop_unreferenced the representatives a surviving triangle names, without it all representatives; in
+ *                   ascending original index, each with its own xyz0, nrmw and rgba bit for bit: nothing is averaged. The
+ *                   surviving triangles keep their input order and are written as their rotated triples in the kept vertices' ranks.
+ * grids = 1 is pass 0; grids = 8 is passes 0 .. 7 chained, each on the output of the one before. Two vertices closer than eps / 2
+ * on every axis share a cell of at least one of the eight grids.
+ * Counters (odo_mesh_weld_stats, in this order): vertices_in and triangles_in of the first pass, vertices_out and triangles_out of
+ * the last; merged (vertices that took another representative), unreferenced (representatives dropped because no surviving triangle
+ * names them; 0 without drop_unreferenced), degenerate, duplicate and bad_index summed over the passes, so that vertices_out =
+ * vertices_in - merged - unreferenced and triangles_out = triangles_in - degenerate - duplicate - bad_index; keyless summed over the
+ * passes (a vertex keyless in all eight grids counts eight times); guard (0; see below); passes.
+ * Nothing depends on timing: keys are integers, the vertex table holds a 64-bit key word claimed with atomicCAS and a smallest-index
+ * word lowered with atomicMin, the triangle table holds triangle indices claimed with atomicCAS and lowered with atomicMin, and the
+ * compaction is count, scan, scatter. Both tables have 2^ceil(log2(2 capacity)) slots and are probed linearly from a splitmix64
+ * hash; every probe loop carries a hard trip bound, the table's size, and a loop that runs into it sets a bit of `guard` and leaves
+ * (DESIGN.md section 9.19). No loop waits for another thread. */
+typedef struct odo_mesh_weld odo_mesh_weld;
+typedef struct {
+  int vertex_capacity, triangle_capacity; /* 1 .. 2^28 each */
+  int colour;                             /* 0 or 1: room for rgba */
+} odo_mesh_weld_params;
+typedef struct {
+  float eps;
+  float origin[3];
+  int grids;
+  int drop_unreferenced;
+} odo_mesh_weld_rule;
+/* Validates before it touches the device: -1 with the bound named in the message and *out untouched on any violation. Device memory,
+ * allocated once, in one block: per vertex of capacity 73 B (81 B with colour: two sets of output buffers and the scratch), per
+ * triangle 40 B, per slot of the vertex table 12 B and of the triangle table 4 B. ctx must outlive the welder. One host thread at a
+ * time. */
+int odo_mesh_weld_create(odo_ctx* ctx, const odo_mesh_weld_params* p, odo_mesh_weld** out);
+/* Enqueues the passes on ctx's stream and returns at once, no host wait; a pass reads the counts of the one before on the device.
+ * The inputs are never written. rgba_dev may be NULL (no colours this run); xyz0_dev / nrmw_dev may be NULL iff n_vertices == 0 and
+ * tri_dev iff n_triangles == 0, and either count may be 0. -1 and nothing enqueued for: NULL where not allowed; eps not finite or
+ * <= 0; a non-finite origin; grids not 1 or 8; drop_unreferenced not 0 or 1; a negative count or one beyond 2^28; a misaligned
+ * pointer (16 bytes for xyz0 and nrmw, 4 for rgba and tri) — all decided before the welder is read — and for counts beyond the
+ * capacities, rgba_dev on a welder without colour, and an input that overlaps the welder's buffers. Ordering is
+ * odo_speckle_run_dev's: what is enqueued on ctx's stream afterwards is ordered behind it; the inputs must stay as they are until
+ * then. */
+int odo_mesh_weld_run_dev(odo_mesh_weld* w, const odo_mesh_weld_rule* rule, long n_vertices, long n_triangles, const float* xyz0_dev,
+                          const float* nrmw_dev, const uint8_t* rgba_dev, const int32_t* tri_dev);
+/* The last run's result in the welder's own buffers (valid until the next run or destroy; *rgba_dev NULL when the run carried no
+ * colours; any pointer argument may be NULL) and its two counts, for which it waits for ctx's stream. 0, 0 before the first run. */
+int odo_mesh_weld_result_dev(odo_mesh_weld* w, const float** xyz0_dev, const float** nrmw_dev, const uint8_t** rgba_dev,
+                             const int32_t** tri_dev, long* n_vertices, long* n_triangles);
+/* Copies the last run's result into host buffers of the given capacities and waits. Capacities 0, 0: the counts alone. As
+ * odo_volume_spill_mesh does, it refuses capacities below the counts (-1, the counts still returned) rather than cutting. rgba may
+ * be NULL. */
+int odo_mesh_weld_download(odo_mesh_weld* w, long vertex_capacity, long triangle_capacity, float* xyz0, float* nrmw, uint8_t* rgba,
+                           int32_t* tri, long* n_vertices, long* n_triangles);
+/* The host-array convenience: upload (a staging block of this call's own), odo_mesh_weld_run_dev, odo_mesh_weld_download. */
+int odo_mesh_weld_run(odo_mesh_weld* w, const odo_mesh_weld_rule* rule, long n_vertices, long n_triangles, const float* xyz0,
+                      const float* nrmw, const uint8_t* rgba, const int32_t* tri, long vertex_capacity, long triangle_capacity,
+                      float* out_xyz0, float* out_nrmw, uint8_t* out_rgba, int32_t* out_tri, long* out_vertices, long* out_triangles);
+/* Of the last run, exact, in the order above. Waits for ctx's stream. Zeros before the first run. */
+int odo_mesh_weld_stats(odo_mesh_weld* w, long out[12]);
+/* Diagnostic: the passes in order, within a pass each of the six groups of launches `reps` (1 .. 10000) times between two events on
+ * ctx's stream; us[0 .. 5] = the mean time in microseconds, summed over the passes, of keys + vertex table / representatives /
+ * triangle remap + table / survivors / scans / scatters (table clears included), us[6] = their sum. Waits. Then one run: the
+ * outputs and the statistics are exactly one run's afterwards. */
+int odo_mesh_weld_time_dev(odo_mesh_weld* w, const odo_mesh_weld_rule* rule, long n_vertices, long n_triangles, const float* xyz0_dev,
+                           const float* nrmw_dev, const uint8_t* rgba_dev, const int32_t* tri_dev, int reps, float us[7]);
+/* Safe with a run in flight: waits for ctx's stream first. */
+int odo_mesh_weld_destroy(odo_mesh_weld* w);
+
 /* ---- S sequences in lock step on one GPU (the data-parallel axis of SURVEY section 8e inside one device) -----------------
  * One odo_tracker tracks one sequence as a serial chain of ~70 short launches per frame, which leaves most of the chip
  * idle. odo_tracker_batch runs the same frame loop (ref: run_odometry_kitti_offline.cpp:198-271) for n_sequences independent

@@ -58,6 +58,14 @@ class SpeckleParams(C.Structure):
     _fields_ = [("rows", C.c_int), ("cols", C.c_int), ("max_diff", C.c_int), ("min_size", C.c_int)]
 
 
+class MeshWeldParams(C.Structure):
+    _fields_ = [("vertex_capacity", C.c_int), ("triangle_capacity", C.c_int), ("colour", C.c_int)]
+
+
+class MeshWeldRule(C.Structure):
+    _fields_ = [("eps", C.c_float), ("origin", C.c_float * 3), ("grids", C.c_int), ("drop_unreferenced", C.c_int)]
+
+
 class VolumeParams(C.Structure):
     _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("voxel_size", C.c_float), ("origin", C.c_float * 3),
                 ("mu", C.c_float), ("max_depth", C.c_float), ("max_weight", C.c_int), ("rows", C.c_int), ("cols", C.c_int),
@@ -351,6 +359,16 @@ SIGNATURES = {
     "odo_stereo_depth_enable_sgm": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
     "odo_stereo_depth_sgm_time_dev": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _fp]),
     "odo_debug_sgm_volume": (C.c_int, [_vp, _vp]),
+    "odo_mesh_weld_create": (C.c_int, [_vp, C.POINTER(MeshWeldParams), C.POINTER(_vp)]),
+    "odo_mesh_weld_run_dev": (C.c_int, [_vp, C.POINTER(MeshWeldRule), C.c_long, C.c_long, _vp, _vp, _vp, _vp]),
+    "odo_mesh_weld_result_dev": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_long),
+                                           C.POINTER(C.c_long)]),
+    "odo_mesh_weld_download": (C.c_int, [_vp, C.c_long, C.c_long, _vp, _vp, _vp, _vp, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "odo_mesh_weld_run": (C.c_int, [_vp, C.POINTER(MeshWeldRule), C.c_long, C.c_long, _vp, _vp, _vp, _vp, C.c_long, C.c_long, _vp, _vp,
+                                    _vp, _vp, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "odo_mesh_weld_stats": (C.c_int, [_vp, C.POINTER(C.c_long)]),
+    "odo_mesh_weld_time_dev": (C.c_int, [_vp, C.POINTER(MeshWeldRule), C.c_long, C.c_long, _vp, _vp, _vp, _vp, C.c_int, _fp]),
+    "odo_mesh_weld_destroy": (C.c_int, [_vp]),
 }
 
 _lib = None

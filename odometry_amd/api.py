@@ -916,6 +916,7 @@ class TsdfVolume:
         self._spill_capacity = 0
         self._spill_colour = False
         self._spill_mesh_colour = False
+        self._has_spill_mesh = False
         p = L.VolumeParams()
         p.nx, p.ny, p.nz = dims
         p.voxel_size = voxel_size
@@ -1427,6 +1428,7 @@ class TsdfVolume:
         not need enable_spill, and a volume may have both stores."""
         L.check(self.lib.odo_volume_enable_spill_mesh(self.h, int(vertex_capacity), int(triangle_capacity)), "odo_volume_enable_spill_mesh")
         self._spill_mesh_colour = self.has_colour   # (a store made before enable_colour has no colours)
+        self._has_spill_mesh = True
 
     def spilled_mesh(self, clear=False, colour=False, with_dropped=False):
         """The mesh store as mesh() returns a mesh: (n, 4) float32 x, y, z, e; (n, 4) float32 nx, ny, nz, weight; (m, 3) int32 indices
@@ -1508,6 +1510,36 @@ class TsdfVolume:
             write_ply_mesh(path, parts[0], parts[1], parts[2], rgb=parts[3])
         else:
             write_ply_mesh(path, parts[0], parts[1], parts[2])
+
+    def welded_mesh(self, eps=None, grids=8, spill=True, colour=False):
+        """One mesh of the whole surface, welded (MeshWeld): the mesh store's mesh (where the volume has one and
+        spill is set) in front of the window's, whose indices are offset by the store's vertices, as save_mesh_ply(spill=True) writes
+        them; then vertices that share a cell of edge eps around the volume's first origin become one, and degenerate and duplicate
+        triangles leave. eps=None: voxel_size / 64. dict(xyz0, nrmw, tri, rgba with colour, stats). Waits."""
+        spill = bool(spill) and self._has_spill_mesh
+        if spill and colour and not self._spill_mesh_colour:
+            raise ValueError("welded_mesh(colour=True): the mesh store was enabled before enable_colour and holds no colours, the "
+                             "mesh has them; call enable_colour before enable_spill_mesh")
+        parts = self.mesh(colour=True) if colour else self.mesh()
+        if spill:
+            store = self.spilled_mesh(colour=colour)
+            parts = tuple(np.concatenate([a, b + len(store[0])]) if i == 2 else np.concatenate([a, b])
+                          for i, (a, b) in enumerate(zip(store, parts)))
+        eps = np.float32(self.params.voxel_size) / np.float32(64.0) if eps is None else eps
+        w = MeshWeld(self._owner, max(len(parts[0]), 1), max(len(parts[2]), 1), colour=colour)
+        try:
+            return w.run(parts[0], parts[1], parts[2], rgba=parts[3] if colour else None, eps=eps,
+                         origin=tuple(self.params.origin), grids=grids, drop_unreferenced=True)
+        finally:
+            w.close()
+
+    def save_welded_mesh_ply(self, path, eps=None, grids=8, spill=True):
+        """welded_mesh() as a binary little-endian PLY, through write_ply_mesh: float x y z nx ny nz per vertex (and uchar red green
+        blue when the volume has colour), three int indices per face. Returns the weld's counters."""
+        colour = self.has_colour
+        m = self.welded_mesh(eps=eps, grids=grids, spill=spill, colour=colour)
+        write_ply_mesh(path, m["xyz0"], m["nrmw"], m["tri"], rgb=m["rgba"] if colour else None)
+        return m["stats"]
 
     def close(self):
         if getattr(self, "h", None):
@@ -1906,6 +1938,122 @@ class SpeckleFilter:
     def close(self):
         if getattr(self, "h", None):
             self.lib.odo_speckle_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MeshWeld:
+    """The mesh welder on the device (odo_mesh_weld_*): vertices that share a cell of edge eps become one (the smallest index stays,
+    with its own attributes), triangles that turn degenerate or repeat an earlier one leave, in exact integers behind three fp32
+    operations per coordinate (include/odometry_hip.h): every pass's launches go to the context's stream. ctx_or_tracker: a
+    Context, or a Tracker (its context)."""
+
+    STATS = ("vertices_in", "vertices_out", "merged", "keyless", "unreferenced", "triangles_in", "triangles_out", "degenerate",
+             "duplicate", "bad_index", "guard", "passes")
+    GROUPS = ("vertex_table", "representatives", "triangle_table", "survivors", "scans", "scatters", "run")
+
+    def __init__(self, ctx_or_tracker, vertex_capacity, triangle_capacity, colour=False):
+        self.lib = L.load()
+        self._owner = ctx_or_tracker   # keeps the stream's owner alive as long as the welder
+        self._ctx = ctx_or_tracker._ctx if isinstance(ctx_or_tracker, Tracker) else ctx_or_tracker.h
+        p = L.MeshWeldParams(int(vertex_capacity), int(triangle_capacity), int(bool(colour)))
+        self.params = p
+        self.h = None
+        h = C.c_void_p()
+        L.check(self.lib.odo_mesh_weld_create(self._ctx, C.byref(p), C.byref(h)), "odo_mesh_weld_create")
+        self.h = h
+
+    @staticmethod
+    def rule(eps, origin=(0.0, 0.0, 0.0), grids=8, drop_unreferenced=True):
+        if eps is None:
+            raise ValueError("MeshWeld: eps is required (the cell's edge, metres)")
+        r = L.MeshWeldRule()
+        r.eps = eps
+        for i in range(3):
+            r.origin[i] = origin[i]
+        r.grids, r.drop_unreferenced = int(grids), int(bool(drop_unreferenced))
+        return r
+
+    def run_dev(self, n_vertices, n_triangles, xyz0_dev, nrmw_dev, tri_dev, rgba_dev=None, eps=None, origin=(0.0, 0.0, 0.0), grids=8,
+                drop_unreferenced=True):
+        """Enqueues the weld of a mesh on the device and returns at once; the result stays in the welder's buffers (result_dev,
+        download)."""
+        L.check(self.lib.odo_mesh_weld_run_dev(self.h, C.byref(self.rule(eps, origin, grids, drop_unreferenced)), int(n_vertices),
+                                               int(n_triangles), xyz0_dev, nrmw_dev, rgba_dev, tri_dev), "odo_mesh_weld_run_dev")
+
+    def result_dev(self):
+        """(xyz0, nrmw, rgba or None, tri, n_vertices, n_triangles) of the last run: device pointers into the welder's buffers and
+        the two counts (waits for them)."""
+        p = [C.c_void_p() for _ in range(4)]
+        n, m = C.c_long(0), C.c_long(0)
+        L.check(self.lib.odo_mesh_weld_result_dev(self.h, *[C.byref(x) for x in p], C.byref(n), C.byref(m)), "odo_mesh_weld_result_dev")
+        return p[0], p[1], (p[2] if p[2].value else None), p[3], n.value, m.value
+
+    def download(self, colour=False):
+        """The last run's result on the host (waits): dict(xyz0 (n, 4) float32, nrmw (n, 4) float32, tri (m, 3) int32, and with colour
+        rgba (n, 4) uint8)."""
+        n, m = C.c_long(0), C.c_long(0)
+        L.check(self.lib.odo_mesh_weld_download(self.h, 0, 0, None, None, None, None, C.byref(n), C.byref(m)), "odo_mesh_weld_download")
+        nv, nt = n.value, m.value   # (exact buffers: this thread enqueues nothing between the two calls)
+        out = dict(xyz0=np.zeros((nv, 4), np.float32), nrmw=np.zeros((nv, 4), np.float32), tri=np.zeros((nt, 3), np.int32))
+        if colour:
+            out["rgba"] = np.zeros((nv, 4), np.uint8)
+        if nv or nt:
+            vp = lambda a: a.ctypes.data_as(C.c_void_p)
+            L.check(self.lib.odo_mesh_weld_download(self.h, nv, nt, vp(out["xyz0"]), vp(out["nrmw"]), vp(out["rgba"]) if colour else None,
+                                                    vp(out["tri"]), C.byref(n), C.byref(m)), "odo_mesh_weld_download")
+        return out
+
+    def run(self, xyz0, nrmw, tri, rgba=None, eps=None, origin=(0.0, 0.0, 0.0), grids=8, drop_unreferenced=True):
+        """Host arrays in, a dict out: xyz0 and nrmw (n, 4) float32, tri (m, 3) int32, rgba (n, 4) uint8 or None -> dict(xyz0, nrmw,
+        tri, rgba when given, stats)."""
+        xyz0, nrmw = _f32(xyz0).reshape(-1, 4), _f32(nrmw).reshape(-1, 4)
+        tri = np.ascontiguousarray(tri, np.int32).reshape(-1, 3)
+        if len(nrmw) != len(xyz0):
+            raise ValueError("xyz0 and nrmw differ in length")
+        if rgba is not None:
+            rgba = np.ascontiguousarray(rgba, np.uint8).reshape(-1, 4)
+            if len(rgba) != len(xyz0):
+                raise ValueError("xyz0 and rgba differ in length")
+        nv, nt = len(xyz0), len(tri)
+        out = dict(xyz0=np.zeros((max(nv, 1), 4), np.float32), nrmw=np.zeros((max(nv, 1), 4), np.float32),
+                   tri=np.zeros((max(nt, 1), 3), np.int32))
+        if rgba is not None:
+            out["rgba"] = np.zeros((max(nv, 1), 4), np.uint8)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+        n, m = C.c_long(0), C.c_long(0)
+        L.check(self.lib.odo_mesh_weld_run(self.h, C.byref(self.rule(eps, origin, grids, drop_unreferenced)), nv, nt, vp(xyz0), vp(nrmw),
+                                           vp(rgba), vp(tri), nv, nt, vp(out["xyz0"]), vp(out["nrmw"]), vp(out.get("rgba")) if nv else None,
+                                           vp(out["tri"]), C.byref(n), C.byref(m)), "odo_mesh_weld_run")
+        out = {k: (v[:m.value] if k == "tri" else v[:n.value]).copy() for k, v in out.items()}
+        out["stats"] = self.stats()
+        return out
+
+    def stats(self):
+        """The last run's exact counters by name (waits for it)."""
+        o = (C.c_long * 12)()
+        L.check(self.lib.odo_mesh_weld_stats(self.h, o), "odo_mesh_weld_stats")
+        return dict(zip(self.STATS, list(o)))
+
+    def time(self, n_vertices, n_triangles, xyz0_dev, nrmw_dev, tri_dev, rgba_dev=None, eps=None, origin=(0.0, 0.0, 0.0), grids=8,
+             drop_unreferenced=True, reps=20):
+        """Mean microseconds of each group of launches, summed over the passes, and their sum (a diagnostic: tools/mesh_weld_cost.py):
+        dict(vertex_table, representatives, triangle_table, survivors, scans, scatters, run). The welder holds one run's result
+        afterwards."""
+        us = (C.c_float * 7)()
+        L.check(self.lib.odo_mesh_weld_time_dev(self.h, C.byref(self.rule(eps, origin, grids, drop_unreferenced)), int(n_vertices),
+                                                int(n_triangles), xyz0_dev, nrmw_dev, rgba_dev, tri_dev, int(reps), us),
+                "odo_mesh_weld_time_dev")
+        return dict(zip(self.GROUPS, list(us)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.odo_mesh_weld_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -3335,6 +3335,7 @@ extern "C" int odo_depth_report(const odo_depth* d, int* iters, float* cost, int
 #include "rgbd_frontend_api.hip.h"
 #include "depth_filter_api.hip.h"
 #include "speckle_api.hip.h"
+#include "mesh_weld_api.hip.h"
 #include "stereo_depth_api.hip.h"
 #include "rgbd.hip.h"
 #include "tracker.hip.h"
