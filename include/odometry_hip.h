@@ -1363,6 +1363,91 @@ int odo_mesh_weld_time_dev(odo_mesh_weld* w, const odo_mesh_weld_rule* rule, lon
 /* Safe with a run in flight: waits for ctx's stream first. */
 int odo_mesh_weld_destroy(odo_mesh_weld* w);
 
+/* ---- Mesh component filter: small connected pieces leave an indexed mesh, exact to the last bit ----------------------------------
+ * Input: n_v vertices (xyz0 float4, nrmw float4, optionally rgba uint8[4]) and n_t triangles (int32[3]) on the device, as the
+ * welder's odo_mesh_weld_result_dev gives them. A rule: min_triangles >= 0, keep_largest in {0, 1}, drop_unreferenced in {0, 1}.
+ *   Valid         a triangle is valid iff its three indices lie in [0, n_v). An invalid one is dropped and counted bad_index; its
+ *                 indices are never dereferenced and its label is -1. A valid triangle with two equal indices is degenerate: it
+ *                 counts towards its component's size, stays or leaves with it like any other, and contributes no edge (a, a).
+ *   Component     valid triangles that share a vertex index are connected (vertex connectivity: two tetrahedra that touch in one
+ *                 vertex are one component). A component's label is its smallest vertex index, its size its number of valid
+ *                 triangles.
+ *   Survival      a component survives iff size >= min_triangles (a size equal to the bound stays) and, with keep_largest, it is
+ *                 the component of the largest size, of several the one with the smallest label. If the largest is below
+ *                 min_triangles nothing survives and the result is an empty mesh.
+ *   Output        the surviving triangles in input order, their indices renumbered. The vertices kept are those a surviving
+ *                 triangle names and, without drop_unreferenced, also those no valid triangle names; in ascending index, each with
+ *                 its own xyz0, nrmw and rgba bit for bit. Per input triangle a label (int32): odo_mesh_components_labels.
+ *   Edges         (only on a filter created with edge_stats = 1) the undirected edges a != b of the valid triangles, each with its
+ *                 number of uses; an edge lies in exactly one component.
+ * Counters (odo_mesh_components_stats, in this order): vertices_in, triangles_in, vertices_out, triangles_out; components,
+ * removed_components, removed_triangles, removed_vertices (the vertices of the removed components), largest (the size of the
+ * largest component), bad_index, degenerate, unreferenced (vertices no valid triangle names that were dropped; 0 without
+ * drop_unreferenced), so that triangles_out = triangles_in - removed_triangles - bad_index and vertices_out = vertices_in -
+ * removed_vertices - unreferenced; edges, open_edges (used once), nonmanifold_edges (used more than twice) of the input, and
+ * edges_out, open_edges_out, nonmanifold_edges_out of the edges whose component survives (all six 0 without edge_stats); guard (0;
+ * see below).
+ * Nothing depends on timing: a root is the smallest index of its component whatever the order of the unions (the larger root goes
+ * under the smaller with an integer atomicMin, a lost race goes on from the word it read), sizes and use counts are integer sums,
+ * the largest is a maximum of size << 32 | ~label, an edge slot is claimed with a 64-bit atomicCAS and never changes its key, and
+ * the compaction is count, scan, scatter. The edge table has 2^ceil(log2(6 triangle_capacity)) slots and is probed linearly from a
+ * splitmix64 hash. Every data-dependent loop carries a hard trip bound — n_v for a walk to a root and for a union, the table's size
+ * for a probe — and a loop that runs into it sets a bit of `guard` and leaves. No loop waits for another
+ * thread. */
+typedef struct odo_mesh_components odo_mesh_components;
+typedef struct {
+  int vertex_capacity, triangle_capacity; /* 1 .. 2^28 each */
+  int colour;                             /* 0 or 1: room for rgba */
+  int edge_stats;                         /* 0 or 1: the edge table and its six counters */
+} odo_mesh_components_params;
+typedef struct {
+  int min_triangles;
+  int keep_largest;
+  int drop_unreferenced;
+} odo_mesh_components_rule;
+/* Validates before it touches the device: -1 with the bound named in the message and *out untouched on any violation, and on an
+ * allocation the device refuses. Device memory, allocated once, in one block: per vertex of capacity 45 B (49 B with colour), per
+ * triangle 16 B, per slot of the edge table 12 B. ctx must outlive the filter. One host thread at a time. */
+int odo_mesh_components_create(odo_ctx* ctx, const odo_mesh_components_params* p, odo_mesh_components** out);
+/* Enqueues the run on ctx's stream and returns at once, no host wait. The inputs are never written. rgba_dev may be NULL (no
+ * colours this run); xyz0_dev / nrmw_dev may be NULL iff n_vertices == 0 and tri_dev iff n_triangles == 0, and either count may be
+ * 0. -1 and nothing enqueued for: NULL where not allowed; min_triangles < 0; keep_largest or drop_unreferenced not 0 or 1; a
+ * negative count or one beyond 2^28; a misaligned pointer (16 bytes for xyz0 and nrmw, 4 for rgba and tri) — all decided before the
+ * filter is read — and for counts beyond the capacities, rgba_dev on a filter without colour, and an input that overlaps the
+ * filter's buffers. Ordering is odo_mesh_weld_run_dev's: the inputs may be the welder's result buffers of a weld enqueued on the
+ * same stream before, and must stay as they are until the run is done. */
+int odo_mesh_components_run_dev(odo_mesh_components* f, const odo_mesh_components_rule* rule, long n_vertices, long n_triangles,
+                                const float* xyz0_dev, const float* nrmw_dev, const uint8_t* rgba_dev, const int32_t* tri_dev);
+/* The last run's result in the filter's own buffers (valid until the next run or destroy; *rgba_dev NULL when the run carried no
+ * colours; any pointer argument may be NULL) and its two counts, for which it waits for ctx's stream. 0, 0 before the first run. */
+int odo_mesh_components_result_dev(odo_mesh_components* f, const float** xyz0_dev, const float** nrmw_dev, const uint8_t** rgba_dev,
+                                   const int32_t** tri_dev, long* n_vertices, long* n_triangles);
+/* Copies the last run's result into host buffers of the given capacities and waits. Capacities 0, 0: the counts alone. Refuses
+ * capacities below the counts (-1, the counts still returned) rather than cutting. rgba may be NULL. */
+int odo_mesh_components_download(odo_mesh_components* f, long vertex_capacity, long triangle_capacity, float* xyz0, float* nrmw,
+                                 uint8_t* rgba, int32_t* tri, long* n_vertices, long* n_triangles);
+/* The host-array convenience: upload (a staging block of this call's own), odo_mesh_components_run_dev,
+ * odo_mesh_components_download. */
+int odo_mesh_components_run(odo_mesh_components* f, const odo_mesh_components_rule* rule, long n_vertices, long n_triangles,
+                            const float* xyz0, const float* nrmw, const uint8_t* rgba, const int32_t* tri, long vertex_capacity,
+                            long triangle_capacity, float* out_xyz0, float* out_nrmw, uint8_t* out_rgba, int32_t* out_tri,
+                            long* out_vertices, long* out_triangles);
+/* The last run's labels, one int32 per INPUT triangle (its component's smallest vertex index, -1 for an invalid triangle), in the
+ * filter's own buffer, and their number: that run's n_triangles (0 before the first run). Does not wait. */
+int odo_mesh_components_labels_dev(odo_mesh_components* f, const int32_t** labels_dev, long* n_triangles);
+/* Copies them to the host and waits. capacity 0: the count alone; a capacity below the count is refused. */
+int odo_mesh_components_labels(odo_mesh_components* f, long capacity, int32_t* labels, long* n_triangles);
+/* Of the last run, exact, in the order above. Waits for ctx's stream. Zeros before the first run. */
+int odo_mesh_components_stats(odo_mesh_components* f, long out[19]);
+/* Diagnostic: each of the six groups of launches `reps` (1 .. 10000) times between two events on ctx's stream; us[0 .. 5] = the mean
+ * time in microseconds of union / flatten + sizes + largest / edge table + census / survivors / scans / scatters (clears
+ * included), us[6] = their sum. Waits. Then one run: the outputs, the labels and the statistics are exactly one run's afterwards. */
+int odo_mesh_components_time_dev(odo_mesh_components* f, const odo_mesh_components_rule* rule, long n_vertices, long n_triangles,
+                                 const float* xyz0_dev, const float* nrmw_dev, const uint8_t* rgba_dev, const int32_t* tri_dev,
+                                 int reps, float us[7]);
+/* Safe with a run in flight: waits for ctx's stream first. */
+int odo_mesh_components_destroy(odo_mesh_components* f);
+
 /* ---- S sequences in lock step on one GPU (the data-parallel axis of SURVEY section 8e inside one device) -----------------
  * One odo_tracker tracks one sequence as a serial chain of ~70 short launches per frame, which leaves most of the chip
  * idle. odo_tracker_batch runs the same frame loop (ref: run_odometry_kitti_offline.cpp:198-271) for n_sequences independent

@@ -66,6 +66,14 @@ class MeshWeldRule(C.Structure):
     _fields_ = [("eps", C.c_float), ("origin", C.c_float * 3), ("grids", C.c_int), ("drop_unreferenced", C.c_int)]
 
 
+class MeshComponentsParams(C.Structure):
+    _fields_ = [("vertex_capacity", C.c_int), ("triangle_capacity", C.c_int), ("colour", C.c_int), ("edge_stats", C.c_int)]
+
+
+class MeshComponentsRule(C.Structure):
+    _fields_ = [("min_triangles", C.c_int), ("keep_largest", C.c_int), ("drop_unreferenced", C.c_int)]
+
+
 class VolumeParams(C.Structure):
     _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("voxel_size", C.c_float), ("origin", C.c_float * 3),
                 ("mu", C.c_float), ("max_depth", C.c_float), ("max_weight", C.c_int), ("rows", C.c_int), ("cols", C.c_int),
@@ -369,6 +377,18 @@ SIGNATURES = {
     "odo_mesh_weld_stats": (C.c_int, [_vp, C.POINTER(C.c_long)]),
     "odo_mesh_weld_time_dev": (C.c_int, [_vp, C.POINTER(MeshWeldRule), C.c_long, C.c_long, _vp, _vp, _vp, _vp, C.c_int, _fp]),
     "odo_mesh_weld_destroy": (C.c_int, [_vp]),
+    "odo_mesh_components_create": (C.c_int, [_vp, C.POINTER(MeshComponentsParams), C.POINTER(_vp)]),
+    "odo_mesh_components_run_dev": (C.c_int, [_vp, C.POINTER(MeshComponentsRule), C.c_long, C.c_long, _vp, _vp, _vp, _vp]),
+    "odo_mesh_components_result_dev": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_long),
+                                                 C.POINTER(C.c_long)]),
+    "odo_mesh_components_download": (C.c_int, [_vp, C.c_long, C.c_long, _vp, _vp, _vp, _vp, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "odo_mesh_components_run": (C.c_int, [_vp, C.POINTER(MeshComponentsRule), C.c_long, C.c_long, _vp, _vp, _vp, _vp, C.c_long, C.c_long,
+                                          _vp, _vp, _vp, _vp, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "odo_mesh_components_labels_dev": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(C.c_long)]),
+    "odo_mesh_components_labels": (C.c_int, [_vp, C.c_long, _vp, C.POINTER(C.c_long)]),
+    "odo_mesh_components_stats": (C.c_int, [_vp, C.POINTER(C.c_long)]),
+    "odo_mesh_components_time_dev": (C.c_int, [_vp, C.POINTER(MeshComponentsRule), C.c_long, C.c_long, _vp, _vp, _vp, _vp, C.c_int, _fp]),
+    "odo_mesh_components_destroy": (C.c_int, [_vp]),
 }
 
 _lib = None

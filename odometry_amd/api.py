@@ -1541,6 +1541,55 @@ class TsdfVolume:
         write_ply_mesh(path, m["xyz0"], m["nrmw"], m["tri"], rgb=m["rgba"] if colour else None)
         return m["stats"]
 
+    def cleaned_mesh(self, eps=None, grids=8, spill=True, colour=False, min_triangles=128, keep_largest=False):
+        """welded_mesh()'s mesh without its small pieces (MeshComponents): the same inputs go through
+        MeshWeld.run_dev, the welder's result stays on the device and MeshComponents.run_dev reads it there; components of fewer
+        than min_triangles triangles leave (with keep_largest every component but the largest). dict(xyz0, nrmw, tri, rgba with
+        colour, stats, weld_stats). Waits."""
+        spill = bool(spill) and self._has_spill_mesh
+        if spill and colour and not self._spill_mesh_colour:
+            raise ValueError("cleaned_mesh(colour=True): the mesh store was enabled before enable_colour and holds no colours, the "
+                             "mesh has them; call enable_colour before enable_spill_mesh")
+        parts = self.mesh(colour=True) if colour else self.mesh()
+        if spill:
+            store = self.spilled_mesh(colour=colour)
+            parts = tuple(np.concatenate([a, b + len(store[0])]) if i == 2 else np.concatenate([a, b])
+                          for i, (a, b) in enumerate(zip(store, parts)))
+        eps = np.float32(self.params.voxel_size) / np.float32(64.0) if eps is None else eps
+        nv, nt = len(parts[0]), len(parts[2])
+        ctx = self._owner._ctx if isinstance(self._owner, Tracker) else self._owner.h
+        w = MeshWeld(self._owner, max(nv, 1), max(nt, 1), colour=colour)
+        f = MeshComponents(self._owner, max(nv, 1), max(nt, 1), colour=colour)
+        held = []
+        try:
+            for a in (_f32(parts[0]), _f32(parts[1]), np.ascontiguousarray(parts[2], np.int32)) + \
+                    ((np.ascontiguousarray(parts[3], np.uint8),) if colour else ()):
+                d = C.c_void_p()
+                L.check(self.lib.odo_dev_alloc(ctx, max(a.nbytes, 16), C.byref(d)), "odo_dev_alloc")
+                held.append(d)
+                if a.nbytes:
+                    L.check(self.lib.odo_dev_upload(ctx, d, a.ctypes.data_as(C.c_void_p), a.nbytes), "odo_dev_upload")
+            w.run_dev(nv, nt, held[0], held[1], held[2], held[3] if colour else None, eps=eps, origin=tuple(self.params.origin),
+                      grids=grids, drop_unreferenced=True)
+            x, n, c, t, wv, wt = w.result_dev()
+            f.run_dev(wv, wt, x, n, t, c, min_triangles=min_triangles, keep_largest=keep_largest, drop_unreferenced=True)
+            out = f.download(colour=colour)
+            out["stats"], out["weld_stats"] = f.stats(), w.stats()
+            return out
+        finally:
+            f.close()
+            w.close()
+            for d in held:
+                self.lib.odo_dev_free(ctx, d)
+
+    def save_cleaned_mesh_ply(self, path, eps=None, grids=8, spill=True, min_triangles=128, keep_largest=False):
+        """cleaned_mesh() as a binary little-endian PLY, through write_ply_mesh, as save_welded_mesh_ply writes welded_mesh().
+        Returns the filter's counters."""
+        colour = self.has_colour
+        m = self.cleaned_mesh(eps=eps, grids=grids, spill=spill, colour=colour, min_triangles=min_triangles, keep_largest=keep_largest)
+        write_ply_mesh(path, m["xyz0"], m["nrmw"], m["tri"], rgb=m["rgba"] if colour else None)
+        return m["stats"]
+
     def close(self):
         if getattr(self, "h", None):
             if self._tracker is not None and getattr(self._tracker, "h", None):
@@ -2054,6 +2103,140 @@ class MeshWeld:
     def close(self):
         if getattr(self, "h", None):
             self.lib.odo_mesh_weld_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MeshComponents:
+    """The mesh component filter on the device (odo_mesh_components_*): valid triangles that share a vertex index are one component,
+    its label its smallest vertex index; components of fewer than min_triangles triangles leave (with keep_largest all but the
+    largest), the vertices and triangles that stay are renumbered, in exact integers (include/odometry_hip.h). Every launch goes to
+    the context's stream; the input may be a MeshWeld's result_dev() pointers. ctx_or_tracker: a Context, or a Tracker (its
+    context). edge_stats: count the edges used once and more than twice, before and after."""
+
+    STATS = ("vertices_in", "triangles_in", "vertices_out", "triangles_out", "components", "removed_components", "removed_triangles",
+             "removed_vertices", "largest", "bad_index", "degenerate", "unreferenced", "edges", "open_edges", "nonmanifold_edges",
+             "edges_out", "open_edges_out", "nonmanifold_edges_out", "guard")
+    GROUPS = ("union", "sizes", "edges", "survivors", "scans", "scatters", "run")
+
+    def __init__(self, ctx_or_tracker, vertex_capacity, triangle_capacity, colour=False, edge_stats=True):
+        self.lib = L.load()
+        self._owner = ctx_or_tracker   # keeps the stream's owner alive as long as the filter
+        self._ctx = ctx_or_tracker._ctx if isinstance(ctx_or_tracker, Tracker) else ctx_or_tracker.h
+        p = L.MeshComponentsParams(int(vertex_capacity), int(triangle_capacity), int(bool(colour)), int(bool(edge_stats)))
+        self.params = p
+        self.h = None
+        h = C.c_void_p()
+        L.check(self.lib.odo_mesh_components_create(self._ctx, C.byref(p), C.byref(h)), "odo_mesh_components_create")
+        self.h = h
+
+    @staticmethod
+    def rule(min_triangles, keep_largest=False, drop_unreferenced=True):
+        if min_triangles is None:
+            raise ValueError("MeshComponents: min_triangles is required (the smallest component that stays)")
+        return L.MeshComponentsRule(int(min_triangles), int(bool(keep_largest)), int(bool(drop_unreferenced)))
+
+    def run_dev(self, n_vertices, n_triangles, xyz0_dev, nrmw_dev, tri_dev, rgba_dev=None, min_triangles=None, keep_largest=False,
+                drop_unreferenced=True):
+        """Enqueues the filter on a mesh on the device and returns at once; the result stays in the filter's buffers (result_dev,
+        download, labels)."""
+        L.check(self.lib.odo_mesh_components_run_dev(self.h, C.byref(self.rule(min_triangles, keep_largest, drop_unreferenced)),
+                                                     int(n_vertices), int(n_triangles), xyz0_dev, nrmw_dev, rgba_dev, tri_dev),
+                "odo_mesh_components_run_dev")
+
+    def result_dev(self):
+        """(xyz0, nrmw, rgba or None, tri, n_vertices, n_triangles) of the last run: device pointers into the filter's buffers and
+        the two counts (waits for them)."""
+        p = [C.c_void_p() for _ in range(4)]
+        n, m = C.c_long(0), C.c_long(0)
+        L.check(self.lib.odo_mesh_components_result_dev(self.h, *[C.byref(x) for x in p], C.byref(n), C.byref(m)),
+                "odo_mesh_components_result_dev")
+        return p[0], p[1], (p[2] if p[2].value else None), p[3], n.value, m.value
+
+    def download(self, colour=False):
+        """The last run's result on the host (waits): dict(xyz0 (n, 4) float32, nrmw (n, 4) float32, tri (m, 3) int32, and with colour
+        rgba (n, 4) uint8)."""
+        n, m = C.c_long(0), C.c_long(0)
+        L.check(self.lib.odo_mesh_components_download(self.h, 0, 0, None, None, None, None, C.byref(n), C.byref(m)),
+                "odo_mesh_components_download")
+        nv, nt = n.value, m.value   # (exact buffers: this thread enqueues nothing between the two calls)
+        out = dict(xyz0=np.zeros((nv, 4), np.float32), nrmw=np.zeros((nv, 4), np.float32), tri=np.zeros((nt, 3), np.int32))
+        if colour:
+            out["rgba"] = np.zeros((nv, 4), np.uint8)
+        if nv or nt:
+            vp = lambda a: a.ctypes.data_as(C.c_void_p)
+            L.check(self.lib.odo_mesh_components_download(self.h, nv, nt, vp(out["xyz0"]), vp(out["nrmw"]),
+                                                          vp(out["rgba"]) if colour else None, vp(out["tri"]), C.byref(n), C.byref(m)),
+                    "odo_mesh_components_download")
+        return out
+
+    def run(self, xyz0, nrmw, tri, rgba=None, min_triangles=None, keep_largest=False, drop_unreferenced=True):
+        """Host arrays in, a dict out: xyz0 and nrmw (n, 4) float32, tri (m, 3) int32, rgba (n, 4) uint8 or None -> dict(xyz0, nrmw,
+        tri, rgba when given, labels (one per input triangle), stats)."""
+        xyz0, nrmw = _f32(xyz0).reshape(-1, 4), _f32(nrmw).reshape(-1, 4)
+        tri = np.ascontiguousarray(tri, np.int32).reshape(-1, 3)
+        if len(nrmw) != len(xyz0):
+            raise ValueError("xyz0 and nrmw differ in length")
+        if rgba is not None:
+            rgba = np.ascontiguousarray(rgba, np.uint8).reshape(-1, 4)
+            if len(rgba) != len(xyz0):
+                raise ValueError("xyz0 and rgba differ in length")
+        nv, nt = len(xyz0), len(tri)
+        out = dict(xyz0=np.zeros((max(nv, 1), 4), np.float32), nrmw=np.zeros((max(nv, 1), 4), np.float32),
+                   tri=np.zeros((max(nt, 1), 3), np.int32))
+        if rgba is not None:
+            out["rgba"] = np.zeros((max(nv, 1), 4), np.uint8)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+        n, m = C.c_long(0), C.c_long(0)
+        L.check(self.lib.odo_mesh_components_run(self.h, C.byref(self.rule(min_triangles, keep_largest, drop_unreferenced)), nv, nt,
+                                                 vp(xyz0), vp(nrmw), vp(rgba), vp(tri), nv, nt, vp(out["xyz0"]), vp(out["nrmw"]),
+                                                 vp(out.get("rgba")) if nv else None, vp(out["tri"]), C.byref(n), C.byref(m)),
+                "odo_mesh_components_run")
+        out = {k: (v[:m.value] if k == "tri" else v[:n.value]).copy() for k, v in out.items()}
+        out["labels"] = self.labels()
+        out["stats"] = self.stats()
+        return out
+
+    def labels_dev(self):
+        """(device pointer to the last run's labels, their number): one int32 per input triangle. Does not wait."""
+        p, n = C.c_void_p(), C.c_long(0)
+        L.check(self.lib.odo_mesh_components_labels_dev(self.h, C.byref(p), C.byref(n)), "odo_mesh_components_labels_dev")
+        return p, n.value
+
+    def labels(self):
+        """The last run's label per input triangle (waits): its component's smallest vertex index, -1 for an invalid triangle."""
+        n = C.c_long(0)
+        L.check(self.lib.odo_mesh_components_labels(self.h, 0, None, C.byref(n)), "odo_mesh_components_labels")
+        out = np.zeros(n.value, np.int32)
+        if n.value:
+            L.check(self.lib.odo_mesh_components_labels(self.h, n.value, out.ctypes.data_as(C.c_void_p), C.byref(n)),
+                    "odo_mesh_components_labels")
+        return out
+
+    def stats(self):
+        """The last run's exact counters by name (waits for it)."""
+        o = (C.c_long * 19)()
+        L.check(self.lib.odo_mesh_components_stats(self.h, o), "odo_mesh_components_stats")
+        return dict(zip(self.STATS, list(o)))
+
+    def time(self, n_vertices, n_triangles, xyz0_dev, nrmw_dev, tri_dev, rgba_dev=None, min_triangles=None, keep_largest=False,
+             drop_unreferenced=True, reps=20):
+        """Mean microseconds of each group of launches and their sum (a diagnostic: tools/mesh_components_cost.py): dict(union,
+        sizes, edges, survivors, scans, scatters, run). The filter holds one run's result afterwards."""
+        us = (C.c_float * 7)()
+        L.check(self.lib.odo_mesh_components_time_dev(self.h, C.byref(self.rule(min_triangles, keep_largest, drop_unreferenced)),
+                                                      int(n_vertices), int(n_triangles), xyz0_dev, nrmw_dev, rgba_dev, tri_dev, int(reps),
+                                                      us), "odo_mesh_components_time_dev")
+        return dict(zip(self.GROUPS, list(us)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.odo_mesh_components_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -53,7 +53,7 @@ UNITS = [(SRC, ""), (SRC_DENSE, SCHED_DENSE), (SRC_CHAIN, SCHED_CHAIN)] + [(os.p
     "map_kernels.hip", "rgbd_kernels.hip", "rgbd_frontend_kernels.hip", "volume_kernels.hip", "volume_mesh_kernels.hip",
     "volume_colour_kernels.hip", "volume_raycast_kernels.hip", "volume_icp_kernels.hip", "volume_shift_kernels.hip",
     "depth_filter_kernels.hip", "volume_reentry_kernels.hip", "stereo_depth_kernels.hip", "speckle_kernels.hip",
-    "stereo_sgm_kernels.hip", "mesh_weld_kernels.hip")]
+    "stereo_sgm_kernels.hip", "mesh_weld_kernels.hip", "mesh_components_kernels.hip")]
 
 
 def _flags_for(src, flags):

@@ -3336,6 +3336,7 @@ extern "C" int odo_depth_report(const odo_depth* d, int* iters, float* cost, int
 #include "depth_filter_api.hip.h"
 #include "speckle_api.hip.h"
 #include "mesh_weld_api.hip.h"
+#include "mesh_components_api.hip.h"
 #include "stereo_depth_api.hip.h"
 #include "rgbd.hip.h"
 #include "tracker.hip.h"
